@@ -606,6 +606,45 @@ def measured_traffic(workload):
     return None, None
 
 
+DUMP_SAMPLE_VALUES = 1 << 21  # conserved values sampled over the whole mesh: 16 MB of values + 16 MB of their indices
+DUMP_SEED = 20261015
+
+
+def dump_outputs(sim, outdir, rank, world):
+    """--dump-outputs DIR: the state the timed cycles left behind, as float64 .npy files, so that two builds can be
+    compared output for output.  The conserved state of a 256^3 brick is 1.4 GB with its ghost zones, so every meshblock
+    contributes the same seeded sample of its interior values (cons_sample); cons_sample_index holds the flat index of
+    each one, gid * (values per block) + position in the block's (var, k, j, i) interior.  history: the volume sums of
+    the deck's history output over the whole mesh; time_dt_ncycle: the simulation time, the next time step and the
+    cycle count.  On N > 1 ranks every rank writes the sample of its own blocks (suffix _rank<r>); this is collective
+    there (read_block and history complete the ghost zones first)."""
+    import numpy as np
+    info = sim.info
+    ng = int(info.ng)
+    nvar, nk, nj, ni = sim.block_shape
+    interior = (slice(None),) + tuple(slice(ng, n - ng) if n > 1 else slice(None) for n in (nk, nj, ni))
+    per_block = nvar * int(np.prod([n - 2 * ng if n > 1 else 1 for n in (nk, nj, ni)]))
+    k = min(per_block, max(1, DUMP_SAMPLE_VALUES // int(info.nblocks_total)))
+    vals, idx = [], []
+    for gid, lb in sorted((sim.block_gid(lb)[0], lb) for lb in range(int(info.nblocks_local))):
+        u = sim.read_block(lb, "cons")[interior].reshape(-1)
+        pick = np.sort(np.random.default_rng([DUMP_SEED, gid]).choice(per_block, k, replace=False))
+        vals.append(u[pick])
+        idx.append(gid * per_block + pick)
+    hist = sim.history()
+    suffix = "" if world == 1 else "_rank%d" % rank
+    arrays = {"cons_sample" + suffix: np.concatenate(vals).astype(np.float64),
+              "cons_sample_index" + suffix: np.concatenate(idx).astype(np.float64)}
+    if rank == 0:
+        arrays["history"] = np.asarray(hist, dtype=np.float64)
+        arrays["time_dt_ncycle"] = np.array([sim.time, sim.dt, float(sim.ncycle)], dtype=np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": os.path.abspath(outdir), "files": sorted(n + ".npy" for n in arrays), "values_per_block": k,
+            "seed": DUMP_SEED}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -627,6 +666,9 @@ def main():
     ap.add_argument("--amr-extra", action="store_true",
                     help="append the adaptive-mesh figure (BASELINE config 5 shape) as 'amr_blast_cfg5'; off by default so "
                          "that the kernels of the default command are those of the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (a seeded sample of the conserved state, the "
+                         "history sums, time / dt / cycle) as DIR/<name>.npy, float64, 32 MB at most")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC (RCCL across processes)
@@ -735,6 +777,8 @@ def main():
     med = sorted(range(len(regions)), key=lambda q: regions[q])[len(regions) // 2]
     elapsed = regions[med]
     comm_after = sim.comm_stats() if world > 1 else None
+    # the state the last timed step left (read after the timing, before any further cycle)
+    dumped = dump_outputs(sim, args.dump_outputs, rank, world) if args.dump_outputs else None
     sim.kernel_timing(True)
     sim.read_kernel_timing()
     barrier()
@@ -898,6 +942,8 @@ def main():
                                         "stands for, NOT the north-star roofline fraction (that is `frac` / `general_stage.frac`)"},
             },
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         if sustained:
             out["sustained_%d_cycles" % sustained["cycles"]] = sustained
         if copies_base:

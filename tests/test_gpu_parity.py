@@ -30,8 +30,12 @@ def _cmp(got, want, strict, what):
             raise AssertionError("%s: %d entries differ bitwise, first at %s: %r vs %r" % (
                 what, len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
     else:
-        scale = np.max(np.abs(want)) + 1e-300
-        err = np.max(np.abs(got - want)) / scale
+        # non-finite entries (rough data) where the oracle has them; every finite one within FAST_TOL
+        bad, wbad = ~np.isfinite(got), ~np.isfinite(want)
+        assert np.array_equal(bad, wbad), "%s: %d non-finite entries, the oracle %d, in %d different places" % (
+            what, bad.sum(), wbad.sum(), (bad != wbad).sum())
+        scale = np.max(np.abs(want[~wbad]), initial=0.0) + 1e-300
+        err = np.max(np.abs(got[~wbad] - want[~wbad]), initial=0.0) / scale
         assert err <= FAST_TOL, "%s: max scaled error %.3e" % (what, err)
 
 
@@ -1105,8 +1109,6 @@ def test_fused_stage_with_passive_scalars(request, oracle, fluid, recon, riemann
     from athenapk_amd import hydro, lib as L
     ctx = _ctx(request, strict)
     ndim = sum(1 for n in nx if n > 1)
-    if fill and ndim == 1:
-        pytest.skip("FillDerived is not fused in 1-D")
     ng, prim, g = _case(fluid, recon, nx, kind="smooth", nscalars=2, seed=61)
     cons = H.prim_to_cons(fluid, prim, GAMMA)
     u1c = cons * 1.02
@@ -1117,6 +1119,15 @@ def test_fused_stage_with_passive_scalars(request, oracle, fluid, recon, riemann
                         with_flux=False)
     m1 = hydro.MeshData(ctx, nx, ng, nh, nscalars=2, dx=tuple(g.dx), nblocks=prim.shape[0], cons=u1c,
                         prim=np.full_like(prim, -7.0), with_flux=False)
+    if fill and ndim == 1:
+        # FillDerived is not fused in 1-D: the stage is refused before anything is written
+        with pytest.raises(L.ApkError) as e:
+            hydro.StageFused(m0, m1, fluid, recon, riemann, L.make_eos(GAMMA, **eos_kw), C_H, 0.5, 0.5, 0.004, dedner=ded,
+                             glmmhd_alpha=0.1, mindx=0.07, fill_derived=fill)
+        assert e.value.code == L.APK_ERR_UNSUPPORTED
+        assert np.array_equal(m0.cons_host(), cons) and np.array_equal(m1.cons_host(), u1c)
+        assert np.array_equal(m0.prim_host(), prim) and np.all(m1.prim_host() == -7.0)
+        return
     hydro.StageFused(m0, m1, fluid, recon, riemann, L.make_eos(GAMMA, **eos_kw), C_H, 0.5, 0.5, 0.004, dedner=ded,
                      glmmhd_alpha=0.1, mindx=0.07, fill_derived=fill)
     want = H.orc_stage(fluid, recon, riemann, g, cons, u1c, prim, GAMMA, C_H, 0.5, 0.5, 0.004, dedner=ded, alpha=0.1,
@@ -1365,9 +1376,6 @@ def test_two_kernel_stage_takes_its_input_from_the_conserved_state(request, orac
     import ctypes as C
     import torch
     from athenapk_amd import hydro
-    if kind == "rough" and not strict:
-        pytest.skip("uniform random states reconstruct negative pressures here and there: NaNs, which only the parity build "
-                    "is asked to reproduce place for place (as in the registry tests on rough data)")
     ctx = _ctx(request, strict)
     # (hydro PLM takes the single-march form of these stages -- fused3_kernel.hpp -- which wants an even number of x2 rows)
     nx = (36, 10, 9) if fluid == "euler" else (36, 9, 10)
@@ -1426,7 +1434,14 @@ def test_two_kernel_stage_takes_its_input_from_the_conserved_state(request, orac
         # a NaN density, `(u_d > floor) ? u_d : floor`): the stored state is the oracle's AFTER its ConsToPrim
         want = H.orc_c2p(fluid, g, want, oracle.make_eos(GAMMA))[0]
     got = (m2 if own_input else m0).cons_host()
-    _cmp(H.interior(got, nx, ng), H.interior(want, nx, ng), strict, "updated conserved state")
+    if rough and not strict and fluid == "glmmhd":
+        # the product build's rcp / rsq-based roots (csrc/Makefile FASTFP) meet the negative reconstructed pressures of
+        # uniform random states differently, and the HLLD branches of the faces around them with them: no cell-for-cell
+        # reference there (the parity build pins these values); it may not produce more non-finite entries than the
+        # exact arithmetic, and everything below -- what is written, what is left alone, the refusals -- holds as well
+        assert (~np.isfinite(H.interior(got, nx, ng))).sum() <= (~np.isfinite(H.interior(want, nx, ng))).sum()
+    else:
+        _cmp(H.interior(got, nx, ng), H.interior(want, nx, ng), strict, "updated conserved state")
     if own_input:
         assert np.array_equal(m0.cons_host(), u0c, equal_nan=True), "u0.cons is the stage's input: it must stay as it was"
         ghosts = np.ones(got.shape, dtype=bool)

@@ -3,10 +3,12 @@ peer on a dedicated HIP stream, ncclAllReduce on a second communicator.
 
 * one GPU is enough for the self test: rank 0 sends to itself through the same code path (library
   lookup, two communicators, event ordering against the sim's stream, reductions);
-* the 2-rank cases need two GPUs (RCCL refuses two ranks on one device) and are skipped on one-GPU
-  boxes: they run the driver on device buffers over backend nccl with the native transport and must
+* the 2-rank cases run the driver on device buffers over backend nccl with the native transport and must
   equal the oracle's single-process run bit for bit -- the same cases test_gpu_two_ranks.py runs over
-  gloo with ranks sharing a GPU."""
+  gloo with ranks sharing a GPU.  They need two GPUs: RCCL refuses two ranks on one device.  On a
+  one-GPU box the same cases ask for the native transport on two ranks sharing the GPU (process group
+  gloo): its communicators cannot be created, and every rank must fall back to the torch.distributed
+  callbacks together (driver.Simulation) and still equal the oracle bit for bit."""
 import ctypes as C
 import os
 import sys
@@ -31,27 +33,31 @@ def test_rccl_transport_self_test_on_one_gpu(n):
     assert rc == L.APK_OK and msg.value == b"ok", msg.value
 
 
-def _worker(rank, world, port, case, outdir, overlap):
+def _worker(rank, world, port, case, outdir, overlap, shared=False):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
     import torch.distributed as dist
     from athenapk_amd import decks, driver
     from test_gpu_two_ranks import CASES
-    torch.cuda.set_device(rank)
+    dev = 0 if shared else rank
+    torch.cuda.set_device(dev)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world,
-                            device_id=torch.device("cuda", rank))
+    if shared:
+        dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    else:
+        dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world,
+                                device_id=torch.device("cuda", dev))
     try:
         deck, ov, _, _, _, ncyc = CASES[case]
         s = driver.Simulation(decks.load(deck), ov, rank=rank, nranks=world, strict=True, comm="rccl")
-        assert s.comm_kind == "rccl"
+        assert s.comm_kind == ("torch" if shared else "rccl")
         s.set_overlap(overlap)
         s.initialize()
         for _ in range(ncyc):
             s.step()
-        ex, red = C.c_longlong(0), C.c_longlong(0)
-        s.lib.apk_sim_comm_stats(s.h, C.byref(ex), C.byref(red))
+        stats = s.comm_stats()
+        ex, red = C.c_longlong(stats["exchanges"]), C.c_longlong(stats["reductions"])
         blocks = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
         np.savez(os.path.join(outdir, "rank%d.npz" % rank), time=s.time, dt=s.dt, hist=s.history(), exchanges=ex.value,
                  reductions=red.value, overlapped=s.overlapped_exchanges, **{"b%d" % g: a for g, a in blocks.items()})
@@ -68,7 +74,6 @@ def _ngpus():
         return 0
 
 
-@pytest.mark.skipif(_ngpus() < 2, reason="RCCL needs one GPU per rank")
 @pytest.mark.parametrize("overlap", [True, False])
 @pytest.mark.parametrize("case", ["mhd_ppm_hlld_vl2", "mhd_ppm_two_kernel", "mhd_wenoz_hlld_rk3", "sod_outflow"])
 def test_native_rccl_transport_two_gpus_matches_oracle(oracle, tmp_path, case, overlap):
@@ -80,7 +85,8 @@ def test_native_rccl_transport_two_gpus_matches_oracle(oracle, tmp_path, case, o
     o.pgen(pgen, **pkw)
     for _ in range(ncyc):
         o.step()
-    spawn(_worker, lambda port: (2, port, case, str(tmp_path), overlap), 2)
+    shared = _ngpus() < 2   # (one GPU: the native transport cannot start, the callbacks carry the messages)
+    spawn(_worker, lambda port: (2, port, case, str(tmp_path), overlap, shared), 2)
     seen = set()
     for r in range(2):
         z = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
