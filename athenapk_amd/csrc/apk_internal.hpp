@@ -182,6 +182,10 @@ int launch_fofc_mark(const PackView &u0, const PackView &u1, int fluid, double g
                      double gam1, double beta_dt, int attempt, unsigned char *d_mark,
                      unsigned long long *d_count, hipStream_t s);
 int launch_count_unphysical(const PackView &u0, int fluid, unsigned long long *d_count, hipStream_t s);
+// unsplit diffusion (kernels_diffusion.hip); cond: 0 none, 1 isotropic, 2 anisotropic (fixed coefficients)
+int launch_diff_fluxes(const PackView &pv, int cond, bool visc, bool res, double kappa, double sat_prefac, double nu,
+                       double eta, hipStream_t s);
+int launch_cond_dt(const PackView &pv, double kappa, double sat_prefac, unsigned long long *d_min_bits, hipStream_t s);
 int launch_fofc_fix(const PackView &u0, int fluid, double gamma, double c_h,
                     const unsigned char *d_mark, hipStream_t s);
 int launch_copy_regions(const apk_copy_plan &plan, hipStream_t s, int c2p_fluid = 0, const apk_eos *eos = nullptr,

@@ -566,6 +566,76 @@ int apk_estimate_timestep(apk_ctx *ctx, const apk_pack *md, int fluid, const apk
   return APK_OK;
 }
 
+namespace {
+// the subset of CalcDiffFluxes this library implements (diffusion.cpp:18-53 with fixed coefficients)
+int check_diff_cfg(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c) {
+  if (!c) return set_err(ctx, APK_ERR_INVALID, "diffusion: cfg is NULL");
+  if (c->conduction < APK_COND_NONE || c->conduction > APK_COND_ANISOTROPIC || c->viscosity < APK_VISC_NONE ||
+      c->viscosity > APK_VISC_ISOTROPIC || c->resistivity < APK_RES_NONE || c->resistivity > APK_RES_OHMIC)
+    return set_err(ctx, APK_ERR_INVALID, "diffusion: unknown process");
+  if ((c->conduction != APK_COND_NONE && c->conduction_coeff != APK_CONDC_FIXED) ||
+      (c->viscosity != APK_VISC_NONE && c->viscosity_coeff != APK_VISCC_FIXED) ||
+      (c->resistivity != APK_RES_NONE && c->resistivity_coeff != APK_RESC_FIXED))
+    return set_err(ctx, APK_ERR_UNSUPPORTED, "diffusion: only fixed coefficients are supported (Spitzer needs units)");
+  if ((c->resistivity != APK_RES_NONE || c->conduction == APK_COND_ANISOTROPIC) && md->view.nhydro != 9)
+    return set_err(ctx, APK_ERR_INVALID, "diffusion: resistivity and anisotropic conduction need a GLM-MHD pack");
+  if (md->view.ng < 1) return set_err(ctx, APK_ERR_NGHOST, "diffusion: needs one ghost layer");
+  return APK_OK;
+}
+}  // namespace
+
+int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, apk_stream_t stream) {
+  if (!ctx || !md) return set_err(ctx, APK_ERR_INVALID, "apk_calc_diff_fluxes: bad argument");
+  int rc = check_diff_cfg(ctx, md, cfg);
+  if (rc != APK_OK) return rc;
+  for (int d = 0; d < md->view.ndim; ++d)
+    if (!md->have_flux[d]) return set_err(ctx, APK_ERR_INVALID, "apk_calc_diff_fluxes: pack has no flux arrays");
+  rc = launch_diff_fluxes(md->view, cfg->conduction, cfg->viscosity != APK_VISC_NONE, cfg->resistivity != APK_RES_NONE,
+                          cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, cfg->mom_diff_coeff, cfg->ohm_diff_coeff,
+                          as_stream(stream));
+  if (rc != APK_OK) return set_err(ctx, rc, "diffusion flux kernel launch failed", hipGetLastError());
+  return APK_OK;
+}
+
+int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, double cfl_diff,
+                                    double *dt_out, apk_stream_t stream) {
+  if (!ctx || !md || !dt_out) return set_err(ctx, APK_ERR_INVALID, "apk_estimate_diffusion_timestep: bad argument");
+  int rc = check_diff_cfg(ctx, md, cfg);
+  if (rc != APK_OK) return rc;
+  const double huge = std::numeric_limits<double>::max();
+  const PackView &v = md->view;
+  const double fac = v.ndim == 1 ? 0.5 : (v.ndim == 2 ? 0.25 : 1.0 / 6.0);
+  // a fixed isotropic coefficient: min over cells of Dxc_d^2 / (coeff + TINY), the same for every cell of a block
+  auto iso_fixed = [&](double coeff) {
+    double m = huge;
+    for (const apk_block_desc &b : md->h_blocks)
+      for (int d = 0; d < v.ndim; ++d) m = std::fmin(m, b.dx[d] * b.dx[d] / (coeff + 1.0e-20));
+    return cfl_diff * fac * m;
+  };
+  double dt = huge;
+  if (cfg->conduction == APK_COND_ISOTROPIC) {
+    dt = std::fmin(dt, iso_fixed(cfg->thermal_diff_coeff));
+  } else if (cfg->conduction == APK_COND_ANISOTROPIC) {
+    hipStream_t s = as_stream(stream);
+    unsigned long long bits;
+    std::memcpy(&bits, &huge, sizeof(bits));
+    auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
+    h[0] = bits;
+    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_u64, h, sizeof(bits), hipMemcpyHostToDevice, s));
+    rc = launch_cond_dt(v, cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, ctx->d_u64, s);
+    if (rc != APK_OK) return set_err(ctx, rc, "conduction dt kernel launch failed", hipGetLastError());
+    APK_HIP_TRY(ctx, hipMemcpyAsync(h + 1, ctx->d_u64, sizeof(bits), hipMemcpyDeviceToHost, s));
+    APK_HIP_TRY(ctx, hipStreamSynchronize(s));
+    double m;
+    std::memcpy(&m, h + 1, sizeof(m));
+    dt = std::fmin(dt, cfl_diff * fac * m);
+  }
+  if (cfg->viscosity != APK_VISC_NONE) dt = std::fmin(dt, iso_fixed(cfg->mom_diff_coeff));
+  if (cfg->resistivity != APK_RES_NONE) dt = std::fmin(dt, iso_fixed(cfg->ohm_diff_coeff));
+  *dt_out = dt;
+  return APK_OK;
+}
+
 int apk_first_order_flux_correct(apk_ctx *ctx, const apk_pack *u0, const apk_pack *u1, int fluid,
                                  const apk_eos *eos, double c_h, double gam0, double gam1,
                                  double beta_dt, long long *num_corrected, apk_stream_t stream) {

@@ -121,6 +121,74 @@ void hydro_initialize(apk_sim *s) {
   pkg.eos.eceil = Tceil;
   pkg.nscalars = pin.GetOrAddInteger("hydro", "nscalars", 0);
   if (pkg.nscalars < 0) throw std::runtime_error("hydro/nscalars must be >= 0");
+  diffusion_initialize(s);
+}
+
+// <diffusion> (src/hydro/hydro.cpp:538-702): the fixed-coefficient processes with the unsplit integrator.  What this
+// path does not implement is refused instead of being ignored: a deck that asks for diffusion must not run inviscid.
+void diffusion_initialize(apk_sim *s) {
+  ParameterInput &pin = s->pin;
+  HydroPackage &pkg = s->pkg;
+  apk_diff_cfg &c = pkg.diff;
+  c = apk_diff_cfg{};
+  const std::string conduction = pin.GetOrAddString("diffusion", "conduction", "none");
+  if (conduction == "isotropic") c.conduction = APK_COND_ISOTROPIC;
+  else if (conduction == "anisotropic") c.conduction = APK_COND_ANISOTROPIC;
+  else if (conduction != "none") throw std::runtime_error("Unknown conduction method. Options are: none, isotropic, anisotropic");
+  if (c.conduction != APK_COND_NONE) {
+    const std::string coeff = pin.GetOrAddString("diffusion", "conduction_coeff", "none");
+    const double sat_phi = pin.GetOrAddReal("diffusion", "conduction_sat_phi", 0.3);
+    if (coeff == "spitzer") {
+      throw std::runtime_error("Spitzer thermal conduction requires units and gas composition (not part of this path); "
+                               "use diffusion/conduction_coeff = fixed.");
+    } else if (coeff == "fixed") {
+      c.conduction_coeff = APK_CONDC_FIXED;
+      c.thermal_diff_coeff = pin.GetReal("diffusion", "thermal_diff_coeff_code");
+      c.conduction_sat_prefac = 5.0 * sat_phi;  // eq (8) of Cowie & McKee 1977 (hydro.cpp:595-604)
+    } else {
+      throw std::runtime_error("Thermal conduction is enabled but no coefficient is set. Please set "
+                               "diffusion/conduction_coeff to either 'spitzer' or 'fixed'");
+    }
+    if (c.conduction_sat_prefac == 0.0) throw std::runtime_error("Saturated thermal conduction prefactor uninitialized.");
+  }
+  const std::string viscosity = pin.GetOrAddString("diffusion", "viscosity", "none");
+  if (viscosity == "isotropic") c.viscosity = APK_VISC_ISOTROPIC;
+  else if (viscosity != "none") throw std::runtime_error("Unknown viscosity method. Options are: none, isotropic");
+  if (c.viscosity != APK_VISC_NONE) {
+    if (pin.GetOrAddString("diffusion", "viscosity_coeff", "none") != "fixed")
+      throw std::runtime_error("Viscosity is enabled but no coefficient is set. Please set diffusion/viscosity_coeff to "
+                               "'fixed' and diffusion/mom_diff_coeff_code to the desired value.");
+    c.viscosity_coeff = APK_VISCC_FIXED;
+    c.mom_diff_coeff = pin.GetReal("diffusion", "mom_diff_coeff_code");
+  }
+  const std::string resistivity = pin.GetOrAddString("diffusion", "resistivity", "none");
+  if (resistivity == "ohmic") c.resistivity = APK_RES_OHMIC;
+  else if (resistivity != "none") throw std::runtime_error("Unknown resistivity method. Options are: none, ohmic");
+  if (c.resistivity != APK_RES_NONE) {
+    const std::string coeff = pin.GetOrAddString("diffusion", "resistivity_coeff", "none");
+    if (coeff == "spitzer") throw std::runtime_error("Spitzer resistivity is not implemented (in the reference neither).");
+    if (coeff != "fixed")
+      throw std::runtime_error("Resistivity is enabled but no coefficient is set. Please set diffusion/resistivity_coeff "
+                               "to 'fixed' and diffusion/ohm_diff_coeff_code to the desired value.");
+    c.resistivity_coeff = APK_RESC_FIXED;
+    c.ohm_diff_coeff = pin.GetReal("diffusion", "ohm_diff_coeff_code");
+  }
+  const std::string integrator = pin.GetOrAddString("diffusion", "integrator", "none");
+  if (integrator == "unsplit") pkg.diffint = APK_DIFFINT_UNSPLIT;
+  else if (integrator == "rkl2")
+    throw std::runtime_error("diffusion/integrator = rkl2 (super-time-stepping) is not supported; use unsplit.");
+  else if (integrator == "none") pkg.diffint = APK_DIFFINT_NONE;
+  else throw std::runtime_error("AthenaPK unknown integration method for diffusion processes. Options are: none, unsplit, rkl2");
+  // as in Athena++ a cfl safety factor is applied to the theoretical limit, by default the hyperbolic cfl
+  if (pkg.diffint != APK_DIFFINT_NONE) pkg.cfl_diff = pin.GetOrAddReal("diffusion", "cfl", pkg.cfl);
+  if (!pkg.diffusion_active()) return;
+  if (pkg.fluid == APK_FLUID_EULER && (c.resistivity != APK_RES_NONE || c.conduction == APK_COND_ANISOTROPIC))
+    throw std::runtime_error("Ohmic resistivity and anisotropic conduction need hydro/fluid = glmmhd.");
+  if (pkg.riemann == APK_RS_LLF)
+    throw std::runtime_error("Diffusion with hydro/riemann = llf is not supported: the reference's (dc, llf) flux "
+                             "function (CalculateFluxesTight) adds no diffusive fluxes.");
+  if (pin.GetOrAddString("parthenon/mesh", "refinement", "none") != "none")
+    throw std::runtime_error("Diffusion on refined meshes is not supported: parthenon/mesh/refinement must be none.");
 }
 
 void mesh_initialize(apk_sim *s) {
@@ -268,8 +336,9 @@ int ensure_flux_arrays(apk_sim *s) {
 bool stage_can_fuse(const apk_sim *s) {
   // (refined meshes included: the coarse-fine flux correction is applied after the fused stage from
   // boundary-plane fluxes, see amr_flux_fix)
+  // (diffusion: the stages run through the flux arrays, whose face fluxes the diffusive ones are added to)
   return s->fused && !s->pkg.first_order_flux_correct && s->pkg.riemann != APK_RS_NONE &&
-         s->pkg.riemann != APK_RS_LLF;
+         s->pkg.riemann != APK_RS_LLF && !s->pkg.diffusion_active();
 }
 
 // the plans of one field buffer (`field`: the first block's array; blocks follow at nper doubles)
@@ -347,12 +416,17 @@ int estimate_timestep_read(apk_sim *s, DtEstimate *e) {
   }
   if (!have_flags) SIM_TRY(s, apk_poll_device_flags(s->ctx, &flags, s->stream));
   e->dt_hyp_local = dt;
+  // the diffusive limit (hydro.cpp:935-963; unsplit: min_dt = min(dt_hyp, dt_diff))
+  if (s->pkg.diffusion_active()) {
+    if (s->prim_stale) SIM_TRY(s, sync_ghosts(s));  // (the estimate reads stored primitives)
+    SIM_TRY(s, apk_estimate_diffusion_timestep(s->ctx, s->mu0(), &s->pkg.diff, s->pkg.cfl_diff, &e->dt_diff_local, s->stream));
+  }
   e->flags |= flags;  // (flags latched before an earlier read of the same cycle stay raised)
   return APK_OK;
 }
 
 int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
-  double dt = e.dt_hyp_local;
+  double dt = std::min(e.dt_hyp_local, e.dt_diff_local);
   if (s->pkg.max_dt > 0.0 && s->pkg.max_dt < dt) dt = s->pkg.max_dt;
   // one reduction for both minima: the time step, and the hyperbolic estimate that the next cycle's
   // c_h needs (hydro.cpp:102-143 reduces it in PreStepMeshUserWorkInLoop; same value, one message less).
@@ -510,7 +584,7 @@ bool direct_neighbors(const apk_sim *s) {
   // admissibility test in the finishing sweep; a stage that fails it is redone through the flux arrays, which read ghost
   // zones: do_stage fills them first (materialize_local_ghosts).  One-rank periodic boxes, no forcing.
   const bool optimistic = s->fused && pkg.first_order_flux_correct && !s->fmft && pkg.riemann != APK_RS_NONE && pkg.riemann != APK_RS_LLF &&
-                          table_covers_all_faces(s);
+                          !pkg.diffusion_active() && table_covers_all_faces(s);
   if (!stage_can_fuse(s) && !optimistic) return false;
   // (floors and ceilings: ConsToPrim is not fused into the ghost fills then, and the separate pass over the ghost zones
   // would convert the zones nobody filled -- unless no zone is left to fill at all.  What the stages read across a face
@@ -1278,7 +1352,8 @@ int do_stage(apk_sim *s, int stage) {
     // regenerated from the conserved state they belong to -- which an in-place trial would have overwritten.)
     const bool trial_out_of_place = g0 != 0.0 || (direct && stage > 1);
     if (s->fused && pkg.first_order_flux_correct && (g0 == 0.0 || (pkg.nscalars == 0 && !s->amr)) &&
-        !pkg.glmmhd_source_extended && s->mesh.ndim >= 2 && pkg.riemann != APK_RS_NONE && pkg.riemann != APK_RS_LLF) {
+        !pkg.glmmhd_source_extended && s->mesh.ndim >= 2 && pkg.riemann != APK_RS_NONE && pkg.riemann != APK_RS_LLF &&
+        !pkg.diffusion_active()) {
       if (trial_out_of_place) SIM_TRY(s, ensure_trial_cons(s));
       // FirstOrderFluxCorrect tests the UNfloored trial update (hydro.cpp:1283-1306; floors only act
       // in the ConsToPrim that follows the stage)
@@ -1336,6 +1411,9 @@ int do_stage(apk_sim *s, int stage) {
     SIM_TRY(s, ensure_flux_arrays(s));
     // (faces of interior cells only: nothing downstream reads the reference's extra transverse rows)
     SIM_TRY(s, apk_calculate_fluxes_tight(s->ctx, s->mu0(), cfg, &pkg.eos, pkg.c_h, s->stream));
+    // the diffusive fluxes are added at the end of CalculateFluxes (hydro.cpp:1202-1205): FOFC's LLF fluxes, where it
+    // corrects a cell, replace whole face fluxes after that
+    if (pkg.diffusion_active()) SIM_TRY(s, apk_calc_diff_fluxes(s->ctx, s->mu0(), &pkg.diff, s->stream));
     if (pkg.first_order_flux_correct) {
       long long nfix = 0;
       SIM_TRY(s, apk_first_order_flux_correct(s->ctx, s->mu0(), s->mu1(), pkg.fluid, &pkg.eos, pkg.c_h, g0, g1,
@@ -1497,10 +1575,11 @@ int create_common(const char *deck, const char *const *overrides, int noverrides
     else if (s->problem_id == "lw_implode" && s->pkg.fluid == APK_FLUID_GLMMHD)
       throw std::runtime_error("Only hydro runs are supported for LW implosion problem generator.");
     else if (s->problem_id == "turbulence") turbulence_setup(s);
+    else if (s->problem_id == "diffusion") diffusion_check(s);
     else if (s->problem_id != "sod" && s->problem_id != "orszag_tang" && s->problem_id != "synthetic" &&
              s->problem_id != "blast" && s->problem_id != "lw_implode" && s->problem_id != "cpaw" &&
              s->problem_id != "advection" && s->problem_id != "field_loop" && s->problem_id != "kh" &&
-             s->problem_id != "linear_wave" && s->problem_id != "linear_wave_mhd")
+             s->problem_id != "linear_wave" && s->problem_id != "linear_wave_mhd" && s->problem_id != "diffusion")
       throw std::runtime_error("unknown job/problem_id: " + s->problem_id);
     // src/bvals/boundary_conditions_apk.hpp:47-50 (raised when the wall is first applied, i.e. after
     // the problem generator's own checks): the wall only mirrors the normal momentum
@@ -1827,6 +1906,14 @@ double apk_sim_c_h(const apk_sim *s) { return s->pkg.c_h; }
 int apk_sim_ncycle(const apk_sim *s) { return s->ncycle; }
 long long apk_sim_fofc_count(const apk_sim *s) { return s->fofc_total; }
 
+int apk_sim_diffusion_options(const apk_sim *s, apk_diff_cfg *cfg, int *integrator, double *cfl_diff) {
+  if (!s || !cfg || !integrator || !cfl_diff) return APK_ERR_INVALID;
+  *cfg = s->pkg.diff;
+  *integrator = s->pkg.diffint;
+  *cfl_diff = s->pkg.cfl_diff;
+  return APK_OK;
+}
+
 int apk_sim_get_info(const apk_sim *s, apk_sim_info *o) {
   if (!s || !o) return APK_ERR_INVALID;
   std::memset(o, 0, sizeof(*o));
@@ -2094,7 +2181,29 @@ int apk_sim_history_labels(const apk_sim *s, char *buf, size_t len) {
   if (mhd) l += " ME relDivB";
   if (s->fmft) l += mhd ? " Ms Ma plasma_beta" : " Ms";
   if (s->problem_id == "field_loop") l += " UserRelDivB";
+  if (s->problem_id == "linear_wave_mhd" && s->lwm.dump_max_v2) l += " MaxAbsV2";
   std::snprintf(buf, len, "%s", l.c_str());
+  return APK_OK;
+}
+
+// HstMaxV2 (src/pgen/linear_wave_mhd.cpp:713-737): max |v2| over the interior cells of every block, max over ranks.  For
+// history outputs only: each block's v2 comes to the host (one plane of the primitives per block).
+static int max_abs_v2(apk_sim *s, double *out) {
+  if (s->prim_stale) SIM_TRY(s, sync_ghosts(s));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  const Mesh &m = s->mesh;
+  std::vector<double> v((size_t)m.sn);
+  double mx = 0.0;
+  for (int lb = 0; lb < (int)m.local_gids.size(); ++lb) {
+    SIM_HIP(s, hipMemcpy(v.data(), s->blk(s->d_prim(), lb) + 2 * m.sn /* IV2 */, sizeof(double) * m.sn, hipMemcpyDeviceToHost));
+    for (int k = m.ks; k <= m.ke; ++k)
+      for (int j = m.js; j <= m.je; ++j)
+        for (int i = m.is; i <= m.ie; ++i) mx = std::fmax(mx, std::fabs(v[k * m.sk + j * m.sj + i]));
+  }
+  double neg = -mx;  // (max over ranks as the min of the negatives)
+  if (s->have_comm && s->nranks > 1 && s->comm.allreduce_min(s->comm.user, &neg, 1) != 0)
+    return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
+  *out = -neg;
   return APK_OK;
 }
 
@@ -2108,10 +2217,14 @@ int apk_sim_write_history(apk_sim *s, const char *path) {
   const bool floop = s->problem_id == "field_loop";
   double urdb = 0.0;
   if (floop && (rc = apk_sim_user_reldivb(s, &urdb)) != APK_OK) return rc;
+  const bool maxv2 = s->problem_id == "linear_wave_mhd" && s->lwm.dump_max_v2;
+  double mv2 = 0.0;
+  if (maxv2 && (rc = max_abs_v2(s, &mv2)) != APK_OK) return rc;
   if (s->rank != 0) return APK_OK;
   std::vector<double> row(h, h + (mhd ? 8 : 6));
   if (s->fmft) row.insert(row.end(), t3, t3 + (mhd ? 3 : 1));
   if (floop) row.push_back(urdb);
+  if (maxv2) row.push_back(mv2);
   FILE *f = std::fopen(path, "r");
   const bool fresh = (f == nullptr);
   if (f) std::fclose(f);

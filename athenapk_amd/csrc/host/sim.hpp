@@ -38,6 +38,16 @@ struct HydroPackage {
   double dt_hyp = std::numeric_limits<double>::max();
   // flux function keys (FluxFunKey_t) of the first and the other stages (hydro.cpp:449-467)
   apk_flux_cfg flux_first_stage{}, flux_other_stage{};
+  // <diffusion> (hydro.cpp:538-702): the processes, diffint and cfl_diff
+  apk_diff_cfg diff{};
+  int diffint = APK_DIFFINT_NONE;
+  double cfl_diff = 0.0;
+  // configured processes act only with the unsplit integrator (with integrator = none they do nothing, as in the
+  // reference)
+  bool diffusion_active() const {
+    return diffint == APK_DIFFINT_UNSPLIT &&
+           (diff.conduction != APK_COND_NONE || diff.viscosity != APK_VISC_NONE || diff.resistivity != APK_RES_NONE);
+  }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -50,6 +60,7 @@ struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
 
 struct LinearWaveMhdState {  // what src/pgen/linear_wave_mhd.cpp keeps besides the hydro wave's geometry (LinearWaveState)
   double bx0 = 1.0, by0 = 0.0, bz0 = 0.0, dby = 0.0, dbz = 0.0, ev[7] = {0}, rem[7][7] = {{0}};
+  bool dump_max_v2 = false;  // problem/linear_wave/dump_max_v2: the MaxAbsV2 history column (linear_wave_mhd.cpp:739-744)
 };
 
 struct CpawState {  // globals of src/pgen/cpaw.cpp

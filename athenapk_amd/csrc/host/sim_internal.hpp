@@ -46,6 +46,7 @@ inline hipStream_t hs(const apk_sim *s) { return reinterpret_cast<hipStream_t>(s
 
 int parse_bc(const std::string &v);
 void hydro_initialize(apk_sim *s);
+void diffusion_initialize(apk_sim *s);  // <diffusion>, called by hydro_initialize
 void mesh_initialize(apk_sim *s);
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);
 void dev_free(apk_sim *s, double *p);
@@ -58,6 +59,7 @@ int build_prim_plans(apk_sim *s);
 void set_global_dt(apk_sim *s, double dt_est);
 struct DtEstimate {  // what one rank measured: see estimate_timestep_read / _commit
   double dt_hyp_local = kHuge;
+  double dt_diff_local = kHuge;  // the diffusive limit (unsplit diffusion)
   unsigned flags = 0;
 };
 int estimate_timestep_read(apk_sim *s, DtEstimate *e);
@@ -97,6 +99,7 @@ double xc(const apk_sim *s, const double x0[3], int d, int idx);
 void block_origin(const apk_sim *s, int lb, double x0[3]);
 void lw_eigensystem(double gm1, double v1, double v2, double v3, double h, double ev[5], double rem[5][5]);
 void lw_setup(apk_sim *s);
+void diffusion_check(apk_sim *s);  // problem_id = diffusion: the iprob / fluid combination
 void lw_state(const LinearWaveState &lw, double x1, double x2, double x3, double u[5]);
 void lwm_setup(apk_sim *s);
 void lwm_state(const apk_sim *s, double x1, double x2, double x3, double u[8]);  // analytic d, M, E, B (no psi)

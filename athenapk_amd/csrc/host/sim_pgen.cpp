@@ -42,6 +42,16 @@ void lw_eigensystem(double gm1, double v1, double v2, double v3, double h, doubl
 }
 
 // src/pgen/linear_wave.cpp:72-176 (InitUserMeshData)
+// the diffusion problem generator's checks at creation (src/pgen/diffusion.cpp:33-36): every iprob that sets a magnetic
+// field needs GLM-MHD.  The reference lists 0, 1, 2, 10, 20 and 40; the rings in the other planes (21, 22) set field
+// components too, which a hydro run does not have, so they are refused with the same message.
+void diffusion_check(apk_sim *s) {
+  const int ip = s->pin.GetInteger("problem/diffusion", "iprob");
+  const bool sets_field = ip == 0 || ip == 1 || ip == 2 || ip == 10 || ip == 20 || ip == 21 || ip == 22 || ip == 40;
+  if (sets_field && s->pkg.fluid != APK_FLUID_GLMMHD)
+    throw std::runtime_error("Selected iprob for diffusion pgen requires MHD enabled.");
+}
+
 void lw_setup(apk_sim *s) {
   ParameterInput &pin = s->pin;
   LinearWaveState &lw = s->lw;
@@ -193,6 +203,7 @@ void lwm_eigensystem(double gm1, double d, double v1, double v2, double v3, doub
 // InitUserMeshData (linear_wave_mhd.cpp:68-172): the hydro wave's geometry and background (the same
 // expressions: :91-143 == linear_wave.cpp:86-140) plus B = (1, sqrt 2, 1/2) in the wave frame
 void lwm_setup(apk_sim *s) {
+  s->lwm.dump_max_v2 = s->pin.GetOrAddBoolean("problem/linear_wave", "dump_max_v2", false);
   if (s->pkg.fluid != APK_FLUID_GLMMHD) throw std::runtime_error("linear_wave_mhd requires hydro/fluid = glmmhd");
   lw_setup(s);
   LinearWaveState &lw = s->lw;
@@ -458,11 +469,79 @@ void pgen_block(apk_sim *s, int lb, std::vector<double> &u) {
       }
     lwi[4] = y0;
   }
+  // diffusion (src/pgen/diffusion.cpp:19-55): step functions, Gaussians and rings of the diffusion tests
+  int df_iprob = -1;
+  double df_bx = 0.0, df_by = 0.0, df_t0 = 0.5, df_coeff = 0.0, df_amp = 1e-6;
+  if (s->problem_id == "diffusion") {
+    df_bx = pin.GetOrAddReal("problem/diffusion", "Bx", 0.0);
+    df_by = pin.GetOrAddReal("problem/diffusion", "By", 0.0);
+    df_iprob = pin.GetInteger("problem/diffusion", "iprob");
+    const int ip = df_iprob;  // (a hydro run with an iprob that sets a field was refused at creation: diffusion_check)
+    if (ip == 10 || ip == 30 || ip == 40) {
+      df_t0 = pin.GetOrAddReal("problem/diffusion", "t0", df_t0);
+      df_amp = pin.GetOrAddReal("problem/diffusion", "amp", df_amp);
+    }
+    if (ip == 10) df_coeff = pin.GetReal("diffusion", "thermal_diff_coeff_code");
+    else if (ip == 30) df_coeff = pin.GetReal("diffusion", "mom_diff_coeff_code");
+    else if (ip == 40) df_coeff = pin.GetReal("diffusion", "ohm_diff_coeff_code");
+  }
   for (int k = m.ks; k <= m.ke; ++k)
     for (int j = m.js; j <= m.je; ++j)
       for (int i = m.is; i <= m.ie; ++i) {
         const double x1 = xc(s, x0, 0, i), x2 = xc(s, x0, 1, j), x3 = xc(s, x0, 2, k);
-        if (s->problem_id == "advection") {  // src/pgen/advection.cpp:91-110
+        if (s->problem_id == "diffusion") {  // src/pgen/diffusion.cpp:57-158
+          double w[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0}, eint = -1.0;
+          const int ip = df_iprob;
+          // ring of a hotter arc in the plane (a, b): field circles the origin, |B| = 1
+          auto ring = [&](double x, double y, double &ba, double &bb) {
+            const double r = std::sqrt(x * x + y * y), phi = std::atan2(y, x);
+            ba = y / r;
+            bb = -x / r;
+            return std::abs(r - 0.6) < 0.1 && std::abs(phi) < M_PI / 12.0 ? 12.0 : 10.0;
+          };
+          if (ip == 0) {
+            b[0] = df_bx, b[1] = df_by;
+            eint = x1 <= 0.0 ? 10.0 : 12.0;
+          } else if (ip == 1) {
+            b[1] = df_bx, b[2] = df_by;
+            eint = x2 <= 0.0 ? 10.0 : 12.0;
+          } else if (ip == 2) {
+            b[2] = df_bx, b[0] = df_by;
+            eint = x3 <= 0.0 ? 10.0 : 12.0;
+          } else if (ip == 10) {
+            b[0] = df_bx, b[1] = df_by;
+            // a field perpendicular to x1 conducts nothing: the profile is kept as for a unit coefficient
+            const double eff = df_bx == 0.0 ? df_coeff : df_coeff * df_bx * df_bx;
+            eint = 1 + df_amp / std::sqrt(4. * M_PI * eff * df_t0) * std::exp(-(std::pow(x1, 2.)) / (4. * eff * df_t0));
+          } else if (ip == 20) {
+            eint = ring(x1, x2, b[0], b[1]);
+          } else if (ip == 21) {
+            eint = ring(x2, x3, b[1], b[2]);
+          } else if (ip == 22) {
+            eint = ring(x3, x1, b[2], b[0]);
+          } else if (ip == 30) {
+            w[1] = 1.0 * df_amp / std::pow(std::sqrt(4. * M_PI * df_coeff * df_t0), 1.0) *
+                   std::exp(-(std::pow(x1, 2.)) / (4. * df_coeff * df_t0));
+            eint = 1.0 / (pkg.eos.gamma * (pkg.eos.gamma - 1.0));  // c_s = 1
+          } else if (ip == 40) {
+            b[1] = df_amp / std::pow(std::sqrt(4. * M_PI * df_coeff * df_t0), 1.0) *
+                   std::exp(-(std::pow(x1, 2.)) / (4. * df_coeff * df_t0));
+            eint = 1.0 / (pkg.eos.gamma * (pkg.eos.gamma - 1.0));
+          }
+          if (!(eint > 0.0)) throw std::runtime_error("diffusion: unknown problem/diffusion/iprob");
+          at(0, k, j, i) = 1.0;
+          at(1, k, j, i) = w[0];
+          at(2, k, j, i) = w[1];
+          at(3, k, j, i) = w[2];
+          double e = 1.0 * eint + 0.5 * ((w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) / 1.0);
+          if (mhd) {
+            at(5, k, j, i) = b[0];
+            at(6, k, j, i) = b[1];
+            at(7, k, j, i) = b[2];
+            e += 0.5 * (b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+          }
+          at(4, k, j, i) = e;
+        } else if (s->problem_id == "advection") {  // src/pgen/advection.cpp:91-110
           double rho = adv[6];
           const double rsq = x1 * x1 + x2 * x2 + x3 * x3;
           if (rsq < adv[4] * adv[4]) rho += adv[6] * adv[3] * std::exp(-rsq / 2 / adv[8]);

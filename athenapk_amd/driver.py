@@ -619,6 +619,14 @@ class Simulation(_FmftHost, _MeshView):
         return self.dt
 
 
+def _diffusion_options(lib, h):
+    cfg, integ, cfl = L.DiffCfg(), C.c_int(0), C.c_double(0.0)
+    rc = lib.apk_sim_diffusion_options(h, C.byref(cfg), C.byref(integ), C.byref(cfl))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_diffusion_options")
+    return cfg, integ.value, cfl.value
+
+
 class HostPlan(_FmftHost, _MeshView):
     """Host-only view of a rank's mesh partition and ghost-exchange plan (no GPU needed)."""
 
@@ -656,3 +664,7 @@ class HostPlan(_FmftHost, _MeshView):
     @property
     def tlim(self):
         return self.lib.apk_sim_tlim(self.h)
+
+    def diffusion_options(self):
+        """(lib.DiffCfg, diffusion/integrator as apk_diffint, diffusion/cfl) as the deck was parsed"""
+        return _diffusion_options(self.lib, self.h)

@@ -365,6 +365,22 @@ def EstimateTimestep(md, fluid, eos, cfl):
     return dt.value
 
 
+def CalcDiffFluxes(md, cfg):
+    """CalcDiffFluxes(hydro_pkg, md) -- src/hydro/diffusion/diffusion.cpp:18; cfg: lib.DiffCfg (lib.make_diff_cfg).
+    Adds the diffusive fluxes into md.flux[d]."""
+    ctx = md.ctx
+    _check(ctx.lib.apk_calc_diff_fluxes(ctx.h, md.h, C.byref(cfg), _stream()), ctx.lib, ctx.h)
+
+
+def EstimateDiffusionTimestep(md, cfg, cfl_diff):
+    """the diffusive limit of Hydro::EstimateTimestep -- src/hydro/hydro.cpp:935-949"""
+    ctx = md.ctx
+    dt = C.c_double(0.0)
+    _check(ctx.lib.apk_estimate_diffusion_timestep(ctx.h, md.h, C.byref(cfg), float(cfl_diff), C.byref(dt), _stream()),
+           ctx.lib, ctx.h)
+    return dt.value
+
+
 def FirstOrderFluxCorrect(u0, u1, fluid, eos, c_h, gam0, gam1, beta_dt):
     """Hydro::FirstOrderFluxCorrect<fluid>(u0,u1,gam0,gam1,beta_dt) -- hydro.cpp:1223"""
     ctx = u0.ctx

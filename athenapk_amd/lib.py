@@ -16,6 +16,11 @@ FLUID = {"euler": 1, "glmmhd": 2}
 RECON = {"dc": 1, "plm": 2, "ppm": 3, "wenoz": 4, "weno3": 5, "limo3": 6}
 RIEMANN = {"none": 1, "hlle": 2, "llf": 3, "hllc": 4, "hlld": 5}
 INTEGRATOR = {"rk1": 1, "rk2": 2, "vl2": 3, "rk3": 4}
+# diffusion enums of include/apk_amd.h (src/main.hpp:40-46)
+CONDUCTION = {"none": 0, "isotropic": 1, "anisotropic": 2}
+VISCOSITY = {"none": 0, "isotropic": 1}
+RESISTIVITY = {"none": 0, "ohmic": 1}
+DIFF_COEFF = {"none": 0, "fixed": 1, "spitzer": 2}
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
                 "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3")
@@ -40,6 +45,20 @@ def make_eos(gamma, pfloor=-1.0, dfloor=-1.0, efloor=-1.0, vceil=float("inf"),
 
 class FluxCfg(C.Structure):
     _fields_ = [("fluid", C.c_int), ("recon", C.c_int), ("riemann", C.c_int)]
+
+
+class DiffCfg(C.Structure):
+    _fields_ = [("conduction", C.c_int), ("conduction_coeff", C.c_int), ("thermal_diff_coeff", C.c_double),
+                ("conduction_sat_prefac", C.c_double), ("viscosity", C.c_int), ("viscosity_coeff", C.c_int),
+                ("mom_diff_coeff", C.c_double), ("resistivity", C.c_int), ("resistivity_coeff", C.c_int),
+                ("ohm_diff_coeff", C.c_double)]
+
+
+def make_diff_cfg(conduction="none", kappa=0.0, sat_phi=0.3, viscosity="none", nu=0.0, resistivity="none", eta=0.0):
+    """apk_diff_cfg with fixed coefficients; conduction_sat_prefac = 5 phi (hydro.cpp:595-604)"""
+    fixed = DIFF_COEFF["fixed"]
+    return DiffCfg(CONDUCTION[conduction], fixed, kappa, 5.0 * sat_phi, VISCOSITY[viscosity], fixed, nu,
+                   RESISTIVITY[resistivity], fixed, eta)
 
 
 class BlockDesc(C.Structure):
@@ -184,6 +203,8 @@ def _signatures():
         "apk_stage_dt_read": (i, [vp, d, c_dp, vp]),
         "apk_stage_dt_flags_read": (i, [vp, d, c_dp, C.POINTER(C.c_uint), vp]),
         "apk_estimate_timestep": (i, [vp, vp, i, E, d, c_dp, vp]),
+        "apk_calc_diff_fluxes": (i, [vp, vp, C.POINTER(DiffCfg), vp]),
+        "apk_estimate_diffusion_timestep": (i, [vp, vp, C.POINTER(DiffCfg), d, c_dp, vp]),
         "apk_first_order_flux_correct": (i, [vp, vp, vp, i, E, d, d, d, d, C.POINTER(ll), vp]),
         "apk_count_unphysical": (i, [vp, vp, i, C.POINTER(ll), vp]),
         "apk_history": (i, [vp, vp, i, c_dp, vp]),
@@ -251,6 +272,7 @@ def _signatures():
         "apk_sim_loop_seconds": (d, [vp]),
         "apk_sim_loop_cycles": (i, [vp]),
         "apk_sim_get_info": (i, [vp, C.POINTER(SimInfo)]),
+        "apk_sim_diffusion_options": (i, [vp, C.POINTER(DiffCfg), C.POINTER(C.c_int), c_dp]),
         "apk_sim_block_location": (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int * 3)]),
         "apk_sim_block_ptr": (vp, [vp, i, i]),
         "apk_sim_gather": (i, [vp, i, c_dp]),

@@ -405,6 +405,48 @@ int apk_stage_dt_flags_read(apk_ctx *ctx, double cfl, double *dt_out, unsigned *
 int apk_estimate_timestep(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos,
                           double cfl, double *dt_out, apk_stream_t stream);
 
+/* ---- unsplit diffusion (diffusion/integrator = unsplit) -----------------------------------------------------------
+ * Option enums: numeric values = position in the reference's enum classes, src/main.hpp:40-46. */
+enum apk_conduction { APK_COND_NONE = 0, APK_COND_ISOTROPIC = 1, APK_COND_ANISOTROPIC = 2 };
+enum apk_conduction_coeff { APK_CONDC_NONE = 0, APK_CONDC_FIXED = 1, APK_CONDC_SPITZER = 2 };
+enum apk_viscosity { APK_VISC_NONE = 0, APK_VISC_ISOTROPIC = 1 };
+enum apk_viscosity_coeff { APK_VISCC_NONE = 0, APK_VISCC_FIXED = 1 };
+enum apk_resistivity { APK_RES_NONE = 0, APK_RES_OHMIC = 1 };
+enum apk_resistivity_coeff { APK_RESC_NONE = 0, APK_RESC_FIXED = 1, APK_RESC_SPITZER = 2 };
+enum apk_diffint { APK_DIFFINT_NONE = 0, APK_DIFFINT_UNSPLIT = 1, APK_DIFFINT_RKL2 = 2 };
+
+/* The "Hydro" params of the diffusive processes (hydro.cpp:538-702): the ThermalDiffusivity, MomentumDiffusivity and
+ * OhmicDiffusivity objects with a fixed coefficient, and conduction_sat_prefac (5 * diffusion/conduction_sat_phi for a
+ * fixed coefficient, hydro.cpp:595-604).  A process set to *_NONE is off.  Only the *_FIXED coefficients are supported
+ * (Spitzer needs units: APK_ERR_UNSUPPORTED). */
+typedef struct apk_diff_cfg {
+  int conduction, conduction_coeff; /* apk_conduction, apk_conduction_coeff */
+  double thermal_diff_coeff;        /* diffusion/thermal_diff_coeff_code */
+  double conduction_sat_prefac;     /* conduction_sat_prefac */
+  int viscosity, viscosity_coeff;   /* apk_viscosity, apk_viscosity_coeff */
+  double mom_diff_coeff;            /* diffusion/mom_diff_coeff_code */
+  int resistivity, resistivity_coeff; /* apk_resistivity, apk_resistivity_coeff */
+  double ohm_diff_coeff;            /* diffusion/ohm_diff_coeff_code */
+} apk_diff_cfg;
+
+/* Replaces CalcDiffFluxes(StateDescriptor*, MeshData<Real>*) src/hydro/diffusion/diffusion.cpp:18-53 (called at the end
+ * of CalculateFluxes when diffusion/integrator = unsplit, hydro.cpp:1202-1205): ThermalFluxIsoFixed
+ * (conduction.cpp:189-259), ThermalFluxGeneral for anisotropic conduction (conduction.cpp:265-471),
+ * MomentumDiffFluxIsoFixed (viscosity.cpp:94-289), OhmicDiffFluxIsoFixed (resistivity.cpp:91-230).  ADDS the diffusive
+ * fluxes of every enabled process into flux[d] on the faces of interior cells: one launch per active direction.  Reads
+ * prim, including one layer of ghost cells (edges too).  Resistivity and anisotropic conduction need GLM-MHD.  The
+ * transverse derivatives of the Ohmic current divide by 2 dx where the reference takes Xf(k+1) - Xf(k-1). */
+int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, apk_stream_t stream);
+
+/* Replaces the diffusive part of Hydro::EstimateTimestep (hydro.cpp:935-949): the minimum of
+ * EstimateConductionTimestep (conduction.cpp:44-184), EstimateViscosityTimestep (viscosity.cpp:34-89) and
+ * EstimateResistivityTimestep (resistivity.cpp:33-86) over the enabled processes, each cfl_diff * fac * min(...) with
+ * fac = 1/2, 1/4, 1/6 in 1, 2, 3 dimensions.  Fixed isotropic processes depend on the cell widths only and are
+ * evaluated on the host; anisotropic conduction is a device min-reduction over the interior (synchronises `stream`).
+ * No process enabled: *dt_out = DBL_MAX. */
+int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, double cfl_diff,
+                                    double *dt_out, apk_stream_t stream);
+
 /* Replaces Hydro::FirstOrderFluxCorrect<fluid>(u0,u1,gam0,gam1,beta_dt)
  * src/hydro/hydro.cpp:1223-1342.  Iterates <= 4 attempts, one host sync per attempt like
  * the reference's parallel_reduce.  *num_corrected (optional) = cells corrected. */

@@ -180,6 +180,9 @@ typedef struct apk_sim_info {
   int64_t zones_total;
 } apk_sim_info;
 int apk_sim_get_info(const apk_sim *sim, apk_sim_info *info);
+/* the <diffusion> options as parsed (hydro.cpp:538-702): the processes and coefficients, diffusion/integrator
+ * (apk_diffint) and diffusion/cfl (0 when the integrator is none) */
+int apk_sim_diffusion_options(const apk_sim *sim, apk_diff_cfg *cfg, int *integrator, double *cfl_diff);
 /* global block id and logical (bx,by,bz) of local block lb */
 int apk_sim_block_location(const apk_sim *sim, int lb, int *gid, int loc[3]);
 /* Mesh refinement (parthenon/mesh/refinement = static | adaptive, numlevel, derefine_count,
