@@ -68,7 +68,8 @@ class MeshData:
         pitch that is a multiple of 16 doubles from a base that puts the first interior cell of a row on a 128-byte
         boundary; an int = that pitch.  (APK_TEST_ROW_PITCH in the environment sets the default: the parity tests run
         unchanged on either layout.)  self.cons / prim / flux[d] are VIEWS [nblocks][nvar][Nk][Nj][Ni] of the padded
-        storage; the padding holds NaNs."""
+        storage; the padding holds NaNs.  dx: one (dx1, dx2, dx3) for every block, or a sequence of nblocks of them (a
+        pack that mixes refinement levels); self.dx is then that tuple of triples."""
         self.ctx = ctx
         self.nx, self.ng, self.nhydro, self.nscalars = tuple(nx), ng, nhydro, nscalars
         self.nvar = nhydro + nscalars
@@ -78,7 +79,12 @@ class MeshData:
         self.shape = (self.nvar, nk, nj, ni)
         self.ndim = 3 if nx[2] > 1 else (2 if nx[1] > 1 else 1)
         self.nblocks = nblocks
-        self.dx = tuple(dx)
+        per_block = np.ndim(dx) == 2
+        if per_block:
+            assert np.shape(dx) == (nblocks, 3), "dx: one triple, or one per block"
+            self.dx = tuple(tuple(float(v) for v in t) for t in dx)
+        else:
+            self.dx = tuple(dx)
         dev = torch.device("cuda")
         if row_pitch is None:
             row_pitch = os.environ.get("APK_TEST_ROW_PITCH") or None
@@ -125,7 +131,7 @@ class MeshData:
             blocks[b].prim = self.prim.data_ptr() + b * per
             for d in range(3):
                 blocks[b].flux[d] = (self.flux[d].data_ptr() + b * per) if self.flux[d] is not None else None
-            blocks[b].dx[:] = list(dx)
+            blocks[b].dx[:] = list(self.dx[b] if per_block else self.dx)
         desc = L.PackDesc()
         desc.nblocks, desc.nhydro, desc.nscalars, desc.ng = nblocks, nhydro, nscalars, ng
         desc.nx[:] = list(nx)

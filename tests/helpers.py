@@ -98,6 +98,11 @@ def geom(fluid, nx, ng, nscalars=0, dx=(1.0, 1.0, 1.0)):
 
 
 # ---- oracle block-level wrappers (loop over pack blocks) ----------------------------------------
+# g: one geometry for the whole pack, or a sequence of one per block (a pack that mixes refinement levels)
+def _g(g, b):
+    return g[b] if isinstance(g, (list, tuple)) else g
+
+
 def orc_fluxes(fluid, recon, riemann, g, prim, gamma, c_h, tight=False):
     lib = O.load()
     eos = O.make_eos(gamma)
@@ -107,10 +112,10 @@ def orc_fluxes(fluid, recon, riemann, g, prim, gamma, c_h, tight=False):
         p = np.ascontiguousarray(prim[b])
         f = [np.zeros_like(p) for _ in range(3)]
         if tight or riemann == "llf":
-            lib.orc_calculate_fluxes_tight(C.byref(g), O.FLUID[fluid], C.byref(eos), c_h, O.dp(p),
+            lib.orc_calculate_fluxes_tight(C.byref(_g(g, b)), O.FLUID[fluid], C.byref(eos), c_h, O.dp(p),
                                            O.dp(f[0]), O.dp(f[1]), O.dp(f[2]))
         else:
-            lib.orc_calculate_fluxes(C.byref(g), O.FLUID[fluid], O.RECON[recon], O.RIEMANN[riemann],
+            lib.orc_calculate_fluxes(C.byref(_g(g, b)), O.FLUID[fluid], O.RECON[recon], O.RIEMANN[riemann],
                                      C.byref(eos), c_h, O.dp(p), O.dp(f[0]), O.dp(f[1]), O.dp(f[2]))
         for d in range(3):
             fl[d][b] = f[d]
@@ -122,7 +127,7 @@ def orc_update(g, u0, u1, fl, gam0, gam1, beta_dt):
     out = np.array(u0, copy=True)
     for b in range(u0.shape[0]):
         o = np.ascontiguousarray(out[b])
-        lib.orc_update_flux_div(C.byref(g), O.dp(o), O.dp(np.ascontiguousarray(u1[b])),
+        lib.orc_update_flux_div(C.byref(_g(g, b)), O.dp(o), O.dp(np.ascontiguousarray(u1[b])),
                                 O.dp(np.ascontiguousarray(fl[0][b])), O.dp(np.ascontiguousarray(fl[1][b])),
                                 O.dp(np.ascontiguousarray(fl[2][b])), gam0, gam1, beta_dt)
         out[b] = o
@@ -134,7 +139,7 @@ def orc_dedner(g, cons, prim, extended, alpha, c_h, mindx, beta_dt):
     out = np.array(cons, copy=True)
     for b in range(cons.shape[0]):
         o = np.ascontiguousarray(out[b])
-        lib.orc_dedner_source(C.byref(g), int(extended), alpha, c_h, mindx, beta_dt, O.dp(o),
+        lib.orc_dedner_source(C.byref(_g(g, b)), int(extended), alpha, c_h, mindx, beta_dt, O.dp(o),
                               O.dp(np.ascontiguousarray(prim[b])))
         out[b] = o
     return out
@@ -148,7 +153,7 @@ def orc_c2p(fluid, g, cons, eos):
     for b in range(cons.shape[0]):
         c = np.ascontiguousarray(cons_out[b])
         p = np.zeros_like(c)
-        bad += lib.orc_cons_to_prim(C.byref(g), O.FLUID[fluid], C.byref(eos), O.dp(c), O.dp(p))
+        bad += lib.orc_cons_to_prim(C.byref(_g(g, b)), O.FLUID[fluid], C.byref(eos), O.dp(c), O.dp(p))
         cons_out[b] = c
         prim[b] = p
     return cons_out, prim, bad
@@ -157,7 +162,7 @@ def orc_c2p(fluid, g, cons, eos):
 def orc_min_dt(fluid, g, prim, gamma):
     lib = O.load()
     eos = O.make_eos(gamma)
-    return min(lib.orc_estimate_dt_hyp(C.byref(g), O.FLUID[fluid], C.byref(eos),
+    return min(lib.orc_estimate_dt_hyp(C.byref(_g(g, b)), O.FLUID[fluid], C.byref(eos),
                                        O.dp(np.ascontiguousarray(prim[b]))) for b in range(prim.shape[0]))
 
 
@@ -166,7 +171,7 @@ def orc_history(fluid, g, cons):
     tot = np.zeros(8)
     for b in range(cons.shape[0]):
         o = np.zeros(8)
-        lib.orc_history(C.byref(g), O.FLUID[fluid], O.dp(np.ascontiguousarray(cons[b])), O.dp(o))
+        lib.orc_history(C.byref(_g(g, b)), O.FLUID[fluid], O.dp(np.ascontiguousarray(cons[b])), O.dp(o))
         tot += o
     return tot
 
@@ -188,7 +193,7 @@ def orc_turb_history(fluid, g, prim, gamma):
     lib = O.load()
     out = np.zeros(3)
     for b in range(prim.shape[0]):
-        lib.orc_turb_history(C.byref(g), O.FLUID[fluid], gamma, O.dp(np.ascontiguousarray(prim[b])), O.dp(out))
+        lib.orc_turb_history(C.byref(_g(g, b)), O.FLUID[fluid], gamma, O.dp(np.ascontiguousarray(prim[b])), O.dp(out))
     return out
 
 
@@ -200,7 +205,7 @@ def orc_fofc(fluid, g, u0c, u0p, u1c, fl, gamma, c_h, gam0, gam1, beta_dt):
     for b in range(u0c.shape[0]):
         f = [np.ascontiguousarray(out[d][b]) for d in range(3)]
         total += lib.orc_first_order_flux_correct(
-            C.byref(g), O.FLUID[fluid], C.byref(eos), c_h, O.dp(np.ascontiguousarray(u0c[b])),
+            C.byref(_g(g, b)), O.FLUID[fluid], C.byref(eos), c_h, O.dp(np.ascontiguousarray(u0c[b])),
             O.dp(np.ascontiguousarray(u0p[b])), O.dp(np.ascontiguousarray(u1c[b])), O.dp(f[0]), O.dp(f[1]),
             O.dp(f[2]), gam0, gam1, beta_dt)
         for d in range(3):
