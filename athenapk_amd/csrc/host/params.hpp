@@ -7,6 +7,7 @@
 
 #include <cstdlib>
 #include <map>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -28,6 +29,7 @@ class ParameterInput {
         const auto close = line.find('>');
         if (close == std::string::npos) throw std::runtime_error("deck: unterminated block header: " + line);
         block = Trim(line.substr(1, close - 1));
+        blocks_.insert(block);
         continue;
       }
       const auto eq = line.find('=');
@@ -53,6 +55,15 @@ class ParameterInput {
       if (block.compare(0, prefix.size(), prefix) == 0 && (out.empty() || out.back() != block)) out.push_back(block);
     }
     return out;
+  }
+  // a "<block>" header in the deck (keys or not), or an override into it
+  bool DoesBlockExist(const std::string &block) const {
+    if (blocks_.count(block)) return true;
+    for (const auto &kv : values_)
+      if (kv.first.size() > block.size() && kv.first.compare(0, block.size(), block) == 0 && kv.first[block.size()] == '/' &&
+          kv.first.find('/', block.size() + 1) == std::string::npos)
+        return true;
+    return false;
   }
   bool DoesParameterExist(const std::string &block, const std::string &key) const {
     return values_.count(block + "/" + key) > 0;
@@ -120,6 +131,7 @@ class ParameterInput {
     throw std::runtime_error("deck: <" + b + "> " + k + " is not a boolean: " + v);
   }
   std::map<std::string, std::string> values_;
+  std::set<std::string> blocks_;  // block headers seen in the deck
 };
 
 }  // namespace apk

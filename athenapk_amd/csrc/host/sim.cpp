@@ -111,17 +111,31 @@ void hydro_initialize(apk_sim *s) {
   pkg.eos.gamma = pin.GetReal("hydro", "gamma");
   pkg.eos.dfloor = pin.GetOrAddReal("hydro", "dfloor", -1.0);
   pkg.eos.pfloor = pin.GetOrAddReal("hydro", "pfloor", -1.0);
+  units_initialize(s);
+  // temperature floor and ceiling as specific internal energies (hydro.cpp:509-536)
   const double Tfloor = pin.GetOrAddReal("hydro", "Tfloor", -1.0);
-  if (Tfloor > 0.0) throw std::runtime_error("Temperature floor requires units and gas composition (not part of this path).");
-  pkg.eos.efloor = Tfloor;
+  double efloor = Tfloor;
+  if (efloor > 0.0) {
+    if (!pkg.units.has_composition)
+      throw std::runtime_error("Temperature floor requires units and gas composition. Either set a 'units' block and the "
+                               "'hydro/He_mass_fraction' in input file or use a pressure floor (defined code units) instead.");
+    efloor = Tfloor / pkg.units.mbar_over_kb / (pkg.eos.gamma - 1.0);
+  }
+  pkg.eos.efloor = efloor;
   pkg.eos.vceil = pin.GetOrAddReal("hydro", "vceil", std::numeric_limits<double>::infinity());
   const double Tceil = pin.GetOrAddReal("hydro", "Tceil", std::numeric_limits<double>::infinity());
-  if (Tceil < std::numeric_limits<double>::infinity())
-    throw std::runtime_error("Temperature ceiling requires units and gas composition (not part of this path).");
-  pkg.eos.eceil = Tceil;
+  double eceil = Tceil;
+  if (eceil < std::numeric_limits<double>::infinity()) {
+    if (!pkg.units.has_composition)
+      throw std::runtime_error("Temperature ceiling requires units and gas composition. Either set a 'units' block and the "
+                               "'hydro/He_mass_fraction' in input file or use a pressure floor (defined code units) instead.");
+    eceil = Tceil / pkg.units.mbar_over_kb / (pkg.eos.gamma - 1.0);
+  }
+  pkg.eos.eceil = eceil;
   pkg.nscalars = pin.GetOrAddInteger("hydro", "nscalars", 0);
   if (pkg.nscalars < 0) throw std::runtime_error("hydro/nscalars must be >= 0");
   diffusion_initialize(s);
+  cooling_initialize(s);
 }
 
 // <diffusion> (src/hydro/hydro.cpp:538-702): the fixed-coefficient processes with the unsplit integrator.  What this
@@ -336,9 +350,10 @@ int ensure_flux_arrays(apk_sim *s) {
 bool stage_can_fuse(const apk_sim *s) {
   // (refined meshes included: the coarse-fine flux correction is applied after the fused stage from
   // boundary-plane fluxes, see amr_flux_fix)
-  // (diffusion: the stages run through the flux arrays, whose face fluxes the diffusive ones are added to)
+  // (diffusion: the stages run through the flux arrays, whose face fluxes the diffusive ones are added to; cooling: the
+  // source acts between the update and ConsToPrim, which the fused stages do in one sweep)
   return s->fused && !s->pkg.first_order_flux_correct && s->pkg.riemann != APK_RS_NONE &&
-         s->pkg.riemann != APK_RS_LLF && !s->pkg.diffusion_active();
+         s->pkg.riemann != APK_RS_LLF && !s->pkg.flux_path_sources();
 }
 
 // the plans of one field buffer (`field`: the first block's array; blocks follow at nper doubles)
@@ -421,20 +436,40 @@ int estimate_timestep_read(apk_sim *s, DtEstimate *e) {
     if (s->prim_stale) SIM_TRY(s, sync_ghosts(s));  // (the estimate reads stored primitives)
     SIM_TRY(s, apk_estimate_diffusion_timestep(s->ctx, s->mu0(), &s->pkg.diff, s->pkg.cfl_diff, &e->dt_diff_local, s->stream));
   }
+  // the cooling limit (hydro.cpp:926-933): joins min_dt, not dt_hyp (so c_h is untouched)
+  if (s->pkg.cooling) {
+    if (s->prim_stale) SIM_TRY(s, sync_ghosts(s));  // (the estimate reads stored primitives)
+    SIM_TRY(s, apk_estimate_cooling_timestep(s->ctx, s->mu0(), s->cool_tab, &e->dt_cool_local, s->stream));
+    unsigned more = 0;  // (what the source term latched since the stage's read)
+    SIM_TRY(s, apk_poll_device_flags(s->ctx, &more, s->stream));
+    flags |= more;
+  }
   e->flags |= flags;  // (flags latched before an earlier read of the same cycle stay raised)
   return APK_OK;
 }
 
 int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
-  double dt = std::min(e.dt_hyp_local, e.dt_diff_local);
+  double dt = std::min(std::min(e.dt_hyp_local, e.dt_diff_local), e.dt_cool_local);
   if (s->pkg.max_dt > 0.0 && s->pkg.max_dt < dt) dt = s->pkg.max_dt;
   // one reduction for both minima: the time step, and the hyperbolic estimate that the next cycle's
   // c_h needs (hydro.cpp:102-143 reduces it in PreStepMeshUserWorkInLoop; same value, one message less).
   // The negative-state flags travel with them (two more slots, MIN of -1 / 0): a rank that latched a flag must not
   // leave the collective to its peers -- every rank takes part, then every rank fails.
-  double mins[4] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0, (e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0};
+  // With cooling two more: the flags of its device failures, and the table's fingerprint (as x and -x) -- every rank
+  // must integrate with the same table.
+  const bool cool = s->pkg.cooling;
+  const double h = s->pkg.cool_table_hash;
+  double mins[7] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0, (e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0,
+                    (e.flags & (APK_FLAG_COOL_MAX_ITER | APK_FLAG_COOL_TABLE)) ? -1.0 : 0.0, h, -h};
   if (s->have_comm && s->nranks > 1) {
-    if (s->comm.allreduce_min(s->comm.user, mins, 4) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
+    if (s->comm.allreduce_min(s->comm.user, mins, cool ? 7 : 4) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
+  }
+  if (cool && mins[5] != -mins[6]) return fail(s, APK_ERR_INVALID, "cooling: the ranks read different cooling tables");
+  if (cool && mins[4] < 0.0) {
+    if (e.flags & APK_FLAG_COOL_MAX_ITER)
+      return fail(s, APK_ERR_INVALID, "FATAL ERROR in [TabularCooling::SubcyclingFixedIntSrcTerm]: Sub cycles exceed max_iter (This should be impossible)");
+    if (e.flags & APK_FLAG_COOL_TABLE) return fail(s, APK_ERR_INVALID, "FATAL ERROR in [CoolingTable::DeDt]: Failed to find log_temp");
+    return fail(s, APK_ERR_INVALID, "cooling failed on another rank");
   }
   if (mins[2] < 0.0)
     return fail(s, APK_ERR_INVALID, "Got negative density. Consider enabling first-order flux correction or setting a reasonble density floor.");
@@ -584,7 +619,7 @@ bool direct_neighbors(const apk_sim *s) {
   // admissibility test in the finishing sweep; a stage that fails it is redone through the flux arrays, which read ghost
   // zones: do_stage fills them first (materialize_local_ghosts).  One-rank periodic boxes, no forcing.
   const bool optimistic = s->fused && pkg.first_order_flux_correct && !s->fmft && pkg.riemann != APK_RS_NONE && pkg.riemann != APK_RS_LLF &&
-                          !pkg.diffusion_active() && table_covers_all_faces(s);
+                          !pkg.flux_path_sources() && table_covers_all_faces(s);
   if (!stage_can_fuse(s) && !optimistic) return false;
   // (floors and ceilings: ConsToPrim is not fused into the ghost fills then, and the separate pass over the ghost zones
   // would convert the zones nobody filled -- unless no zone is left to fill at all.  What the stages read across a face
@@ -1353,7 +1388,7 @@ int do_stage(apk_sim *s, int stage) {
     const bool trial_out_of_place = g0 != 0.0 || (direct && stage > 1);
     if (s->fused && pkg.first_order_flux_correct && (g0 == 0.0 || (pkg.nscalars == 0 && !s->amr)) &&
         !pkg.glmmhd_source_extended && s->mesh.ndim >= 2 && pkg.riemann != APK_RS_NONE && pkg.riemann != APK_RS_LLF &&
-        !pkg.diffusion_active()) {
+        !pkg.flux_path_sources()) {
       if (trial_out_of_place) SIM_TRY(s, ensure_trial_cons(s));
       // FirstOrderFluxCorrect tests the UNfloored trial update (hydro.cpp:1283-1306; floors only act
       // in the ConsToPrim that follows the stage)
@@ -1426,6 +1461,9 @@ int do_stage(apk_sim *s, int stage) {
       SIM_TRY(s, apk_dedner_source(s->ctx, s->mu0(), pkg.glmmhd_source_extended ? 1 : 0, pkg.glmmhd_alpha,
                                    pkg.c_h, pkg.mindx, beta_dt, s->stream));
     }
+    // the other unsplit source (AddUnsplitSources, hydro.cpp:227-246): after the update and the Dedner source, before
+    // the exchange and ConsToPrim of the stage (and before the turbulence kick of the last stage)
+    if (pkg.cooling) SIM_TRY(s, apk_tabular_cooling_src(s->ctx, s->mu0(), s->cool_tab, pkg.fluid, beta_dt, s->stream));
     }
   }
   if (s->fmft && stage == s->nstages) {
@@ -1646,6 +1684,18 @@ int apk_sim_create(const char *deck, const char *const *overrides, int noverride
     s->err = "apk_create failed: no usable gfx950 device (there is no CPU fallback)";
     return bail(rc);
   }
+  if (s->pkg.cooling) {
+    const CoolingTableHost &ct = s->pkg.cool_table;
+    // (the rows as read: the table handle converts and checks them itself)
+    std::vector<double> ll(ct.n);
+    const double shift = std::log10(s->pkg.cool.lambda_units);
+    for (int i = 0; i < ct.n; ++i) ll[i] = ct.log_lambdas[i] + shift;
+    rc = apk_cooling_table_create(s->ctx, ct.log_temps.data(), ll.data(), ct.n, &s->pkg.cool, &s->cool_tab);
+    if (rc != APK_OK) {
+      s->err = apk_last_error(s->ctx);
+      return bail(rc);
+    }
+  }
   if (s->amr) {
     if ((rc = amr_allocate(s, s->mesh.local_gids.size(), s->d_cons2, &s->d_prim2[0], s->d_flux, &s->d_coarse)) != APK_OK) return bail(rc);
     if ((rc = amr_rebuild(s)) != APK_OK) return bail(rc);
@@ -1733,6 +1783,7 @@ void apk_sim_destroy(apk_sim *s) {
     for (auto *f : s->d_flux) dev_free(s, f);
     for (auto *b : s->send_buf) dev_free(s, b);
     for (auto *b : s->recv_buf) dev_free(s, b);
+    apk_cooling_table_destroy(s->cool_tab);
     apk_destroy(s->ctx);
   }
   delete s;
@@ -1911,6 +1962,40 @@ int apk_sim_diffusion_options(const apk_sim *s, apk_diff_cfg *cfg, int *integrat
   *cfg = s->pkg.diff;
   *integrator = s->pkg.diffint;
   *cfl_diff = s->pkg.cfl_diff;
+  return APK_OK;
+}
+
+int apk_sim_units(const apk_sim *s, apk_units_info *o) {
+  if (!s || !o) return APK_ERR_INVALID;
+  std::memset(o, 0, sizeof(*o));
+  const UnitsState &u = s->pkg.units;
+  o->has_units = u.has_units;
+  o->has_composition = u.has_composition;
+  o->code_length_cgs = u.code_length_cgs, o->code_mass_cgs = u.code_mass_cgs, o->code_time_cgs = u.code_time_cgs;
+  o->mh = u.mh(), o->k_boltzmann = u.k_boltzmann(), o->atomic_mass_unit = u.atomic_mass_unit();
+  o->erg = u.erg(), o->cm = u.cm(), o->s = u.s();
+  o->He_mass_fraction = u.He_mass_fraction, o->mu = u.mu, o->mu_e = u.mu_e, o->mbar = u.mbar;
+  o->mbar_over_kb = u.mbar_over_kb;
+  o->efloor = s->pkg.eos.efloor, o->eceil = s->pkg.eos.eceil;
+  return APK_OK;
+}
+
+int apk_sim_cooling_options(const apk_sim *s, int *enabled, apk_cooling_params *p, int *n_temp) {
+  if (!s || !enabled || !p || !n_temp) return APK_ERR_INVALID;
+  *enabled = s->pkg.cooling ? 1 : 0;
+  *p = s->pkg.cool;
+  *n_temp = s->pkg.cool_table.n;
+  return APK_OK;
+}
+
+int apk_sim_cooling_table(const apk_sim *s, int which, double *out, int n, int *size) {
+  if (!s || !size || (n > 0 && !out)) return APK_ERR_INVALID;
+  const CoolingTableHost &t = s->pkg.cool_table;
+  const std::vector<double> *v = which == 0 ? &t.log_temps : which == 1 ? &t.log_lambdas : which == 2 ? &t.alpha_k
+                                 : which == 3 ? &t.Y_k : nullptr;
+  if (!v) return APK_ERR_INVALID;
+  *size = (int)v->size();
+  for (int i = 0; i < n && i < (int)v->size(); ++i) out[i] = (*v)[i];
   return APK_OK;
 }
 

@@ -11,12 +11,23 @@
 
 #include "../../../include/apk_amd.h"
 #include "../../../include/apk_host.h"
+#include "../cooling_table.hpp"
 #include "amr.hpp"
 #include "mesh.hpp"
 #include "params.hpp"
 #include "turbulence.hpp"
 
 namespace apk {
+
+// Units (src/units.hpp) and the gas composition (hydro.cpp:482-503)
+struct UnitsState {
+  bool has_units = false, has_composition = false;
+  double code_length_cgs = 1, code_mass_cgs = 1, code_time_cgs = 1;
+  double He_mass_fraction = 0, mu = 0, mu_e = 0, mbar = 0, mbar_over_kb = 0;
+  double code_energy_cgs() const;
+  // constants and scales in code units
+  double k_boltzmann() const, mh() const, atomic_mass_unit() const, erg() const, cm() const, s() const;
+};
 
 // "Hydro" StateDescriptor params (names as in hydro.cpp)
 struct HydroPackage {
@@ -48,6 +59,14 @@ struct HydroPackage {
     return diffint == APK_DIFFINT_UNSPLIT &&
            (diff.conduction != APK_COND_NONE || diff.viscosity != APK_VISC_NONE || diff.resistivity != APK_RES_NONE);
   }
+  UnitsState units;
+  // <cooling> enable_cooling = tabular (hydro.cpp:723-738): the parameters, the table as parsed and its fingerprint
+  bool cooling = false;
+  apk_cooling_params cool{};
+  CoolingTableHost cool_table;
+  double cool_table_hash = 0.0;
+  // the unsplit sources that run through the flux-array stage path (no fused stage forms with them)
+  bool flux_path_sources() const { return diffusion_active() || cooling; }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -90,6 +109,7 @@ struct apk_sim {
   apk::host::RcclTransport *rccl = nullptr;  // native transport (apk_sim_comm_rccl); comm.* point into it
   apk::ParameterInput pin;
   apk::Mesh mesh;
+  apk_cooling_table *cool_tab = nullptr;  // the device table of <cooling> (created with ctx)
   apk::HydroPackage pkg;
   std::string problem_id;
   apk::LinearWaveState lw;

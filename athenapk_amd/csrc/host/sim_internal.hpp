@@ -47,6 +47,8 @@ inline hipStream_t hs(const apk_sim *s) { return reinterpret_cast<hipStream_t>(s
 int parse_bc(const std::string &v);
 void hydro_initialize(apk_sim *s);
 void diffusion_initialize(apk_sim *s);  // <diffusion>, called by hydro_initialize
+void units_initialize(apk_sim *s);      // <units> and hydro/He_mass_fraction (host/cooling.cpp)
+void cooling_initialize(apk_sim *s);    // <cooling> (host/cooling.cpp), called by hydro_initialize
 void mesh_initialize(apk_sim *s);
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);
 void dev_free(apk_sim *s, double *p);
@@ -60,6 +62,7 @@ void set_global_dt(apk_sim *s, double dt_est);
 struct DtEstimate {  // what one rank measured: see estimate_timestep_read / _commit
   double dt_hyp_local = kHuge;
   double dt_diff_local = kHuge;  // the diffusive limit (unsplit diffusion)
+  double dt_cool_local = kHuge;  // the cooling limit (tabular cooling)
   unsigned flags = 0;
 };
 int estimate_timestep_read(apk_sim *s, DtEstimate *e);

@@ -627,6 +627,32 @@ def _diffusion_options(lib, h):
     return cfg, integ.value, cfl.value
 
 
+def _units(lib, h):
+    u = L.UnitsInfo()
+    rc = lib.apk_sim_units(h, C.byref(u))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_units")
+    return u
+
+
+def _cooling_options(lib, h):
+    en, p, n = C.c_int(0), L.CoolingParams(), C.c_int(0)
+    rc = lib.apk_sim_cooling_options(h, C.byref(en), C.byref(p), C.byref(n))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_cooling_options")
+    return bool(en.value), p, n.value
+
+
+def _cooling_table(lib, h, which):
+    size = C.c_int(0)
+    rc = lib.apk_sim_cooling_table(h, which, None, 0, C.byref(size))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_cooling_table")
+    out = (C.c_double * max(size.value, 1))()
+    lib.apk_sim_cooling_table(h, which, out, size.value, C.byref(size))
+    return np.array(out[:size.value], dtype=np.float64)
+
+
 class HostPlan(_FmftHost, _MeshView):
     """Host-only view of a rank's mesh partition and ghost-exchange plan (no GPU needed)."""
 
@@ -668,3 +694,15 @@ class HostPlan(_FmftHost, _MeshView):
     def diffusion_options(self):
         """(lib.DiffCfg, diffusion/integrator as apk_diffint, diffusion/cfl) as the deck was parsed"""
         return _diffusion_options(self.lib, self.h)
+
+    def units(self):
+        """lib.UnitsInfo: <units>, the gas composition and the EOS's efloor / eceil as parsed"""
+        return _units(self.lib, self.h)
+
+    def cooling_options(self):
+        """(enabled, lib.CoolingParams, rows of the table) of <cooling> as parsed"""
+        return _cooling_options(self.lib, self.h)
+
+    def cooling_table(self, which):
+        """one array of the parsed table: "log_temps", "log_lambdas" (code units), "alpha_k", "Y_k" (Townsend)"""
+        return _cooling_table(self.lib, self.h, ("log_temps", "log_lambdas", "alpha_k", "Y_k").index(which))

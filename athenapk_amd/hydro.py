@@ -387,6 +387,75 @@ def EstimateDiffusionTimestep(md, cfg, cfl_diff):
     return dt.value
 
 
+class TabularCooling:
+    """cooling::TabularCooling (src/hydro/srcterms/tabular_cooling.hpp:175-250) on an apk_cooling_table.
+    log_temps / log_lambdas: the table's rows as read from the file (log10 K, log10 of lambda in lambda_units_cgs);
+    params: lib.CoolingParams (lib.make_cooling_params).  A table the reference refuses raises ApkError with its
+    message."""
+
+    def __init__(self, ctx, log_temps, log_lambdas, params):
+        self.ctx, self.params = ctx, params
+        lt = np.ascontiguousarray(log_temps, dtype=np.float64)
+        ll = np.ascontiguousarray(log_lambdas, dtype=np.float64)
+        n = min(len(lt), len(ll))
+        dp = C.POINTER(C.c_double)
+        h = C.c_void_p()
+        _check(ctx.lib.apk_cooling_table_create(ctx.h, lt.ctypes.data_as(dp), ll.ctypes.data_as(dp), n,
+                                                C.byref(params), C.byref(h)), ctx.lib, ctx.h)
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.apk_cooling_table_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _failed(self):
+        f = self.ctx.poll_flags()
+        if f & L.APK_FLAG_COOL_MAX_ITER:
+            raise L.ApkError(L.APK_ERR_INVALID, "TabularCooling: sub cycles exceed max_iter")
+        if f & L.APK_FLAG_COOL_TABLE:
+            raise L.ApkError(L.APK_ERR_INVALID, "CoolingTable::DeDt: failed to find log_temp")
+
+    def SrcTerm(self, md, fluid, dt):
+        """TabularCooling::SrcTerm(md, dt) -- tabular_cooling.cpp:278-288: cools the interior cells of md.cons
+        (IEN only).  Synchronises to read the failure flags."""
+        ctx = self.ctx
+        _check(ctx.lib.apk_tabular_cooling_src(ctx.h, md.h, self.h, L.FLUID[fluid], float(dt), _stream()), ctx.lib,
+               ctx.h)
+        self._failed()
+
+    def EstimateTimeStep(self, md):
+        """TabularCooling::EstimateTimeStep(md) -- tabular_cooling.cpp:606-665 (reads md.prim)"""
+        ctx = self.ctx
+        dt = C.c_double(0.0)
+        _check(ctx.lib.apk_estimate_cooling_timestep(ctx.h, md.h, self.h, C.byref(dt), _stream()), ctx.lib, ctx.h)
+        self._failed()
+        return dt.value
+
+    def DeDt(self, e, rho):
+        """CoolingTableObj::DeDt(e, rho, is_valid) -- tabular_cooling.hpp:129-173, pointwise: (dedt, valid) numpy
+        arrays"""
+        ctx = self.ctx
+        dev = torch.device("cuda")
+        te = torch.from_numpy(np.ascontiguousarray(e, dtype=np.float64).ravel()).to(dev)
+        tr = torch.from_numpy(np.ascontiguousarray(rho, dtype=np.float64).ravel()).to(dev)
+        assert te.numel() == tr.numel()
+        out = torch.empty_like(te)
+        valid = torch.empty(te.numel(), dtype=torch.int32, device=dev)
+        _check(ctx.lib.apk_cooling_dedt(ctx.h, self.h, te.data_ptr(), tr.data_ptr(), out.data_ptr(), valid.data_ptr(),
+                                        te.numel(), _stream()), ctx.lib, ctx.h)
+        # (a lookup that fails the reference's REQUIRE is reported in last_flags, not raised: the table's own nodes
+        # sit on that boundary)
+        self.last_flags = ctx.poll_flags()
+        return out.cpu().numpy(), valid.cpu().numpy().astype(bool)
+
+
 def FirstOrderFluxCorrect(u0, u1, fluid, eos, c_h, gam0, gam1, beta_dt):
     """Hydro::FirstOrderFluxCorrect<fluid>(u0,u1,gam0,gam1,beta_dt) -- hydro.cpp:1223"""
     ctx = u0.ctx

@@ -21,6 +21,10 @@ CONDUCTION = {"none": 0, "isotropic": 1, "anisotropic": 2}
 VISCOSITY = {"none": 0, "isotropic": 1}
 RESISTIVITY = {"none": 0, "ohmic": 1}
 DIFF_COEFF = {"none": 0, "fixed": 1, "spitzer": 2}
+# cooling integrators (apk_cool_integrator; cooling::CoolIntegrator) and the flag bits of its device failures
+COOL_INTEGRATOR = {"rk12": 1, "rk45": 2, "townsend": 3}
+APK_FLAG_COOL_MAX_ITER = 4
+APK_FLAG_COOL_TABLE = 8
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
                 "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3")
@@ -59,6 +63,28 @@ def make_diff_cfg(conduction="none", kappa=0.0, sat_phi=0.3, viscosity="none", n
     fixed = DIFF_COEFF["fixed"]
     return DiffCfg(CONDUCTION[conduction], fixed, kappa, 5.0 * sat_phi, VISCOSITY[viscosity], fixed, nu,
                    RESISTIVITY[resistivity], fixed, eta)
+
+
+class CoolingParams(C.Structure):
+    _fields_ = [("integrator", C.c_int), ("max_iter", C.c_int), ("cfl", C.c_double), ("d_log_temp_tol", C.c_double),
+                ("d_e_tol", C.c_double), ("T_floor", C.c_double), ("lambda_units", C.c_double), ("gamma", C.c_double),
+                ("mbar_over_kb", C.c_double), ("He_mass_fraction", C.c_double), ("mh", C.c_double)]
+
+
+def make_cooling_params(integrator="rk12", max_iter=100, cfl=0.1, d_log_temp_tol=1e-8, d_e_tol=1e-8, T_floor=-1.0,
+                        lambda_units=1.0, gamma=5.0 / 3.0, mbar_over_kb=1.0, He_mass_fraction=0.25, mh=1.0):
+    """apk_cooling_params with the reference's defaults (tabular_cooling.cpp:53-68)"""
+    return CoolingParams(COOL_INTEGRATOR[integrator], int(max_iter), float(cfl), float(d_log_temp_tol), float(d_e_tol),
+                         float(T_floor), float(lambda_units), float(gamma), float(mbar_over_kb), float(He_mass_fraction),
+                         float(mh))
+
+
+class UnitsInfo(C.Structure):
+    _fields_ = [("has_units", C.c_int), ("has_composition", C.c_int), ("code_length_cgs", C.c_double),
+                ("code_mass_cgs", C.c_double), ("code_time_cgs", C.c_double), ("mh", C.c_double),
+                ("k_boltzmann", C.c_double), ("atomic_mass_unit", C.c_double), ("erg", C.c_double), ("cm", C.c_double),
+                ("s", C.c_double), ("He_mass_fraction", C.c_double), ("mu", C.c_double), ("mu_e", C.c_double),
+                ("mbar", C.c_double), ("mbar_over_kb", C.c_double), ("efloor", C.c_double), ("eceil", C.c_double)]
 
 
 class BlockDesc(C.Structure):
@@ -205,6 +231,11 @@ def _signatures():
         "apk_estimate_timestep": (i, [vp, vp, i, E, d, c_dp, vp]),
         "apk_calc_diff_fluxes": (i, [vp, vp, C.POINTER(DiffCfg), vp]),
         "apk_estimate_diffusion_timestep": (i, [vp, vp, C.POINTER(DiffCfg), d, c_dp, vp]),
+        "apk_cooling_table_create": (i, [vp, c_dp, c_dp, i, C.POINTER(CoolingParams), pp]),
+        "apk_cooling_table_destroy": (None, [vp]),
+        "apk_cooling_dedt": (i, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
+        "apk_tabular_cooling_src": (i, [vp, vp, vp, i, d, vp]),
+        "apk_estimate_cooling_timestep": (i, [vp, vp, vp, c_dp, vp]),
         "apk_first_order_flux_correct": (i, [vp, vp, vp, i, E, d, d, d, d, C.POINTER(ll), vp]),
         "apk_count_unphysical": (i, [vp, vp, i, C.POINTER(ll), vp]),
         "apk_history": (i, [vp, vp, i, c_dp, vp]),
@@ -273,6 +304,9 @@ def _signatures():
         "apk_sim_loop_cycles": (i, [vp]),
         "apk_sim_get_info": (i, [vp, C.POINTER(SimInfo)]),
         "apk_sim_diffusion_options": (i, [vp, C.POINTER(DiffCfg), C.POINTER(C.c_int), c_dp]),
+        "apk_sim_units": (i, [vp, C.POINTER(UnitsInfo)]),
+        "apk_sim_cooling_options": (i, [vp, C.POINTER(C.c_int), C.POINTER(CoolingParams), C.POINTER(C.c_int)]),
+        "apk_sim_cooling_table": (i, [vp, i, c_dp, i, C.POINTER(C.c_int)]),
         "apk_sim_block_location": (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int * 3)]),
         "apk_sim_block_ptr": (vp, [vp, i, i]),
         "apk_sim_gather": (i, [vp, i, c_dp]),

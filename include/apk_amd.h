@@ -54,6 +54,9 @@ enum apk_status {
 /* device flag bits latched by kernels (apk_poll_device_flags) */
 #define APK_FLAG_NEG_DENSITY 1u
 #define APK_FLAG_NEG_PRESSURE 2u
+/* tabular cooling: the reference's device failures (PARTHENON_FAIL / REQUIRE), latched instead of trapping */
+#define APK_FLAG_COOL_MAX_ITER 4u /* "Sub cycles exceed max_iter", tabular_cooling.cpp:375-380 */
+#define APK_FLAG_COOL_TABLE 8u    /* "Failed to find log_temp", tabular_cooling.hpp:155-156 */
 
 typedef void *apk_stream_t; /* hipStream_t */
 
@@ -446,6 +449,57 @@ int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c
  * No process enabled: *dt_out = DBL_MAX. */
 int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, double cfl_diff,
                                     double *dt_out, apk_stream_t stream);
+
+/* ---- tabular radiative cooling (<cooling> enable_cooling = tabular) -------------------------------------------------
+ * Integrator enum: numeric values = position in cooling::CoolIntegrator, tabular_cooling.hpp:96. */
+enum apk_cool_integrator { APK_COOL_UNDEFINED = 0, APK_COOL_RK12 = 1, APK_COOL_RK45 = 2, APK_COOL_TOWNSEND = 3 };
+
+/* The parameters TabularCooling::TabularCooling reads (tabular_cooling.cpp:30-276) and the "Hydro" params it takes from
+ * the package (AdiabaticIndex, mbar_over_kb, He_mass_fraction, units.mh()), all in code units. */
+typedef struct apk_cooling_params {
+  int integrator;         /* apk_cool_integrator */
+  int max_iter;           /* cooling/max_iter */
+  double cfl;             /* cooling/cfl (<= 0: no time-step limit) */
+  double d_log_temp_tol;  /* cooling/d_log_temp_tol: allowed relative unevenness of the log T spacing */
+  double d_e_tol;         /* cooling/d_e_tol (0: fixed sub steps dt / max_iter) */
+  double T_floor;         /* hydro/Tfloor in K (negative: none) */
+  double lambda_units;    /* cooling/lambda_units_cgs / (erg cm^3 / s in code units) */
+  double gamma;           /* hydro/gamma */
+  double mbar_over_kb;    /* mu mh / kB */
+  double He_mass_fraction;
+  double mh;              /* hydrogen mass in code units (Units::mh) */
+} apk_cooling_params;
+
+typedef struct apk_cooling_table apk_cooling_table;
+
+/* Replaces the table part of TabularCooling::TabularCooling (tabular_cooling.cpp:103-276): checks the table (>= 2
+ * rows, increasing log T, even spacing within d_log_temp_tol unless townsend with cfl <= 0), converts log_lambdas to code
+ * units (log_lambda - log10(lambda_units)), precomputes the Townsend coefficients alpha_k, Y_k (:230-265; alpha_k == 1 is
+ * refused) and uploads the arrays.  log_temps / log_lambdas: host arrays of n rows as read from the file.  A refusal
+ * returns APK_ERR_INVALID with the reference's message in apk_last_error. */
+int apk_cooling_table_create(apk_ctx *ctx, const double *log_temps, const double *log_lambdas, int n,
+                             const apk_cooling_params *params, apk_cooling_table **out);
+void apk_cooling_table_destroy(apk_cooling_table *table);
+
+/* CoolingTableObj::DeDt (tabular_cooling.hpp:129-173) at n points: device arrays e (specific internal energy), rho ->
+ * dedt; valid[i] = 0 where DeDt cleared is_valid (e < 0 or NaN), else 1.  For testing. */
+int apk_cooling_dedt(apk_ctx *ctx, const apk_cooling_table *table, const double *e, const double *rho, double *dedt,
+                     int *valid, int64_t n, apk_stream_t stream);
+
+/* Replaces TabularCooling::SrcTerm (tabular_cooling.cpp:278-288), called with beta_dt by AddUnsplitSources
+ * (hydro.cpp:227-246): SubcyclingFixedIntSrcTerm<RK12Stepper | RK45Stepper> (:290-487) or TownsendSrcTerm (:489-604) on
+ * the interior cells of every block.  Changes cons(IEN) only.  Deviations: ghost cells are not cooled (the reference
+ * loops over IndexDomain::entire; the stage's ghost exchange refills them before anything reads them) and prim(IPR) is
+ * not written (ConsToPrim recomputes it after the stage).  The reference's device failures latch APK_FLAG_COOL_* into the
+ * flag word (apk_poll_device_flags). */
+int apk_tabular_cooling_src(apk_ctx *ctx, const apk_pack *md, const apk_cooling_table *table, int fluid, double dt,
+                            apk_stream_t stream);
+
+/* Replaces TabularCooling::EstimateTimeStep (tabular_cooling.cpp:606-665), joined to min_dt by Hydro::EstimateTimestep
+ * (hydro.cpp:926-933): cfl * min over interior cells of |e / DeDt(e)| from the stored primitives (+inf where DeDt is 0
+ * or e is below the floor).  cfl <= 0: DBL_MAX; cfl NaN or infinite: +inf (no launch).  Synchronises `stream`. */
+int apk_estimate_cooling_timestep(apk_ctx *ctx, const apk_pack *md, const apk_cooling_table *table, double *dt_out,
+                                  apk_stream_t stream);
 
 /* Replaces Hydro::FirstOrderFluxCorrect<fluid>(u0,u1,gam0,gam1,beta_dt)
  * src/hydro/hydro.cpp:1223-1342.  Iterates <= 4 attempts, one host sync per attempt like

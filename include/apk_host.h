@@ -183,6 +183,22 @@ int apk_sim_get_info(const apk_sim *sim, apk_sim_info *info);
 /* the <diffusion> options as parsed (hydro.cpp:538-702): the processes and coefficients, diffusion/integrator
  * (apk_diffint) and diffusion/cfl (0 when the integrator is none) */
 int apk_sim_diffusion_options(const apk_sim *sim, apk_diff_cfg *cfg, int *integrator, double *cfl_diff);
+/* <units> (src/units.hpp) and the gas composition (hydro.cpp:482-503) as parsed.  has_units: a <units> block exists;
+ * has_composition: so does hydro/He_mass_fraction (mu, mu_e, mbar, mbar_over_kb are 0 otherwise). */
+typedef struct apk_units_info {
+  int has_units, has_composition;
+  double code_length_cgs, code_mass_cgs, code_time_cgs;
+  double mh, k_boltzmann, atomic_mass_unit, erg, cm, s; /* in code units */
+  double He_mass_fraction, mu, mu_e, mbar, mbar_over_kb;
+  double efloor, eceil; /* the EOS fields hydro/Tfloor and hydro/Tceil map to */
+} apk_units_info;
+int apk_sim_units(const apk_sim *sim, apk_units_info *info);
+/* <cooling> as parsed (tabular_cooling.cpp:30-276): *enabled = 1 for enable_cooling = tabular (then *params is filled,
+ * else zeroed), *n_temp = rows of the table */
+int apk_sim_cooling_options(const apk_sim *sim, int *enabled, apk_cooling_params *params, int *n_temp);
+/* one array of the parsed table: which = 0 log_temps, 1 log_lambdas (code units), 2 Townsend alpha_k, 3 Townsend Y_k
+ * (n_temp - 1 entries; townsend only); copies min(n, size) values into out, *size = the array's length */
+int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int *size);
 /* global block id and logical (bx,by,bz) of local block lb */
 int apk_sim_block_location(const apk_sim *sim, int lb, int *gid, int loc[3]);
 /* Mesh refinement (parthenon/mesh/refinement = static | adaptive, numlevel, derefine_count,
