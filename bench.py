@@ -9,15 +9,21 @@ all-reduce).  Weak scaling: every GPU owns a 256^3 brick = 8 meshblocks of 128^3
 between bricks travel as one RCCL send/recv per peer per stage (torch.distributed "nccl").
 
   python bench.py                          # N=1
+  python bench.py --full                   # N=1 with every supplementary figure (below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times its regions,
+writes --dump-outputs and prints the headline:
   value        : the median of three timed regions of --steps cycles each (no event records inside)
+With --full the line also carries what takes runs of its own after the timed regions (the --no-* options and
+--sustained select among them):
   roofline     : algorithmic bytes of one fused stage / live HIP-event time of its kernels (a fourth region of the same
                  cycles with the library's event timing on), priced against HBM; `bound` names what binds the kernels;
                  general_stage.scheme_floor: the issue floor of the scheme's own arithmetic on this device
+  sustained_500_cycles, weak_scaling_base_with_ghost_copies : N = 1 only, the same sim after the timed regions
   rehearsal_8gpu_rank : one rank of the 2 x 2 x 2 run on this GPU (loopback transport), against the N = 1 brick timed beside it
+  other_workloads : BASELINE configs 2 - 5 next to the headline, a few cycles each
   cpu_baseline : the CPU oracle (-O3 -march=native, OpenMP) on a bounded sample of the same
                  workload on this box's host cores -- a reported baseline, not the target.
 """
@@ -651,18 +657,23 @@ def main():
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps cycles each; the median one is reported")
-    ap.add_argument("--sustained", type=int, default=500, help="cycles of the 'sustained' figure of the N = 1 line (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also measure everything beside the headline: the kernels' HIP-event times "
+                         "and the roofline, and at N = 1 the sustained figure, the weak-scaling base with ghost copies, the "
+                         "general stage, the 8-GPU rehearsal, the other workloads and the CPU baseline (the options below "
+                         "leave out single ones)")
+    ap.add_argument("--sustained", type=int, default=500, help="cycles of the 'sustained' figure of the N = 1 --full line (0: skip)")
     ap.add_argument("--workload", default="mhd_ppm_hlld_vl2_256", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of the N = 1 --full run")
     ap.add_argument("--no-copies-base", action="store_true",
-                    help="skip the second N = 1 figure (same steps with the same-rank ghost copies of an N > 1 run)")
+                    help="skip the second N = 1 --full figure (same steps with the same-rank ghost copies of an N > 1 run)")
     ap.add_argument("--unfused", action="store_true", help="use the flux-array path (for A/B)")
     ap.add_argument("--brick", type=int, default=0, help="cells per GPU and direction instead of the workload's 256 (tests)")
     ap.add_argument("--meshblock", type=int, default=0, help="meshblock size instead of the workload's 128 (tests)")
     ap.add_argument("--no-rehearsal", action="store_true",
                     help="skip 'rehearsal_8gpu_rank' (the N = 1 brick with its outer faces exchanged like those between bricks; ~10 s)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the 'other_workloads' figures of the default N = 1 run (BASELINE configs 2, 4's scheme, 5's mesh; ~20 s)")
+                    help="skip the 'other_workloads' figures of the N = 1 --full run (BASELINE configs 2, 4's scheme, 5's mesh; ~20 s)")
     ap.add_argument("--amr-extra", action="store_true",
                     help="append the adaptive-mesh figure (BASELINE config 5 shape) as 'amr_blast_cfg5'; off by default so "
                          "that the kernels of the default command are those of the headline workload only")
@@ -756,9 +767,9 @@ def main():
     info = sim.info
     # THREE timed regions of exactly --steps cycles each, every one bracketed by barrier + synchronize and reduced with
     # MAX over the ranks; `value` / `ms_per_step` are those of the MEDIAN region, all three are listed in
-    # `timed_regions_ms`.  No event records in these loops (round-5 review): the kernels' HIP-event durations behind
-    # `roofline` come from a FOURTH region of the same --steps cycles right after them, with the in-library timing on
-    # (two event records per launch on the stream the kernels run on).
+    # `timed_regions_ms`.  No event records in these loops (round-5 review): with --full the kernels' HIP-event durations
+    # behind `roofline` come from a FOURTH region of the same --steps cycles right after them, with the in-library timing
+    # on (two event records per launch on the stream the kernels run on).
     regions = []
     comm_before = sim.comm_stats() if world > 1 else None
     for _ in range(max(1, args.regions)):
@@ -779,24 +790,25 @@ def main():
     comm_after = sim.comm_stats() if world > 1 else None
     # the state the last timed step left (read after the timing, before any further cycle)
     dumped = dump_outputs(sim, args.dump_outputs, rank, world) if args.dump_outputs else None
-    sim.kernel_timing(True)
-    sim.read_kernel_timing()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        sim.step()
-    torch.cuda.synchronize()
-    barrier()
-    event_region = time.perf_counter() - t0
-    timing = sim.read_kernel_timing()
-    sim.kernel_timing(False)
+    if args.full:
+        sim.kernel_timing(True)
+        sim.read_kernel_timing()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            sim.step()
+        torch.cuda.synchronize()
+        barrier()
+        event_region = time.perf_counter() - t0
+        timing = sim.read_kernel_timing()
+        sim.kernel_timing(False)
     comm_stats = comm_after
     x1_direct_per_cycle = sim.x1_direct_exchanges() / max(1, sim.ncycle)
     skipped_per_cycle = sim.skipped_local_exchanges() / max(1, sim.ncycle)
     overlapped_per_cycle = sim.overlapped_exchanges / max(1, sim.ncycle)
     # 500 cycles back to back (N = 1): does the rate hold once the clocks have settled under the power cap?
     sustained = None
-    if world == 1 and not args.unfused and args.sustained > 0 and not (args.brick or args.meshblock):
+    if args.full and world == 1 and not args.unfused and args.sustained > 0 and not (args.brick or args.meshblock):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.sustained):
@@ -810,7 +822,7 @@ def main():
     # and unpacked.  Same workload once more with the same-rank ghost copies done as at N > 1 (a second
     # figure; `value` stays the default configuration's).
     copies_base = None
-    if world == 1 and not args.unfused and not args.no_copies_base and sim.skipped_local_exchanges() > 0:
+    if args.full and world == 1 and not args.unfused and not args.no_copies_base and sim.skipped_local_exchanges() > 0:
         sim.set_direct_neighbors(False)
         for _ in range(max(1, args.warmup)):
             sim.step()
@@ -829,38 +841,6 @@ def main():
         zones_local = int(info.zones_local)
         value = zones_total * args.steps / elapsed
         nstages = len(GAM0[integrator])
-        per_kernel = {k: (ms / n if n else 0.0) for k, (ms, n) in timing.items()}
-        # with the exchange overlapped the x1 sweep of a stage is several launches (main window +
-        # slabs): account it per stage (= per finishing-sweep launch)
-        fin = "fused_x3" if info.ndim == 3 else "fused_x2"
-        if timing[fin][1]:
-            per_kernel["fused_x1"] = timing["fused_x1"][0] / timing[fin][1]
-        # one "launch" of the fused stage = its three sweep kernels back to back
-        if args.unfused:
-            stage_ms = per_kernel["fluxes"] + per_kernel["update"] + per_kernel["dedner"]
-            stage_name = "flux-array stage: CalculateFluxes + UpdateWithFluxDivergence + DednerSource"
-        else:
-            # the high-order (PPM+HLLD) stage; the VL2 donor-cell predictor is timed in its own slots
-            stage_ms = per_kernel["fused_x1"] + per_kernel["fused_x2"] + per_kernel["fused_x3"]
-            two_kernel = info.ndim == 3 and per_kernel["fused_x2"] == 0.0 and per_kernel["fused_x3"] > 0.0
-            if two_kernel:
-                stage_name = ("fused %s+%s stage, two kernels: x3 sweep writing its flux difference (timing slot fused_x3) "
-                              "+ ONE march doing x1 (DPP stencil) and x2 (LDS ring) that finishes the stage: RK update%s, "
-                              "ConsToPrim of the interior, dt in the last stage (slot fused_x1)"
-                              % (recon.upper(), riemann.upper(), ", Dedner" if fluid == "glmmhd" else ""))
-            else:
-                stage_name = ("fused %s+%s stage: x1 DPP sweep + x2 march + x3 march (+RK update%s, +ConsToPrim of "
-                              "the interior, +dt in the last stage)" % (recon.upper(), riemann.upper(),
-                                                                        " +Dedner" if fluid == "glmmhd" else ""))
-        # high-order stages only (for vl2: the corrector, gam0 = 0)
-        ho = [g0 for n, g0 in enumerate(GAM0[integrator]) if not (integrator == "vl2" and n == 0)]
-        b_stage = sum(B_STAGE[fluid][0 if g0 == 0.0 else 1] for g0 in ho) / len(ho)
-        achieved = b_stage * zones_local / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
-        b_cycle = sum(B_STAGE[fluid][0 if g0 == 0.0 else 1] for g0 in GAM0[integrator]) + nstages * B_C2P[fluid]
-        traffic_gb, traffic_src = (None, None) if args.unfused else measured_traffic(args.workload)
-        dominant = max(("fused_x1", "fused_x2", "fused_x3", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "fluxes",
-                        "cons_to_prim", "copy_regions", "update", "min_dt"),
-                       key=lambda k: timing[k][0])
         out = {
             "metric": "cell-updates/s (zone-cycles/s) for 3D %s, uniform grid" % (
                 "MHD PPM+HLLD" if fluid == "glmmhd" else "hydro %s+%s" % (recon.upper(), riemann.upper())),
@@ -872,7 +852,6 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3,
             "timed_regions_ms": [e * 1e3 for e in regions],
             "timed_region_reported": "median of %d regions of %d cycles each (barrier + synchronize around each, max over ranks; no event records inside)" % (len(regions), args.steps),
-            "kernel_event_region_ms": event_region * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -896,7 +875,44 @@ def main():
                        # exchanges per cycle whose x1 strips bypassed the pack / unpack kernels (apk_stage_args.x1_halo)
                        "exchanges_with_x1_strips_in_the_buffers_per_cycle": x1_direct_per_cycle if world > 1 else None},
             "cell_stage_updates_per_s": value * nstages,
-            "roofline": {
+        }
+        if dumped:
+            out["dumped_outputs"] = dumped
+        if args.full:
+            out["kernel_event_region_ms"] = event_region * 1e3
+            per_kernel = {k: (ms / n if n else 0.0) for k, (ms, n) in timing.items()}
+            # with the exchange overlapped the x1 sweep of a stage is several launches (main window +
+            # slabs): account it per stage (= per finishing-sweep launch)
+            fin = "fused_x3" if info.ndim == 3 else "fused_x2"
+            if timing[fin][1]:
+                per_kernel["fused_x1"] = timing["fused_x1"][0] / timing[fin][1]
+            # one "launch" of the fused stage = its three sweep kernels back to back
+            if args.unfused:
+                stage_ms = per_kernel["fluxes"] + per_kernel["update"] + per_kernel["dedner"]
+                stage_name = "flux-array stage: CalculateFluxes + UpdateWithFluxDivergence + DednerSource"
+            else:
+                # the high-order (PPM+HLLD) stage; the VL2 donor-cell predictor is timed in its own slots
+                stage_ms = per_kernel["fused_x1"] + per_kernel["fused_x2"] + per_kernel["fused_x3"]
+                two_kernel = info.ndim == 3 and per_kernel["fused_x2"] == 0.0 and per_kernel["fused_x3"] > 0.0
+                if two_kernel:
+                    stage_name = ("fused %s+%s stage, two kernels: x3 sweep writing its flux difference (timing slot fused_x3) "
+                                  "+ ONE march doing x1 (DPP stencil) and x2 (LDS ring) that finishes the stage: RK update%s, "
+                                  "ConsToPrim of the interior, dt in the last stage (slot fused_x1)"
+                                  % (recon.upper(), riemann.upper(), ", Dedner" if fluid == "glmmhd" else ""))
+                else:
+                    stage_name = ("fused %s+%s stage: x1 DPP sweep + x2 march + x3 march (+RK update%s, +ConsToPrim of "
+                                  "the interior, +dt in the last stage)" % (recon.upper(), riemann.upper(),
+                                                                            " +Dedner" if fluid == "glmmhd" else ""))
+            # high-order stages only (for vl2: the corrector, gam0 = 0)
+            ho = [g0 for n, g0 in enumerate(GAM0[integrator]) if not (integrator == "vl2" and n == 0)]
+            b_stage = sum(B_STAGE[fluid][0 if g0 == 0.0 else 1] for g0 in ho) / len(ho)
+            achieved = b_stage * zones_local / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
+            b_cycle = sum(B_STAGE[fluid][0 if g0 == 0.0 else 1] for g0 in GAM0[integrator]) + nstages * B_C2P[fluid]
+            traffic_gb, traffic_src = (None, None) if args.unfused else measured_traffic(args.workload)
+            dominant = max(("fused_x1", "fused_x2", "fused_x3", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "fluxes",
+                            "cons_to_prim", "copy_regions", "update", "min_dt"),
+                           key=lambda k: timing[k][0])
+            out["roofline"] = {
                 # what binds the stage kernels (SQ counters); `achieved` / `peak` / `frac` are priced against HBM bandwidth,
                 # as north_star asks -- `priced_against` -- and against the fp64 vector roof in `valu`
                 # (the hydro single march as well: vector issue busy 94 % of its run time, profiles/r06_pmc_sq_hydro.json)
@@ -940,36 +956,33 @@ def main():
                                         "the reference's cycle, which this cycle no longer performs where it can derive the "
                                         "primitives in registers: a figure of how much reference traffic per second the cycle "
                                         "stands for, NOT the north-star roofline fraction (that is `frac` / `general_stage.frac`)"},
-            },
-        }
-        if dumped:
-            out["dumped_outputs"] = dumped
-        if sustained:
-            out["sustained_%d_cycles" % sustained["cycles"]] = sustained
-        if copies_base:
-            out["weak_scaling_base_with_ghost_copies"] = copies_base
-        if world == 1 and fluid == "glmmhd" and not args.unfused:
-            try:
-                sim.close()
-                out["roofline"]["general_stage"] = general_stage_bench(recon, riemann)
-                if recon == "ppm" and riemann == "hlld":
-                    out["roofline"]["valu"] = valu_roofline(out["roofline"]["general_stage"]["ms_per_stage"])
-            except Exception as e:  # supplementary figure; never lose the headline
-                out["roofline"]["general_stage"] = {"error": repr(e)}
-        if world == 1 and not args.unfused and not args.no_rehearsal and not (args.brick or args.meshblock):
-            try:
-                out["rehearsal_8gpu_rank"] = rehearsal_8gpu_rank(args.workload, elapsed / args.steps * 1e3)
-            except Exception as e:  # supplementary figure
-                out["rehearsal_8gpu_rank"] = {"error": repr(e)}
-        if world == 1 and not args.unfused and not args.no_other_workloads and not (args.brick or args.meshblock) \
-                and args.workload == "mhd_ppm_hlld_vl2_256":
-            out["other_workloads"] = other_workloads()
+            }
+            if sustained:
+                out["sustained_%d_cycles" % sustained["cycles"]] = sustained
+            if copies_base:
+                out["weak_scaling_base_with_ghost_copies"] = copies_base
+            if world == 1 and fluid == "glmmhd" and not args.unfused:
+                try:
+                    sim.close()
+                    out["roofline"]["general_stage"] = general_stage_bench(recon, riemann)
+                    if recon == "ppm" and riemann == "hlld":
+                        out["roofline"]["valu"] = valu_roofline(out["roofline"]["general_stage"]["ms_per_stage"])
+                except Exception as e:  # supplementary figure; never lose the headline
+                    out["roofline"]["general_stage"] = {"error": repr(e)}
+            if world == 1 and not args.unfused and not args.no_rehearsal and not (args.brick or args.meshblock):
+                try:
+                    out["rehearsal_8gpu_rank"] = rehearsal_8gpu_rank(args.workload, elapsed / args.steps * 1e3)
+                except Exception as e:  # supplementary figure
+                    out["rehearsal_8gpu_rank"] = {"error": repr(e)}
+            if world == 1 and not args.unfused and not args.no_other_workloads and not (args.brick or args.meshblock) \
+                    and args.workload == "mhd_ppm_hlld_vl2_256":
+                out["other_workloads"] = other_workloads()
         if world == 1 and args.amr_extra:
             try:
                 out["amr_blast_cfg5"] = amr_blast_bench()
             except Exception as e:  # supplementary figure
                 out["amr_blast_cfg5"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(fluid, integrator, recon, riemann)
             except Exception as e:  # the baseline is informational; never lose the GPU number

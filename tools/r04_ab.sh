@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 for rep in 1 2; do for cfg in "default:" "$@"; do
  label="${cfg%%:*}"; envs="${cfg#*:}"
- env $envs python bench.py --no-cpu-baseline --no-copies-base ${BENCH_ARGS} 2>/dev/null | python -c "
+ env $envs python bench.py --full --no-cpu-baseline --no-copies-base ${BENCH_ARGS} 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline()); k=d['roofline']['per_kernel_avg_ms']
 g=d['roofline'].get('general_stage',{}).get('ms_per_stage',0)
