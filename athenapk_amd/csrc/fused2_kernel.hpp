@@ -231,7 +231,6 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
     // addresses, unused values)
     [[maybe_unused]] int64_t lsn = u0.sn;  // (X1H: per lane)
     [[maybe_unused]] int gseg = 0;       // (X1H: per lane, tested afresh at every use -- see X1Store)
-#ifndef APK_X1H_NO_RECV
     if constexpr (X1H) {
       if (sp.x1_blocks && sp.x1_recv_depth > 0 && ((i < u0.is) || (i > u0.ie))) {
         const int dpt = sp.x1_recv_depth, side = (i < u0.is) ? 0 : 1;
@@ -244,7 +243,6 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
         }
       }
     }
-#endif
     const auto prim = as_global(prim_generic);
     auto row_off = [&](int r) -> int64_t {
       const int64_t d = (r < u0.js) ? nbr_lo : ((r > u0.je) ? nbr_hi : (int64_t)0);  // wave-uniform
@@ -278,9 +276,7 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
     };
     // x1_halo, send side
     [[maybe_unused]] X1Store xs;
-#ifndef APK_X1H_NO_SEND
     if constexpr (X1H) xs = x1_store_of<true>(sp, u0, b, i, active, (int64_t)krow * sp.x1_send_depth * u0.nx2, sp.x1_send_depth);
-#endif
 
     int c = s - 1;
     const int r0 = c - H;
@@ -635,8 +631,6 @@ inline int resident_march_waves() {
 // BASELINE config 5 (232 blocks of 16^3, MHD PPM+HLLD, nghost 4): 8.52e8 against 8.36e8 zone-cycles/s for the
 // three-sweep schedule with several rows per wave, so 16-cell blocks take it too; narrower ones do not.
 inline bool two_kernel_stage_applies(const PackView &u0, int recon, int extra, const StageParams &sp) {
-  static const int mode = std::getenv("APK_STAGE_MODE") ? std::atoi(std::getenv("APK_STAGE_MODE")) : 2;  // A/B switch: 3 = three sweeps
-  if (mode == 3) return false;
   constexpr int min_nx1 = 16;
   // (blocks narrower than 32 cells only if they are deep enough along x3 for the plane windows of a split stage --
   // 4 nghost planes: the driver's overlap rule -- so that taking this form never costs an overlapped exchange)

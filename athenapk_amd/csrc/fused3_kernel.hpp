@@ -320,17 +320,16 @@ fused_s3_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, int
 // a conserved state (what a prim-free RK cycle asks of every stage), whole blocks (a split stage keeps the two kernels:
 // its x3 sweep runs on plane windows while the halo messages fly), an even number of x2 rows, no primitives stored.
 // Hydro with PLM for now: 256 VGPRs, no scratch (WENO3 / LimO3 spill 44 - 98 registers in this form, GLM-MHD would hold
-// 2 x 9 x 7 doubles across a Riemann solve): the others keep the two-kernel stage.  APK_S3=0 switches it off (A/B).
+// 2 x 9 x 7 doubles across a Riemann solve): the others keep the two-kernel stage.
 template <int FLUID, int RECON>
 constexpr bool single_march_compiled() { return FLUID == APK_FLUID_EULER && RECON == APK_RC_PLM; }
 template <int FLUID, int RECON>
 inline bool single_march_stage_applies(const PackView &u0, int extra, const StageParams &sp) {
-  static const int mode = std::getenv("APK_S3") ? std::atoi(std::getenv("APK_S3")) : 1;
   if constexpr (!single_march_compiled<FLUID, RECON>()) return false;
   // (rows of 32 cells and more: on the 16^3 blocks of a refined mesh the march's x1 halo lanes outnumber its cells and the
   // two-kernel form is faster -- refined hydro blast of BASELINE config 5, zone-cycles/s, same box: 16^3 blocks 2.02e9 with
   // this march against 2.32e9 with the two-kernel stage; 32^3: 4.55e9 against 4.17e9; 48^3: 5.85e9 against 5.23e9)
-  return mode != 0 && u0.ndim == 3 && u0.nx1 >= 32 && (uint64_t)u0.sn * sizeof(double) < (1ull << 32) && sp.prim_from_cons != 0 && sp.phase == 0 && sp.window == nullptr && stage_is_lean(sp) &&
+  return u0.ndim == 3 && u0.nx1 >= 32 && (uint64_t)u0.sn * sizeof(double) < (1ull << 32) && sp.prim_from_cons != 0 && sp.phase == 0 && sp.window == nullptr && stage_is_lean(sp) &&
          u0.nx2 % 2 == 0 && u0.nx2 >= 4 && u0.ng >= 2 && (extra == EXTRA_NONE || (extra == EXTRA_C2P_DT && sp.no_prim_store)) &&
          (sp.prim_from_cons == 1 || sp.out_delta != 0);
 }
@@ -344,9 +343,7 @@ inline void launch_s3(const PackView &u0, const PackView &u1, const StageParams 
     // stage): 8 planes 0.742, 12: 0.749, 13: 0.747, **14: 0.705, 15: 0.705**, 16: 0.722, 19: 0.723, 22: 0.737, 24: 0.730,
     // 32: 0.795, 64: 0.97 -- 15 (nine segments, 10152 waves = 4.96 rounds of the 2048 the device holds) where 16 is
     // 4.41 rounds with the fifth one mostly empty
-    static const int forced_kseg = std::getenv("APK_S3_KSEG") ? std::atoi(std::getenv("APK_S3_KSEG")) : 0;  // A/B switch
-    int kseg = forced_kseg > 0 ? forced_kseg : 15;
-    if (kseg > u0.nx3) kseg = u0.nx3;
+    const int kseg = u0.nx3 < 15 ? u0.nx3 : 15;
     const int nseg = (u0.nx3 + kseg - 1) / kseg;
     const int64_t total = (int64_t)wpb * nseg * u0.nblocks;
     const int per_xcd = (int)((total + 7) / 8);

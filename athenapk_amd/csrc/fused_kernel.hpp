@@ -1312,7 +1312,6 @@ fused_dc3r2_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, 
   [[maybe_unused]] int64_t lsn = u0.sn;  // (X1H: per lane)
   [[maybe_unused]] int lsk = (int)u0.sk, lsj = (int)u0.sj;  // (a block's plane fits 31 bits: two_kernel_stage_applies' rule for sn)
   [[maybe_unused]] bool gseg = false;
-#ifndef APK_X1H_NO_RECV
   if constexpr (X1H) {
     if (sp.x1_blocks && sp.x1_recv_depth > 0 && (i < u0.is || i > u0.ie)) {
       const int dpt = sp.x1_recv_depth, side = (i < u0.is) ? 0 : 1;
@@ -1330,16 +1329,13 @@ fused_dc3r2_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, 
       }
     }
   }
-#endif
   auto plane = [&](int c) -> int {  // (wave-uniform candidates, chosen per lane)
     if constexpr (X1H) return gseg ? ((c < u0.ks) ? u0.ks : ((c > u0.ke) ? u0.ke : c)) : c;
     else return c;
   };
   // x1_halo, send side: cell A's place; cell B's is one row (lsj of the segment = send_depth) further
   [[maybe_unused]] X1Store xs;
-#ifndef APK_X1H_NO_SEND
   if constexpr (X1H) xs = x1_store_of<false>(sp, u0, b, i, active, (int64_t)(ja - u0.js) * sp.x1_send_depth, (int64_t)sp.x1_send_depth * u0.nx2);
-#endif
   const double area1 = b0.dx[1] * b0.dx[2], area2 = b0.dx[0] * b0.dx[2], area3 = b0.dx[0] * b0.dx[1];
   const double vol = b0.dx[0] * b0.dx[1] * b0.dx[2];
   const double upd = update_coefficient(sp, vol);

@@ -99,6 +99,12 @@ struct Mesh {
     bc[2] = gid / (nb[0] * nb[1]);
   }
   bool Active(int d) const { return mb[d] > 1; }
+  // both boundaries of every active direction periodic
+  bool AllPeriodic() const {
+    for (int d = 0; d < 3; ++d)
+      if (Active(d) && (bc_in[d] != BC_PERIODIC || bc_out[d] != BC_PERIODIC)) return false;
+    return true;
+  }
 
   void Build() {
     for (int d = 0; d < 3; ++d) {

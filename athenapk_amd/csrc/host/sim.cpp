@@ -1,6 +1,7 @@
 // sim.cpp -- the standalone host driver (include/apk_host.h): deck -> packages and mesh, device
 // resources and plans, ghost exchange, the stage loop, outputs and the C API.
 #include "sim_internal.hpp"
+#include "../hydro_math.hpp"
 
 using namespace apk;
 
@@ -602,19 +603,11 @@ int exchange_ghosts(apk_sim *s, int c2p, bool skip_local, bool thin) {
 // turbulence driver, into the kick; an exchange followed by a full-block ConsToPrim is a complete one.)
 // one rank, every active direction periodic: the face table covers every face of every block, so an exchange that
 // follows it has no ghost zone left to fill (edges and corners are read by no stage that follows the table)
-bool table_covers_all_faces(const apk_sim *s) {
-  const Mesh &m = s->mesh;
-  if (!m.peers.empty()) return false;
-  for (int d = 0; d < 3; ++d)
-    if (m.Active(d) && (m.bc_in[d] != BC_PERIODIC || m.bc_out[d] != BC_PERIODIC)) return false;
-  return true;
-}
+bool table_covers_all_faces(const apk_sim *s) { return s->mesh.peers.empty() && s->mesh.AllPeriodic(); }
 
 bool direct_neighbors(const apk_sim *s) {
-  static const int mode = std::getenv("APK_DIRECT_NEIGHBORS") ? std::atoi(std::getenv("APK_DIRECT_NEIGHBORS")) : 1;  // A/B switch
-  static const int dc_mode = std::getenv("APK_DC_MODE") ? std::atoi(std::getenv("APK_DC_MODE")) : 2;
   const HydroPackage &pkg = s->pkg;
-  if (!mode || !s->direct_on || !s->d_face_nbr || s->amr || s->mesh.ndim != 3) return false;
+  if (!s->direct_on || !s->d_face_nbr || s->amr || s->mesh.ndim != 3) return false;
   // first-order flux correction: every stage runs as the optimistic fused stage (do_stage) -- the same kernels with the
   // admissibility test in the finishing sweep; a stage that fails it is redone through the flux arrays, which read ghost
   // zones: do_stage fills them first (materialize_local_ghosts).  One-rank periodic boxes, no forcing.
@@ -628,13 +621,8 @@ bool direct_neighbors(const apk_sim *s) {
   if (pkg.nscalars != 0 || (!ghost_c2p_fusable(s) && !table_covers_all_faces(s))) return false;
   if (pkg.fluid == APK_FLUID_GLMMHD && pkg.glmmhd_source_extended) return false;
   const apk_flux_cfg *cfgs[2] = {&pkg.flux_first_stage, &pkg.flux_other_stage};
-  for (const apk_flux_cfg *cfg : cfgs) {
-    if (cfg->recon == APK_RC_DC) {
-      if (dc_mode != 2) return false;
-    } else if (apk_stage_split_axis(s->mu0(), cfg, 2) != 3) {
-      return false;
-    }
-  }
+  for (const apk_flux_cfg *cfg : cfgs)
+    if (cfg->recon != APK_RC_DC && apk_stage_split_axis(s->mu0(), cfg, 2) != 3) return false;
   return true;
 }
 
@@ -643,9 +631,8 @@ bool direct_neighbors(const apk_sim *s) {
 // those copies and their ConsToPrim (AMR_XCHG_DIRECT).  The stage forms that follow the table: the single-march
 // donor-cell stage and the two-kernel stage (launch_fused_stage); refined-mesh stages run without FillDerived.
 bool amr_direct(const apk_sim *s) {
-  static const int mode = std::getenv("APK_DIRECT_NEIGHBORS") ? std::atoi(std::getenv("APK_DIRECT_NEIGHBORS")) : 1;  // A/B switch
   const HydroPackage &pkg = s->pkg;
-  if (!mode || !s->direct_on || !s->amr || !s->d_face_nbr || s->mesh.ndim != 3 || !stage_can_fuse(s) || !amr_faces_only(s)) return false;
+  if (!s->direct_on || !s->amr || !s->d_face_nbr || s->mesh.ndim != 3 || !stage_can_fuse(s) || !amr_faces_only(s)) return false;
   if (pkg.nscalars != 0 || (pkg.fluid == APK_FLUID_GLMMHD && pkg.glmmhd_source_extended)) return false;
   const apk_flux_cfg *cfgs[2] = {&pkg.flux_first_stage, &pkg.flux_other_stage};
   for (const apk_flux_cfg *cfg : cfgs)
@@ -702,13 +689,10 @@ int materialize_local_ghosts(apk_sim *s, int buf) {
 // not store primitives?  The single-march donor-cell stage in its lean form (uniform 3-D mesh, VL2), and a last stage
 // that is the lean two-kernel stage with the time-step estimate fused in.
 bool prim_free_cycle(const apk_sim *s) {
-  static const int mode = std::getenv("APK_PRIM_FREE") ? std::atoi(std::getenv("APK_PRIM_FREE")) : 1;  // A/B switch
-  static const int dc_mode = std::getenv("APK_DC_MODE") ? std::atoi(std::getenv("APK_DC_MODE")) : 2;
   const HydroPackage &pkg = s->pkg;
-  if (!mode || !s->prim_free_on || s->amr || s->fmft || s->mesh.ndim != 3 || !stage_can_fuse(s) || dc_mode != 2) return false;
+  if (!s->prim_free_on || s->amr || s->fmft || s->mesh.ndim != 3 || !stage_can_fuse(s)) return false;
   if (pkg.nscalars != 0 || (pkg.fluid == APK_FLUID_GLMMHD && pkg.glmmhd_source_extended) || !pkg.calc_dt_hyp) return false;
-  const apk_eos &e = pkg.eos;
-  if (!(e.vceil > 1.0e300 && e.eceil > 1.0e300 && e.pfloor <= 0.0)) return false;  // (eos_is_lean)
+  if (!eos_is_lean(pkg.eos)) return false;
   if (pkg.flux_first_stage.recon != APK_RC_DC || pkg.flux_other_stage.recon == APK_RC_DC || s->nstages < 2) return false;
   return apk_stage_split_axis(s->mu0(), &pkg.flux_other_stage, 2) == 3;
 }
@@ -717,16 +701,15 @@ bool prim_free_cycle(const apk_sim *s) {
 // stage derives its input from the conserved state (apk_stage_args.prim_from_cons: u1's in stages with gam0 = 0, u0's
 // with an out-of-place result in the others -- a third buffer in rotation, as for the trial stages of first-order flux
 // correction) and stores no primitives; the last one computes them for the time-step estimate (fill_derived = 3).
-// APK_RK_PRIM_FREE=0 switches it off (A/B).
+// apk_sim_set_prim_free(0) switches it off.
 bool rk_prim_free_cycle(const apk_sim *s) {
-  static const int mode = std::getenv("APK_RK_PRIM_FREE") ? std::atoi(std::getenv("APK_RK_PRIM_FREE")) : 1;  // A/B switch
   const HydroPackage &pkg = s->pkg;
   // (forced turbulence included: its kick after the last stage estimates the time step without storing primitives,
   // apk_turb_apply_dt)
-  if (!mode || !s->prim_free_on || s->amr || s->mesh.ndim != 3 || !stage_can_fuse(s)) return false;
+  if (!s->prim_free_on || s->amr || s->mesh.ndim != 3 || !stage_can_fuse(s)) return false;
   if (pkg.nscalars != 0 || (pkg.fluid == APK_FLUID_GLMMHD && pkg.glmmhd_source_extended) || !pkg.calc_dt_hyp) return false;
   const apk_eos &e = pkg.eos;
-  if (!(e.vceil > 1.0e300 && e.eceil > 1.0e300 && e.pfloor <= 0.0)) return false;  // (eos_is_lean)
+  if (!eos_is_lean(e)) return false;
   // Stages that are not the last store their result without ConsToPrim (fill_derived = 0): a density or internal-energy
   // floor would act on the register copy the next stage converts but never reach the stored conserved state, where the
   // reference's FillDerived after every stage writes the floored values back (adiabatic_hydro.hpp:81,129-136).  With
@@ -741,17 +724,13 @@ bool rk_prim_free_cycle(const apk_sim *s) {
 // between the two stages, 38 of 810 us per cycle on config 5's mesh -- and the flux correction's boundary planes likewise
 // (apk_calculate_fluxes_boundary_list_from_cons)?  The corrector's result goes over the register u1, cell by cell the
 // value the lane has just read, and the two buffers swap roles.  No floors or ceilings (the in-register ConsToPrim is
-// the lean one and writes nothing back), no passive scalars, no forcing.  apk_sim_set_prim_free(0) / APK_AMR_PRIM_FREE=0
-// switch it off (A/B).
+// the lean one and writes nothing back), no passive scalars, no forcing.  apk_sim_set_prim_free(0) switches it off.
 bool amr_prim_free_cycle(const apk_sim *s) {
-  static const int mode = std::getenv("APK_AMR_PRIM_FREE") ? std::atoi(std::getenv("APK_AMR_PRIM_FREE")) : 1;
-  static const int dc_mode = std::getenv("APK_DC_MODE") ? std::atoi(std::getenv("APK_DC_MODE")) : 2;  // (the predictor's form)
   const HydroPackage &pkg = s->pkg;
-  if (dc_mode != 2) return false;
-  if (!mode || !s->prim_free_on || !s->amr || s->fmft || s->mesh.ndim != 3 || !stage_can_fuse(s) || !amr_faces_only(s)) return false;
+  if (!s->prim_free_on || !s->amr || s->fmft || s->mesh.ndim != 3 || !stage_can_fuse(s) || !amr_faces_only(s)) return false;
   if (pkg.nscalars != 0 || (pkg.fluid == APK_FLUID_GLMMHD && pkg.glmmhd_source_extended)) return false;
   const apk_eos &e = pkg.eos;
-  if (!(e.vceil > 1.0e300 && e.eceil > 1.0e300 && e.pfloor <= 0.0 && e.dfloor <= 0.0 && e.efloor <= 0.0)) return false;
+  if (!eos_is_lean(e) || e.dfloor > 0.0 || e.efloor > 0.0) return false;
   if (pkg.flux_first_stage.recon != APK_RC_DC || pkg.flux_other_stage.recon == APK_RC_DC || s->nstages != 2) return false;
   if (s->gam0[1] != 0.0) return false;  // (the corrector must not read the old u0: VL2)
   return apk_stage_split_axis(s->mu0(), &pkg.flux_other_stage, 0) == 3 && apk_stage_split_axis(s->mu0(), &pkg.flux_other_stage, 2) == 3;
@@ -761,18 +740,13 @@ bool amr_prim_free_cycle(const apk_sim *s) {
 // next cycle must be the single-march donor-cell stage (it reads one layer; the corrector's exchange stays a full one),
 // nothing else in a cycle may read ghost zones (no forcing, no refinement), and the box must be periodic: a physical
 // boundary phase copies corner cells out of ghost zones the messages fill.  Uniform 3-D meshes, exchanges left in
-// flight (the path of N > 1 runs).  APK_THIN_EXCHANGE=0 switches it off (A/B).
+// flight (the path of N > 1 runs).  apk_sim_set_thin_exchange(0) switches it off.
 bool thin_exchange_cycle(const apk_sim *s) {
-  static const int mode = std::getenv("APK_THIN_EXCHANGE") ? std::atoi(std::getenv("APK_THIN_EXCHANGE")) : 1;
-  static const int dc_mode = std::getenv("APK_DC_MODE") ? std::atoi(std::getenv("APK_DC_MODE")) : 2;
   const HydroPackage &pkg = s->pkg;
   const Mesh &mm = s->mesh;
-  if (!mode || !s->thin_on || s->amr || s->fmft || mm.ndim != 3 || mm.peers.empty() || !stage_can_fuse(s) || dc_mode != 2) return false;
+  if (!s->thin_on || s->amr || s->fmft || mm.ndim != 3 || mm.peers.empty() || !stage_can_fuse(s)) return false;
   if (mm.ng <= kThinDepth || pkg.nscalars != 0 || (pkg.fluid == APK_FLUID_GLMMHD && pkg.glmmhd_source_extended)) return false;
-  if (pkg.flux_first_stage.recon != APK_RC_DC || s->nstages < 2) return false;
-  for (int d = 0; d < 3; ++d)
-    if (mm.bc_in[d] != BC_PERIODIC || mm.bc_out[d] != BC_PERIODIC) return false;
-  return true;
+  return pkg.flux_first_stage.recon == APK_RC_DC && s->nstages >= 2 && mm.AllPeriodic();
 }
 
 // May the x1 strips of this cycle's exchanges bypass the pack / unpack kernels (apk_stage_args.x1_halo)?  On a uniform
@@ -782,15 +756,12 @@ bool thin_exchange_cycle(const apk_sim *s) {
 //   2  the RK integrators whose stages all derive their input from the conserved state (rk_prim_free_cycle) in the
 //      two-kernel form: every exchange moves the conserved state nghost deep, and every finishing march stores its x1
 //      strips into the messages and reads the ones of the stage before from them;
-// both in stage forms that follow the table.  0: neither.  APK_X1_DIRECT=0: off (A/B).
+// both in stage forms that follow the table.  0: neither.  apk_sim_set_x1_direct(0) switches it off.
 int x1_direct_kind(const apk_sim *s) {
-  static const int mode = std::getenv("APK_X1_DIRECT") ? std::atoi(std::getenv("APK_X1_DIRECT")) : 1;
   const HydroPackage &pkg = s->pkg;
   const Mesh &mm = s->mesh;
-  if (!mode || !s->x1_on || !s->d_x1_tab[0] || mm.mb[0] < 2 * mm.ng || mm.peers.empty()) return 0;
+  if (!s->x1_on || !s->d_x1_tab[0] || mm.mb[0] < 2 * mm.ng || mm.peers.empty() || !mm.AllPeriodic()) return 0;
   if (!direct_neighbors(s) || !ghost_c2p_fusable(s)) return 0;
-  for (int d = 0; d < 3; ++d)
-    if (mm.bc_in[d] != BC_PERIODIC || mm.bc_out[d] != BC_PERIODIC) return 0;
   const int ded = (pkg.fluid == APK_FLUID_GLMMHD) ? 1 : 0;
   if (s->nstages == 2 && thin_exchange_cycle(s) && prim_free_cycle(s)) {
     return (apk_stage_x1_halo(s->mu0(), &pkg.flux_first_stage, &pkg.eos, 2, ded, 1) == 1 &&
@@ -1194,16 +1165,13 @@ int do_stage(apk_sim *s, int stage) {
     // let the finishing sweep do FillDerived (and, in the last stage, the dt estimate) on the
     // cells it updates; only the ghost zones are converted after the exchange
     // (not when the turbulence driver kicks the state after this stage)
-    // nor in a 3-D donor-cell stage (the VL2 predictor): its single-march kernel leaves prim
-    // untouched and the full ConservedToPrimitive pass is cheaper than the du round trip it avoids
     // nor on refined meshes (the flux correction changes cells after the stage; the full pass after
     // the multilevel exchange converts everything)
     fused_fill = (s->mesh.ndim >= 2) && !(s->fmft && stage == s->nstages) && !s->amr;
     // A 3-D donor-cell stage (the VL2 predictor) runs as ONE march whose lanes read their
     // neighbours' primitives from memory, so it cannot replace prim in place: it writes the new
     // primitives into the spare buffer ("u1.prim") and the two prim buffers swap roles.
-    static const int dc_mode = std::getenv("APK_DC_MODE") ? std::atoi(std::getenv("APK_DC_MODE")) : 2;  // A/B switch
-    const bool dc3 = cfg.recon == APK_RC_DC && s->mesh.ndim == 3 && dc_mode != 0;
+    const bool dc3 = cfg.recon == APK_RC_DC && s->mesh.ndim == 3;
     bool swap_prim = false;
     // waves of the finishing march if it cannot be cut into segments (an in-place ConsToPrim forbids
     // that): lanes along x1, one wave per transverse row (or 2 / 4 rows for narrow blocks)
@@ -1214,14 +1182,12 @@ int do_stage(apk_sim *s, int stage) {
     const bool few_waves = mm.ndim >= 2 && final_waves < 2048;
     // (the two-kernel 3-D stage: its finishing march reads x1 neighbours from memory -- out of place)
     const bool two_kernel = mm.ndim == 3 && cfg.recon != APK_RC_DC && apk_stage_split_axis(s->mu0(), &cfg, 2) == 3;
-    if (fused_fill && ((dc3 && dc_mode == 2) || a.dedner == 2 || few_waves || two_kernel)) {
+    if (fused_fill && (dc3 || a.dedner == 2 || few_waves || two_kernel)) {
       // (the extended Dedner source reads neighbouring primitives as well: out of place, too; and a
       // finishing march with too few waves to fill the GPU -- 2-D meshes, small packs -- runs out of
       // place so that it can be cut into segments)
       SIM_TRY(s, ensure_spare_prim(s));
       swap_prim = true;
-    } else if (dc3) {
-      fused_fill = false;  // dc_mode 1: single march, separate full ConservedToPrimitive
     }
     a.fill_derived = fused_fill ? (swap_prim ? 2 : 1) : 0;
     a.estimate_dt = (fused_fill && stage == s->nstages && pkg.calc_dt_hyp) ? 1 : 0;
@@ -1250,9 +1216,7 @@ int do_stage(apk_sim *s, int stage) {
       // half-step CONSERVED state is read by nobody but the ghost exchange -- the nghost-deep shell of every block --
       // and by nothing at all when every face is crossed through the face table (apk_stage_args.cons_store).
       const bool dead = dc3 && swap_prim && stage < s->nstages && s->gam0[stage] == 0.0 && !s->amr && !s->fmft && pkg.nscalars == 0;
-      bool all_periodic = true;
-      for (int d = 0; d < 3; ++d)
-        if (mm.Active(d) && (mm.bc_in[d] != BC_PERIODIC || mm.bc_out[d] != BC_PERIODIC)) all_periodic = false;
+      const bool all_periodic = mm.AllPeriodic();
       // (physical boundary phases copy conserved values out of ghost zones filled before them: periodic boxes only)
       // On a periodic box the exchange after this stage moves the stored primitives themselves (GHOST_PRIM_COPY below;
       // floors / ceilings keep the unfused order copy, then ConsToPrim of the ghost zones, which reads the shell):
@@ -1273,9 +1237,9 @@ int do_stage(apk_sim *s, int stage) {
     // deep and reads the one-layer conserved strips the corrector of the cycle before sent; the corrector the other way
     // round.  The receive side only when the exchange this stage follows left the strips in the buffers.
     apk_x1_halo x1h{};
+    const bool from_buffers = s->exchange_pending ? s->xchg_x1_direct : s->x1_in_recv;
     {
       const int x1kind = x1_direct_kind(s);
-      const bool from_buffers = s->exchange_pending ? s->xchg_x1_direct : s->x1_in_recv;
       if (x1kind == 1) {
         const bool predictor = stage == 1 && dc3 && swap_prim && ghost_cons_dead && a.cons_store == 2;
         const bool corrector = stage == s->nstages && stage > 1 && two_kernel && no_prim;
@@ -1297,7 +1261,7 @@ int do_stage(apk_sim *s, int stage) {
         if (x1h.recv_depth > 0 || x1h.send_depth > 0) a.x1_halo = &x1h;
       }
     }
-    if (s->x1_in_recv && !(a.x1_halo && x1h.recv_depth > 0))
+    if (from_buffers && !(a.x1_halo && x1h.recv_depth > 0))
       return fail(s, APK_ERR_INVALID, "do_stage: x1 ghost columns were left in the receive buffers for a stage that does not read them there");
     if (s->exchange_pending) {
       // The previous stage's halo messages are still in flight.  Ghost zones filled by same-rank
@@ -1518,17 +1482,14 @@ int do_stage(apk_sim *s, int stage) {
     // ConsToPrim and the next cycle's predictor all follow the table there)
     // (periodic boxes only: a physical-boundary phase copies the edge cells next to the boundary out of ghost zones
     // filled before it, and the tagging criteria read those edges)
-    bool dir = amr_direct(s);
-    for (int d = 0; d < 3; ++d)
-      if (s->mesh.Active(d) && (s->mesh.bc_in[d] != BC_PERIODIC || s->mesh.bc_out[d] != BC_PERIODIC)) dir = false;
+    const bool dir = amr_direct(s) && s->mesh.AllPeriodic();
     SIM_TRY(s, amr_exchange(s, s->cur, dir ? AMR_XCHG_SHELL_DIRECT : AMR_XCHG_SHELL));
     if (dir) s->skipped_local_exchanges += 1;
     int crit = -1;
     double crit_p0 = 0.0, crit_p1 = 0.0;
     if (amr_pf && pkg.calc_dt_hyp) SIM_TRY(s, refinement_criterion(s, &crit, &crit_p0, &crit_p1));
-    static const int fused_tag = std::getenv("APK_AMR_FUSED_TAG") ? std::atoi(std::getenv("APK_AMR_FUSED_TAG")) : 1;  // A/B switch
     bool tags_done = false;
-    if (crit == APK_TAG_PRESSURE_GRADIENT && fused_tag && s->mesh.ndim == 3) {
+    if (crit == APK_TAG_PRESSURE_GRADIENT && s->mesh.ndim == 3) {
       // (... and for the pressure gradient not even that: the criterion is reduced in the same pass, its pressures in LDS)
       int pending = 0;
       const int rc_tag = apk_tag_blocks_dt_from_cons(s->ctx, s->mu0(), pkg.fluid, &pkg.eos, dir ? s->d_face_nbr : nullptr, &pending, s->stream);

@@ -205,7 +205,7 @@ struct apk_sim {
   //   xchg_x1_direct  the exchange begun last leaves the x1 ghost columns in the receive buffers (unpacks without them)
   //   x1_in_recv      ... and has completed: the next stage reads them there.  Always together with a one-layer exchange
   //                   (remote_ghosts_thin: whoever else reads ghost zones repeats the exchange in full) or inside a cycle.
-  bool x1_on = true;  // apk_sim_set_x1_direct / APK_X1_DIRECT=0 (A/B)
+  bool x1_on = true;  // apk_sim_set_x1_direct
   void *d_x1_tab[3] = {nullptr, nullptr, nullptr};  // ([2]: full messages both ways -- the RK integrators)
   bool x1_out_direct = false, xchg_x1_direct = false, x1_in_recv = false;
   long long x1_direct_exchanges = 0;
@@ -235,7 +235,7 @@ struct apk_sim {
   // donor-cell predictor -- derives its input from the conserved state (prim_from_cons).  Whatever else reads
   // primitives goes through sync_ghosts(), which materialises them (ConsToPrim of every block).
   bool prim_stale = false;
-  bool prim_free_on = true;  // apk_sim_set_prim_free / APK_PRIM_FREE=0 (A/B)
+  bool prim_free_on = true;  // apk_sim_set_prim_free
   long long skipped_local_exchanges = 0;
   // ... or the criterion itself was reduced with the time-step estimate at the end of the last stage
   // (apk_tag_blocks_dt_from_cons): amr_tags_begin hands this request on instead of launching one

@@ -547,7 +547,7 @@ int amr_rebuild(apk_sim *s) {
     SIM_HIP(s, hipMemcpy(s->d_face_nbr, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
   }
   // (a graph launch costs the host ~8 us and the stream a gap of that size: with no messages to wait for between the
-  // halves -- one rank -- an exchange is ONE graph; APK_NO_GRAPH=1 launches everything one by one)
+  // halves -- one rank -- an exchange is ONE graph)
   a.xchg_whole = s->amr_halo.plan.peers.empty() && s->amr_halo_faces.plan.peers.empty() && s->amr_halo_shell.plan.peers.empty();
   const bool w = a.xchg_whole;
   for (int par = 0; par < 2; ++par) {
@@ -608,8 +608,6 @@ int amr_exchange_post(apk_sim *s, int buf, int mode) {
 // whole (with pre): both halves in one graph -- for meshes whose exchange has no messages between them
 void amr_capture_half(apk_sim *s, int buf, bool pre, int mode, void **out, bool whole) {
   *out = nullptr;
-  static const bool disabled = std::getenv("APK_NO_GRAPH") != nullptr;  // A/B switch
-  if (disabled) return;
   hipStream_t cs = nullptr;
   if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) return;
   hipGraph_t graph = nullptr;

@@ -340,7 +340,7 @@ APK_DEV void ppm(double qm2, double qm1, double q0, double qp1, double qp2, doub
 }
 
 // src/recon/wenoz_simple.hpp:28-81
-#if defined(APK_FP_STRICT) || defined(APK_PLAIN_SQRT) || defined(APK_WENOZ_REF_FORM)
+#if defined(APK_FP_STRICT) || defined(APK_PLAIN_SQRT)
 APK_DEV void wenoz(double qm2, double qm1, double q0, double qp1, double qp2, double &ql,
                    double &qr) {
   constexpr double c0 = 13. / 12., c1 = 0.25;
@@ -349,18 +349,9 @@ APK_DEV void wenoz(double qm2, double qm1, double q0, double qp1, double qp2, do
   const double b2 = c0 * sqr(qp2 + q0 - 2.0 * qp1) + c1 * sqr(qp2 + 3.0 * q0 - 4.0 * qp1);
   constexpr double eps = 1.0e-42;
   const double tau5 = fabs(b0 - b2);
-#ifdef APK_WENOZ_REF_FORM
-  const double p0 = b0 + eps, p1 = b1 + eps, p2 = b2 + eps;
-  const double p01 = p0 * p1;
-  const double tinv = tau5 * frcp48(p01 * p2);
-  const double i0 = tinv * (p1 * p2);
-  const double i1 = tinv * (p0 * p2);
-  const double i2 = tinv * p01;
-#else
   const double i0 = fdiv(tau5, (b0 + eps));
   const double i1 = fdiv(tau5, (b1 + eps));
   const double i2 = fdiv(tau5, (b2 + eps));
-#endif
 
   double f0 = (2.0 * qm2 - 7.0 * qm1 + 11.0 * q0);
   double f1 = (-1.0 * qm1 + 5.0 * q0 + 2.0 * qp1);
@@ -1268,7 +1259,7 @@ APK_DEV unsigned cons_to_prim_core(const apk_eos &eos, double gm1, double vceil_
   // kernels -- on a refined mesh the stage kernels AND the kernel of the flux correction's boundary planes, whose flux
   // through a coarse-fine face has to be the one the stage applied: with primitives that differed in the last bit between
   // the two, PPM's limiters now and then decided differently, the correction subtracted a flux the stage had not used, and
-  // the mass of the refined MHD blast drifted by 1e-6 in 1500 cycles (round 6, tools/soak_r06.py; 2e-16 with this).
+  // the mass of the refined MHD blast drifted by 1e-6 in 1500 cycles (round 6, tools/soak_r06.py -- in the history at 8a567ba; 2e-16 with this).
   // (frcp's Newton steps are explicit fma calls: the same everywhere.)
 #pragma clang fp contract(off)
   constexpr bool mhd = (FLUID == APK_FLUID_GLMMHD);

@@ -605,7 +605,8 @@ copy_regions_kernel(const apk_copy_region *regions, const apk_copy_chunk *chunks
 // The same copy, one thread per CELL of a chunk of at most kCopyChunkCells cells, moving all of its variables: the
 // index arithmetic (three integer divisions by run-time extents) is paid once per cell instead of once per value --
 // 134 VALU instructions per 8 bytes made the per-item form compute-bound on the small boxes of a refined mesh
-// (refined mesh of 232 16^3 blocks: 0.893 -> 0.885 ms per cycle).  APK_COPY_PER_ITEM=1: the per-item form (A/B).
+// (refined mesh of 232 16^3 blocks: 0.893 -> 0.885 ms per cycle).  (copy_regions_kernel above is the per-item form; nothing
+// launches it any more.)
 __global__ void __launch_bounds__(256)
 copy_regions_cells_kernel(const apk_copy_region *regions, const apk_copy_chunk *chunks) {
   const apk_copy_chunk ch = chunks[blockIdx.x];

@@ -13,7 +13,6 @@
 // conserved variables and writes one (IEN): 48 B resp. 72 B per cell; the rest is arithmetic: each DeDt is one log10 and
 // one pow(10, x) in fp64 plus ~15 other fp64 operations, and an RK45 step makes six of them.  The table (log_lambdas, a
 // few hundred doubles) is read through the cached global path: a wave's lanes read at most a few neighbouring entries.
-// (An LDS copy of the table, APK_COOL_LDS=1, is kept for A/B measurement; see DESIGN.md.)
 //
 // Build forms.  The parity build (APK_FP_STRICT) keeps the reference's expression order and libm calls: log10,
 // pow(10., x), pow(tol / err, 2 | 5).  The product build uses exp10 for pow(10., x) and multiplies for the integer powers.
@@ -70,7 +69,7 @@ APK_DEV double cool_pow10(double x) {
 #endif
 }
 
-// CoolingTableObj::DeDt (tabular_cooling.hpp:129-173); ll: log_lambdas (global or LDS)
+// CoolingTableObj::DeDt (tabular_cooling.hpp:129-173); ll: log_lambdas
 APK_DEV double dedt(const CoolDev &c, const double *ll, double e, double rho, bool &is_valid, unsigned &flags) {
   if (e < 0 || isnan(e)) {
     is_valid = false;
@@ -141,7 +140,6 @@ struct RK45 {
 };
 
 constexpr double kEpsilon = 1e-12;  // TabularCooling::KEpsilon_
-constexpr int kLdsMax = 1024;       // table rows an LDS copy holds
 
 // (b, k, j, i) of interior cell `idx` of the pack; false past the last one
 APK_DEV bool cell_of(const PackView &pv, int64_t idx, int &b, int64_t &off) {
@@ -157,26 +155,14 @@ APK_DEV bool cell_of(const PackView &pv, int64_t idx, int &b, int64_t &off) {
   return true;
 }
 
-template <bool LDS>
-APK_DEV const double *table_ptr(const CoolDev &c, double *lds) {
-  if constexpr (LDS) {
-    for (int t = threadIdx.x; t < c.n; t += blockDim.x) lds[t] = c.log_lambdas[t];
-    __syncthreads();
-    return lds;
-  } else {
-    return c.log_lambdas;
-  }
-}
-
 APK_DEV void latch(unsigned *d_flags, unsigned flags) {
   if (flags) atomicOr(d_flags, flags);
 }
 
 // SubcyclingFixedIntSrcTerm<RKStepper> (tabular_cooling.cpp:290-487), one interior cell per lane
-template <typename RK, bool MHD, bool LDS>
+template <typename RK, bool MHD>
 __global__ void __launch_bounds__(256) cool_subcycle_kernel(PackView pv, CoolDev c, double dt, unsigned *d_flags) {
-  __shared__ double lds[LDS ? kLdsMax : 1];
-  const double *ll = table_ptr<LDS>(c, lds);
+  const double *ll = c.log_lambdas;
   int b;
   int64_t off;
   if (!cell_of(pv, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b, off)) return;
@@ -349,11 +335,9 @@ APK_DEV double wave_min(double v) {
 
 // EstimateTimeStep (tabular_cooling.cpp:606-665): min over interior cells of the cooling time into min_bits (positive
 // doubles and +inf order like their bit patterns)
-template <bool LDS>
 __global__ void __launch_bounds__(256) cool_dt_kernel(PackView pv, CoolDev c, double gm1, unsigned long long *min_bits,
                                                       unsigned *d_flags) {
-  __shared__ double lds[LDS ? kLdsMax : 1];
-  const double *ll = table_ptr<LDS>(c, lds);
+  const double *ll = c.log_lambdas;
   int b;
   int64_t off;
   unsigned flags = 0;
@@ -393,11 +377,6 @@ __global__ void __launch_bounds__(256) cool_dedt_kernel(CoolDev c, const double 
 }
 
 int64_t interior_cells(const PackView &pv) { return (int64_t)pv.nx1 * pv.nx2 * pv.nx3 * pv.nblocks; }
-
-bool use_lds(const CoolDev &c) {
-  static const int mode = std::getenv("APK_COOL_LDS") ? std::atoi(std::getenv("APK_COOL_LDS")) : 0;  // A/B switch
-  return mode != 0 && c.n <= kLdsMax;
-}
 
 }  // namespace
 }  // namespace apk
@@ -505,25 +484,14 @@ int apk_tabular_cooling_src(apk_ctx *ctx, const apk_pack *md, const apk_cooling_
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool mhd = fluid == APK_FLUID_GLMMHD;
   const CoolDev &c = table->dev;
-  const bool lds = use_lds(c);
   switch (table->p.integrator) {
     case APK_COOL_RK12:
-      if (mhd) {
-        if (lds) hipLaunchKernelGGL((cool_subcycle_kernel<RK12, true, true>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-        else hipLaunchKernelGGL((cool_subcycle_kernel<RK12, true, false>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-      } else {
-        if (lds) hipLaunchKernelGGL((cool_subcycle_kernel<RK12, false, true>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-        else hipLaunchKernelGGL((cool_subcycle_kernel<RK12, false, false>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-      }
+      if (mhd) hipLaunchKernelGGL((cool_subcycle_kernel<RK12, true>), grid, block, 0, s, v, c, dt, ctx->d_flags);
+      else hipLaunchKernelGGL((cool_subcycle_kernel<RK12, false>), grid, block, 0, s, v, c, dt, ctx->d_flags);
       break;
     case APK_COOL_RK45:
-      if (mhd) {
-        if (lds) hipLaunchKernelGGL((cool_subcycle_kernel<RK45, true, true>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-        else hipLaunchKernelGGL((cool_subcycle_kernel<RK45, true, false>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-      } else {
-        if (lds) hipLaunchKernelGGL((cool_subcycle_kernel<RK45, false, true>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-        else hipLaunchKernelGGL((cool_subcycle_kernel<RK45, false, false>), grid, block, 0, s, v, c, dt, ctx->d_flags);
-      }
+      if (mhd) hipLaunchKernelGGL((cool_subcycle_kernel<RK45, true>), grid, block, 0, s, v, c, dt, ctx->d_flags);
+      else hipLaunchKernelGGL((cool_subcycle_kernel<RK45, false>), grid, block, 0, s, v, c, dt, ctx->d_flags);
       break;
     case APK_COOL_TOWNSEND:
       if (mhd) hipLaunchKernelGGL(cool_townsend_kernel<true>, grid, block, 0, s, v, c, dt);
@@ -560,10 +528,7 @@ int apk_estimate_cooling_timestep(apk_ctx *ctx, const apk_pack *md, const apk_co
   if (ncell > 0) {
     const dim3 grid((unsigned)((ncell + 255) / 256)), block(256);
     const double gm1 = table->p.gamma - 1.0;
-    if (use_lds(table->dev))
-      hipLaunchKernelGGL(cool_dt_kernel<true>, grid, block, 0, s, v, table->dev, gm1, ctx->d_u64, ctx->d_flags);
-    else
-      hipLaunchKernelGGL(cool_dt_kernel<false>, grid, block, 0, s, v, table->dev, gm1, ctx->d_u64, ctx->d_flags);
+    hipLaunchKernelGGL(cool_dt_kernel, grid, block, 0, s, v, table->dev, gm1, ctx->d_u64, ctx->d_flags);
     if (hipGetLastError() != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "cooling time-step launch failed");
   }
   APK_HIP_TRY(ctx, hipMemcpyAsync(h + 1, ctx->d_u64, sizeof(bits), hipMemcpyDeviceToHost, s));

@@ -424,6 +424,7 @@ class Simulation(_FmftHost, _MeshView):
 
     def set_thin_exchange(self, on):
         self._check(self.lib.apk_sim_set_thin_exchange(self.h, int(on)))
+        return self
 
     def x1_direct_exchanges(self):
         """exchanges so far whose x1 strips bypassed the pack / unpack kernels (apk_sim_set_x1_direct)"""

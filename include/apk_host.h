@@ -114,24 +114,23 @@ long long apk_sim_overlapped_exchanges(const apk_sim *sim);
  * all single-march donor-cell or two-kernel stages (no passive scalars, floors, extended Dedner source
  * or flux correction) the stage kernels read the interiors of same-rank neighbour
  * blocks directly and the same-rank ghost-zone copies are skipped; ghost zones are brought up to date
- * on demand (every accessor does).  Results are identical.  APK_DIRECT_NEIGHBORS=0 in the environment
- * switches it off.  Returns the number of stage boundaries so far whose same-rank copies were skipped. */
+ * on demand (every accessor does).  Results are identical.  apk_sim_set_direct_neighbors(sim, 0) switches it
+ * off.  Returns the number of stage boundaries so far whose same-rank copies were skipped. */
 long long apk_sim_skipped_local_exchanges(const apk_sim *sim);
 int apk_sim_set_direct_neighbors(apk_sim *sim, int on); /* 1 (default) / 0 = always copy */
 /* Refined meshes, VL2 with a high-order corrector in the two-kernel form, default equation-of-state limits, no passive
  * scalars: the corrector derives its input from the half-step conserved state (apk_stage_args.prim_from_cons = 2, its
  * result over the register u1) and the flux correction's boundary planes likewise
  * (apk_calculate_fluxes_boundary_list_from_cons), so that no ConsToPrim pass runs between the two stages.  Results are
- * identical.  apk_sim_set_prim_free(sim, 0) / APK_AMR_PRIM_FREE=0 in the environment switch it off.  Returns the number
- * of passes done without. */
+ * identical.  apk_sim_set_prim_free(sim, 0) switches it off.  Returns the number of passes done without. */
 long long apk_sim_amr_c2p_passes_skipped(const apk_sim *sim);
 /* Full-step primitives kept out of memory (on by default where it applies: uniform 3-D meshes, VL2 -- a donor-cell
  * predictor followed by a two-kernel stage --, default equation-of-state limits, no passive scalars, no extended Dedner
  * source, no forcing): the last stage of a cycle computes the primitives of the new state for the time-step estimate
  * only (apk_stage_args.fill_derived = 3) and the predictor of the next cycle derives its input from the conserved state
  * (prim_from_cons) -- the reference stores them in FillDerived (hydro_driver.cpp:571-577) and reads them back in
- * CalculateFluxes.  Every accessor materialises them on demand; results are identical.  APK_PRIM_FREE=0 in the
- * environment switches it off.  apk_sim_prim_is_stale: 1 while the primitives of the current state are not in memory.
+ * CalculateFluxes.  Every accessor materialises them on demand; results are identical.  apk_sim_set_prim_free(sim, 0)
+ * switches it off.  apk_sim_prim_is_stale: 1 while the primitives of the current state are not in memory.
  * The same switch governs the stage loop of refined meshes (apk_sim_amr_c2p_passes_skipped above). */
 int apk_sim_set_prim_free(apk_sim *sim, int on);
 /* One-layer exchanges (on by default where they apply: N > 1 ranks, uniform periodic 3-D meshes, VL2, no passive
@@ -141,7 +140,7 @@ int apk_sim_set_prim_free(apk_sim *sim, int on);
  * the same buffers; the transports find the current sizes in apk_sim_peer at every exchange
  * (apk_sim_message_generation tells when they changed).  Accessors that read ghost zones complete them with a full
  * exchange first: a COLLECTIVE then, to be called on every rank, like the accessors of a refined mesh.  Results are
- * identical.  APK_THIN_EXCHANGE=0 in the environment switches it off.  Returns (apk_sim_thin_exchanges) the number
+ * identical.  apk_sim_set_thin_exchange(sim, 0) switches it off.  Returns (apk_sim_thin_exchanges) the number
  * of one-layer exchanges so far. */
 int apk_sim_set_thin_exchange(apk_sim *sim, int on);
 long long apk_sim_thin_exchanges(const apk_sim *sim);
@@ -152,7 +151,7 @@ long long apk_sim_thin_exchanges(const apk_sim *sim);
  * columns straight from the receive buffers (apk_stage_args.x1_halo in apk_amd.h); the pack and unpack plans leave the
  * x1 faces out.  The messages are byte for byte what the pack kernel would have written, so a rank may use the path or
  * not independently of its peers; results are identical.  Accessors that read ghost zones repeat such an exchange in full
- * first (a COLLECTIVE, as after a one-layer exchange).  APK_X1_DIRECT=0 in the environment switches it off.
+ * first (a COLLECTIVE, as after a one-layer exchange).  apk_sim_set_x1_direct(sim, 0) switches it off.
  * apk_sim_x1_direct_exchanges: the number of exchanges so far whose x1 strips went that way. */
 int apk_sim_set_x1_direct(apk_sim *sim, int on);
 long long apk_sim_x1_direct_exchanges(const apk_sim *sim);

@@ -199,8 +199,8 @@ def _forest_octant_symmetric_within(s, root_blocks, cycles=2):
     (d1 + d3) + d2 in the last bit), and in the product build a*b - c*d is fma(a, b, -(c*d)), whose mirror image rounds
     differently.  A refinement criterion that sits at its threshold can therefore flag a block one cycle before its
     mirror image: the forest is symmetric except for single cycles in which one of the two has not followed yet
-    (tools/dbg_cfg5.py lists them: 3 of 420 cycles on config 5, as in round 3).  So: symmetric now, or after at most
-    `cycles` more cycles."""
+    (tools/dbg_cfg5.py, in the history at 8a567ba, lists them: 3 of 420 cycles on config 5, as in round 3).  So:
+    symmetric now, or after at most `cycles` more cycles."""
     for extra in range(cycles + 1):
         if _forest_is_octant_symmetric(s, root_blocks):
             return True

@@ -145,12 +145,16 @@ def test_meshblock_decomposition_and_fused_path_do_not_change_a_bit(oracle):
     b = _sim("linear_wave3d", base + ["parthenon/meshblock/nx1=32", "parthenon/meshblock/nx2=16",
                                       "parthenon/meshblock/nx3=16"], fused=True).initialize()
     c = _sim("linear_wave3d", base, fused=False).initialize()
+    # a finite velocity ceiling that never binds: the cycle keeps its primitives and the stages take their non-lean forms
+    d = _sim("linear_wave3d", base + ["hydro/vceil=1e301"], fused=True).initialize()
     assert b.info.nblocks_local == 8 and a.info.fused == 1 and c.info.fused == 0
-    for sim in (a, b, c):
+    for sim in (a, b, c, d):
         sim.run()
+    assert a.prim_is_stale and not d.prim_is_stale
     ua = a.gather()
     assert np.array_equal(ua, b.gather())
     assert np.array_equal(ua, c.gather())
+    assert np.array_equal(ua, d.gather())
 
 
 @pytest.mark.parametrize("integrator,recon,riemann,ng", [("rk3", "ppm", "hlle", 3), ("rk3", "wenoz", "hllc", 3),
@@ -452,8 +456,7 @@ def test_one_layer_exchange_before_the_predictor_and_its_completion(strict, over
     for thin in (True, False):
         s = _sim("synthetic_mhd", ov, strict=strict)
         s.set_overlap(overlap)
-        s.set_thin_exchange(thin)
-        s.set_prim_free(prim_free)
+        s.set_thin_exchange(thin).set_prim_free(prim_free)
         sims.append(s.initialize())
     a, b = sims
     for rounds in range(2):

@@ -3,7 +3,7 @@
 # Prints one JSON line per integrator: ms per call (median of >= 3 timed regions of >= 50 ms, the state restored
 # before every call, outside the timed span), the memory floor, and the mean / per-wave maximum substeps of a sample of
 # waves (restated on the host).
-#   python tools/cooling_prof.py                 # APK_COOL_LDS=1: the table in LDS instead of cached global loads
+#   python tools/cooling_prof.py
 #   rocprofv3 --kernel-trace --stats --output-format csv -d prof -o cool -- python tools/cooling_prof.py --quick
 import json
 import math
@@ -83,14 +83,13 @@ def substeps(integ, T, nwaves=48):
     return float(np.mean(mean)), float(np.mean(wmax))
 
 
-lds = os.environ.get("APK_COOL_LDS", "0") != "0"
 for integ in ("rk12", "rk45", "townsend"):
     p = L.make_cooling_params(integ, d_e_tol=1e-8, lambda_units=U.lambda_units(), gamma=GAMMA,
                               mbar_over_kb=MBAR_OVER_KB, He_mass_fraction=HE, mh=U.mh)
     tab = hydro.TabularCooling(ctx, rows[0], rows[1], p)
     ms, regions = timed(tab, region_ms=10.0 if QUICK else 50.0)
     cells = NB * N ** 3
-    out = dict(integrator=integ, cells=cells, dt=dt, ms_per_call=ms, regions_ms=regions, lds=lds,
+    out = dict(integrator=integ, cells=cells, dt=dt, ms_per_call=ms, regions_ms=regions,
                floor_bytes=48 * cells, floor_GBps=48 * cells / ms / 1e6)
     if integ != "townsend" and not QUICK:
         T = R.Table(rows[0], rows[1], U.lambda_units(), GAMMA, MBAR_OVER_KB, HE, U.mh, d_e_tol=1e-8, max_iter=100)

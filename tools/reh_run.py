@@ -1,6 +1,6 @@
 """Development aid (GPU box, repo root): the headline brick for a few cycles -- plain (REHEARSE=0) or as the one-GPU
 rehearsal of an 8-GPU rank -- printing ms per cycle; REPS timed regions of CYCLES cycles.  OVERLAP=0: exchanges
-synchronous; APK_X1_DIRECT=0 / other library switches through the environment."""
+synchronous; X1_DIRECT=0: x1 strips through the pack / unpack kernels (set_x1_direct)."""
 import os, sys, time, torch
 sys.path.insert(0, ".")
 from athenapk_amd import decks, driver
@@ -12,6 +12,7 @@ ov += ["parthenon/time/integrator=%s" % integrator, "hydro/reconstruction=%s" % 
 if os.environ.get("REHEARSE", "1") == "1": ov += ["apk_amd/rehearse_remote_faces=true"]
 s = driver.Simulation(decks.load(deck), ov, strict=False)
 s.set_overlap(os.environ.get("OVERLAP", "1") == "1")
+s.set_x1_direct(os.environ.get("X1_DIRECT", "1") == "1")
 s.initialize()
 for _ in range(3): s.step()
 out = []
@@ -21,5 +22,5 @@ for rep in range(int(os.environ.get("REPS", "3"))):
     for _ in range(cycles): s.step()
     torch.cuda.synchronize(); out.append((time.perf_counter() - t) / cycles * 1e3)
 print("%s rehearse=%s overlap=%s x1=%s: ms/cycle %s  x1_direct_exchanges %d thin %d" % (
-    wl, os.environ.get("REHEARSE", "1"), os.environ.get("OVERLAP", "1"), os.environ.get("APK_X1_DIRECT", "1"),
+    wl, os.environ.get("REHEARSE", "1"), os.environ.get("OVERLAP", "1"), os.environ.get("X1_DIRECT", "1"),
     " ".join("%.3f" % v for v in out), s.x1_direct_exchanges(), s.thin_exchanges()), flush=True)
