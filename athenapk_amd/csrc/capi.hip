@@ -636,6 +636,72 @@ int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_
   return APK_OK;
 }
 
+// ---- RKL2 super-time-stepping (hydro_driver.cpp:93-344) -----------------------------------------------------------
+// (apk_rkl2_num_stages / apk_rkl2_coefficients: host/sts.cpp, compiled without the kernels' fast-math flags)
+int apk_flux_divergence(apk_ctx *ctx, const apk_pack *md, const apk_pack *out, apk_stream_t stream) {
+  if (!ctx || !md || !out || !same_shape(md, out)) return set_err(ctx, APK_ERR_INVALID, "apk_flux_divergence: bad argument");
+  for (int d = 0; d < md->view.ndim; ++d)
+    if (!md->have_flux[d]) return set_err(ctx, APK_ERR_INVALID, "apk_flux_divergence: pack has no flux arrays");
+  int rc = launch_flux_divergence(md->view, out->d_blocks, as_stream(stream));
+  if (rc != APK_OK) return set_err(ctx, rc, "flux divergence kernel launch failed", hipGetLastError());
+  return APK_OK;
+}
+
+namespace {
+// the four registers of a sub-stage: same shape, and the ones written distinct from each other and from Y0
+int check_rkl2_regs(apk_ctx *ctx, const char *who, const apk_pack *y0, const apk_pack *yjm1, const apk_pack *yjm2, const apk_pack *my0) {
+  if (!ctx || !y0 || !yjm1 || !yjm2 || !my0 || !same_shape(yjm1, y0) || !same_shape(yjm1, yjm2) || !same_shape(yjm1, my0))
+    return set_err(ctx, APK_ERR_INVALID, who);
+  for (size_t b = 0; b < yjm1->h_blocks.size(); ++b) {
+    const double *p[4] = {y0->h_blocks[b].cons, yjm1->h_blocks[b].cons, yjm2->h_blocks[b].cons, my0->h_blocks[b].cons};
+    for (int i = 0; i < 4; ++i)
+      for (int q = i + 1; q < 4; ++q)
+        if (!p[i] || p[i] == p[q]) return set_err(ctx, APK_ERR_INVALID, who);
+  }
+  return APK_OK;
+}
+}  // namespace
+
+int apk_rkl2_step_first(apk_ctx *ctx, const apk_pack *y0, const apk_pack *yjm1, const apk_pack *yjm2, const apk_pack *my0,
+                        int s_rkl, double tau, apk_stream_t stream) {
+  int rc = check_rkl2_regs(ctx, "apk_rkl2_step_first: bad argument", y0, yjm1, yjm2, my0);
+  if (rc != APK_OK) return rc;
+  double mu, nu, mu_tilde_1, gamma_tilde;
+  if (apk_rkl2_coefficients(s_rkl, 1, &mu, &nu, &mu_tilde_1, &gamma_tilde) != APK_OK)
+    return set_err(ctx, APK_ERR_INVALID, "apk_rkl2_step_first: s_rkl must be >= 2");
+  rc = launch_rkl2_step_first(yjm1->view, y0->d_blocks, yjm2->d_blocks, my0->d_blocks, mu_tilde_1, tau, as_stream(stream));
+  if (rc != APK_OK) return set_err(ctx, rc, "RKL2 first step kernel launch failed", hipGetLastError());
+  return APK_OK;
+}
+
+int apk_rkl2_step_other(apk_ctx *ctx, const apk_pack *y0, const apk_pack *yjm1, const apk_pack *yjm2, const apk_pack *my0,
+                        double mu_j, double nu_j, double mu_tilde_j, double gamma_tilde_j, double tau, apk_stream_t stream) {
+  int rc = check_rkl2_regs(ctx, "apk_rkl2_step_other: bad argument", y0, yjm1, yjm2, my0);
+  if (rc != APK_OK) return rc;
+  for (int d = 0; d < yjm1->view.ndim; ++d)
+    if (!yjm1->have_flux[d]) return set_err(ctx, APK_ERR_INVALID, "apk_rkl2_step_other: Yjm1 has no flux arrays");
+  rc = launch_rkl2_step_other(yjm1->view, y0->d_blocks, yjm2->d_blocks, my0->d_blocks, mu_j, nu_j, mu_tilde_j, gamma_tilde_j, tau,
+                              as_stream(stream));
+  if (rc != APK_OK) return set_err(ctx, rc, "RKL2 step kernel launch failed", hipGetLastError());
+  return APK_OK;
+}
+
+int apk_rkl2_substage_fused(apk_ctx *ctx, const apk_pack *md, const apk_rkl2_regs *regs, const apk_diff_cfg *cfg,
+                            const apk_rkl2_coeffs *coeffs, double tau, int first, apk_stream_t stream) {
+  if (!regs || !coeffs) return set_err(ctx, APK_ERR_INVALID, "apk_rkl2_substage_fused: bad argument");
+  int rc = check_rkl2_regs(ctx, "apk_rkl2_substage_fused: bad argument", regs->y0, md, regs->yjm2, regs->my0);
+  if (rc != APK_OK) return rc;
+  if ((rc = check_diff_cfg(ctx, md, cfg)) != APK_OK) return rc;
+  for (const apk_block_desc &b : md->h_blocks)
+    if (!b.prim) return set_err(ctx, APK_ERR_INVALID, "apk_rkl2_substage_fused: the pack has no primitives");
+  rc = launch_rkl2_substage_fused(md->view, regs->y0->d_blocks, regs->yjm2->d_blocks, regs->my0->d_blocks, cfg->conduction,
+                                  cfg->viscosity != APK_VISC_NONE, cfg->resistivity != APK_RES_NONE, cfg->thermal_diff_coeff,
+                                  cfg->conduction_sat_prefac, cfg->mom_diff_coeff, cfg->ohm_diff_coeff, coeffs->mu, coeffs->nu,
+                                  coeffs->mu_tilde, coeffs->gamma_tilde, tau, first != 0, as_stream(stream));
+  if (rc != APK_OK) return set_err(ctx, rc, "fused RKL2 sub-stage kernel launch failed", hipGetLastError());
+  return APK_OK;
+}
+
 int apk_first_order_flux_correct(apk_ctx *ctx, const apk_pack *u0, const apk_pack *u1, int fluid,
                                  const apk_eos *eos, double c_h, double gam0, double gam1,
                                  double beta_dt, long long *num_corrected, apk_stream_t stream) {

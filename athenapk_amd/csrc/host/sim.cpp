@@ -190,13 +190,20 @@ void diffusion_initialize(apk_sim *s) {
   }
   const std::string integrator = pin.GetOrAddString("diffusion", "integrator", "none");
   if (integrator == "unsplit") pkg.diffint = APK_DIFFINT_UNSPLIT;
-  else if (integrator == "rkl2")
-    throw std::runtime_error("diffusion/integrator = rkl2 (super-time-stepping) is not supported; use unsplit.");
+  else if (integrator == "rkl2") {
+    pkg.diffint = APK_DIFFINT_RKL2;
+    pkg.rkl2_max_dt_ratio = pin.GetOrAddReal("diffusion", "rkl2_max_dt_ratio", -1.0);
+    // (a deviation: the reference runs rkl2 without a ratio too, one uncapped step under Parthenon's dt_ceil, which this
+    // driver does not have -- the mode its own documentation warns about)
+    if (!(pkg.rkl2_max_dt_ratio > 0.0))
+      throw std::runtime_error("diffusion/integrator = rkl2 (super-time-stepping) is not supported without a positive "
+                               "diffusion/rkl2_max_dt_ratio; set it (the reference's tests use 200) or use unsplit.");
+  }
   else if (integrator == "none") pkg.diffint = APK_DIFFINT_NONE;
   else throw std::runtime_error("AthenaPK unknown integration method for diffusion processes. Options are: none, unsplit, rkl2");
   // as in Athena++ a cfl safety factor is applied to the theoretical limit, by default the hyperbolic cfl
   if (pkg.diffint != APK_DIFFINT_NONE) pkg.cfl_diff = pin.GetOrAddReal("diffusion", "cfl", pkg.cfl);
-  if (!pkg.diffusion_active()) return;
+  if (!pkg.diffusion_configured()) return;
   if (pkg.fluid == APK_FLUID_EULER && (c.resistivity != APK_RES_NONE || c.conduction == APK_COND_ANISOTROPIC))
     throw std::runtime_error("Ohmic resistivity and anisotropic conduction need hydro/fluid = glmmhd.");
   if (pkg.riemann == APK_RS_LLF)
@@ -204,6 +211,11 @@ void diffusion_initialize(apk_sim *s) {
                              "function (CalculateFluxesTight) adds no diffusive fluxes.");
   if (pin.GetOrAddString("parthenon/mesh", "refinement", "none") != "none")
     throw std::runtime_error("Diffusion on refined meshes is not supported: parthenon/mesh/refinement must be none.");
+  // (not a reference parameter: which form an RKL2 sub-stage takes -- the fused kernel, or the reference's sequence of
+  // passes over the flux arrays, the default until the fused kernel has been timed below them)
+  const std::string substage = pin.GetOrAddString("apk_amd", "sts_substage", "arrays");
+  if (substage != "fused" && substage != "arrays") throw std::runtime_error("apk_amd/sts_substage must be fused or arrays");
+  s->sts_fused = substage == "fused";
 }
 
 void mesh_initialize(apk_sim *s) {
@@ -432,8 +444,8 @@ int estimate_timestep_read(apk_sim *s, DtEstimate *e) {
   }
   if (!have_flags) SIM_TRY(s, apk_poll_device_flags(s->ctx, &flags, s->stream));
   e->dt_hyp_local = dt;
-  // the diffusive limit (hydro.cpp:935-963; unsplit: min_dt = min(dt_hyp, dt_diff))
-  if (s->pkg.diffusion_active()) {
+  // the diffusive limit (hydro.cpp:935-963; unsplit: min_dt = min(dt_hyp, dt_diff); rkl2: see estimate_timestep_commit)
+  if (s->pkg.diffusion_configured()) {
     if (s->prim_stale) SIM_TRY(s, sync_ghosts(s));  // (the estimate reads stored primitives)
     SIM_TRY(s, apk_estimate_diffusion_timestep(s->ctx, s->mu0(), &s->pkg.diff, s->pkg.cfl_diff, &e->dt_diff_local, s->stream));
   }
@@ -450,7 +462,9 @@ int estimate_timestep_read(apk_sim *s, DtEstimate *e) {
 }
 
 int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
-  double dt = std::min(std::min(e.dt_hyp_local, e.dt_diff_local), e.dt_cool_local);
+  const bool sts = s->pkg.diffusion_sts();
+  // (rkl2: dt_diff does not join min_dt directly, hydro.cpp:950-956)
+  double dt = std::min(std::min(e.dt_hyp_local, sts ? kHuge : e.dt_diff_local), e.dt_cool_local);
   if (s->pkg.max_dt > 0.0 && s->pkg.max_dt < dt) dt = s->pkg.max_dt;
   // one reduction for both minima: the time step, and the hyperbolic estimate that the next cycle's
   // c_h needs (hydro.cpp:102-143 reduces it in PreStepMeshUserWorkInLoop; same value, one message less).
@@ -460,10 +474,11 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
   // must integrate with the same table.
   const bool cool = s->pkg.cooling;
   const double h = s->pkg.cool_table_hash;
-  double mins[7] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0, (e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0,
-                    (e.flags & (APK_FLAG_COOL_MAX_ITER | APK_FLAG_COOL_TABLE)) ? -1.0 : 0.0, h, -h};
+  // With rkl2 one more, last: the diffusive limit itself, which sizes the next cycle's super-time-steps.
+  double mins[8] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0, (e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0,
+                    (e.flags & (APK_FLAG_COOL_MAX_ITER | APK_FLAG_COOL_TABLE)) ? -1.0 : 0.0, h, -h, e.dt_diff_local};
   if (s->have_comm && s->nranks > 1) {
-    if (s->comm.allreduce_min(s->comm.user, mins, cool ? 7 : 4) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
+    if (s->comm.allreduce_min(s->comm.user, mins, sts ? 8 : (cool ? 7 : 4)) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
   }
   if (cool && mins[5] != -mins[6]) return fail(s, APK_ERR_INVALID, "cooling: the ranks read different cooling tables");
   if (cool && mins[4] < 0.0) {
@@ -478,6 +493,15 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
     return fail(s, APK_ERR_INVALID, "Got negative pressure. Consider enabling first-order flux correction or setting a reasonble pressure or temperature floor.");
   if (s->pkg.calc_dt_hyp && s->pkg.fluid == APK_FLUID_GLMMHD && mins[1] < s->pkg.dt_hyp) s->pkg.dt_hyp = mins[1];  // hydro.cpp:903-908
   s->dt_hyp_is_global = true;
+  if (sts) {
+    // hydro.cpp:950-962.  The reference evaluates this condition per partition, on that partition's dt_hyp and dt_diff;
+    // here it is evaluated once on the globally reduced pair, so that the step does not depend on the decomposition
+    // (identical for one partition).  Without a hyperbolic estimate (riemann = none) dt_hyp is huge and the cap alone
+    // sets the step.
+    s->pkg.dt_diff = mins[7];
+    const double ratio = s->pkg.rkl2_max_dt_ratio;
+    if (mins[1] / mins[7] > ratio) mins[0] = std::min(mins[0], ratio * mins[7]);
+  }
   *dt_out = mins[0];
   return APK_OK;
 }
@@ -1412,7 +1436,7 @@ int do_stage(apk_sim *s, int stage) {
     SIM_TRY(s, apk_calculate_fluxes_tight(s->ctx, s->mu0(), cfg, &pkg.eos, pkg.c_h, s->stream));
     // the diffusive fluxes are added at the end of CalculateFluxes (hydro.cpp:1202-1205): FOFC's LLF fluxes, where it
     // corrects a cell, replace whole face fluxes after that
-    if (pkg.diffusion_active()) SIM_TRY(s, apk_calc_diff_fluxes(s->ctx, s->mu0(), &pkg.diff, s->stream));
+    if (pkg.diffusion_in_fluxes()) SIM_TRY(s, apk_calc_diff_fluxes(s->ctx, s->mu0(), &pkg.diff, s->stream));
     if (pkg.first_order_flux_correct) {
       long long nfix = 0;
       SIM_TRY(s, apk_first_order_flux_correct(s->ctx, s->mu0(), s->mu1(), pkg.fluid, &pkg.eos, pkg.c_h, g0, g1,
@@ -1524,7 +1548,8 @@ int do_stage(apk_sim *s, int stage) {
       // (not after an exchange that filled nothing: direct addressing on a mesh whose faces the table covers)
       const bool filled_none = direct && table_covers_all_faces(s);
       if (!c2p_in_copy && ghost_prims && !filled_none) SIM_TRY(s, apk_cons_to_prim_ghosts(s->ctx, s->mu0(), pkg.fluid, &pkg.eos, s->stream));
-    } else if (stage == s->nstages && pkg.calc_dt_hyp) {
+    } else if (stage == s->nstages && pkg.calc_dt_hyp && !pkg.diffusion_sts()) {
+      // (not with rkl2: the second super-time-step changes the state before the estimate)
       // the last FillDerived of the cycle and the time-step estimate that follows it (hydro_driver.cpp:571-603) in
       // one pass: the interior cells' primitives are in registers anyway (refined meshes, flux-array stages)
       SIM_TRY(s, apk_cons_to_prim_dt(s->ctx, s->mu0(), pkg.fluid, &pkg.eos, -1, s->stream));
@@ -1734,6 +1759,7 @@ void apk_sim_destroy(apk_sim *s) {
     dev_free(s, reinterpret_cast<double *>(s->d_late_regions));
     dev_free(s, reinterpret_cast<double *>(s->d_face_nbr));
     for (auto &t : s->d_x1_tab) dev_free(s, static_cast<double *>(t));
+    sts_free(s);
     dev_free(s, s->d_acc);
     dev_free(s, s->d_phases);
     dev_free(s, s->d_cons2[0]);
@@ -1872,7 +1898,12 @@ int apk_sim_step(apk_sim *s) {
   s->err.clear();
   if (s->time < s->tlim && (s->tlim - s->time) < s->dt) s->dt = s->tlim - s->time;
   SIM_TRY(s, pre_step(s));
+  // diffusion/integrator = rkl2: a parabolic half step before and after the hyperbolic stages (hydro_driver.cpp:455-458,
+  // 581-583), both sized with the diffusive limit estimated at the end of the previous cycle
+  const bool sts = s->pkg.diffusion_sts();
+  if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
   for (int stage = 1; stage <= s->nstages; ++stage) SIM_TRY(s, do_stage(s, stage));
+  if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
   s->time += s->dt;
   s->ncycle += 1;
   s->zone_cycles += (long long)s->mesh.mb[0] * s->mesh.mb[1] * s->mesh.mb[2] * (long long)s->mesh.nblocks_total;

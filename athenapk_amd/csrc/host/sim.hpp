@@ -53,12 +53,22 @@ struct HydroPackage {
   apk_diff_cfg diff{};
   int diffint = APK_DIFFINT_NONE;
   double cfl_diff = 0.0;
-  // configured processes act only with the unsplit integrator (with integrator = none they do nothing, as in the
-  // reference)
-  bool diffusion_active() const {
-    return diffint == APK_DIFFINT_UNSPLIT &&
-           (diff.conduction != APK_COND_NONE || diff.viscosity != APK_VISC_NONE || diff.resistivity != APK_RES_NONE);
+  // diffusion/rkl2_max_dt_ratio (hydro.cpp:686-689); rkl2 is accepted only with a positive ratio
+  double rkl2_max_dt_ratio = -1.0;
+  // the diffusive limit, minimum over all ranks, as estimated last (the "dt_diff" param, hydro.cpp:700-701, 961-962):
+  // what both RKL2 half steps of the next cycle size their stage count with
+  double dt_diff = std::numeric_limits<double>::max();
+  bool diffusion_processes() const {
+    return diff.conduction != APK_COND_NONE || diff.viscosity != APK_VISC_NONE || diff.resistivity != APK_RES_NONE;
   }
+  // a process and an integrator are configured (with integrator = none the processes do nothing, as in the reference):
+  // the diffusive time-step estimate, and stages on the flux-array path
+  bool diffusion_configured() const { return diffint != APK_DIFFINT_NONE && diffusion_processes(); }
+  // the diffusive fluxes are added at the end of CalculateFluxes (hydro.cpp:1202-1205): unsplit only -- with rkl2 the
+  // hyperbolic stages carry none
+  bool diffusion_in_fluxes() const { return diffint == APK_DIFFINT_UNSPLIT && diffusion_processes(); }
+  // operator-split super-time-stepping around the hyperbolic stages (hydro_driver.cpp:455-458, 581-583)
+  bool diffusion_sts() const { return diffint == APK_DIFFINT_RKL2 && diffusion_processes(); }
   UnitsState units;
   // <cooling> enable_cooling = tabular (hydro.cpp:723-738): the parameters, the table as parsed and its fingerprint
   bool cooling = false;
@@ -66,7 +76,7 @@ struct HydroPackage {
   CoolingTableHost cool_table;
   double cool_table_hash = 0.0;
   // the unsplit sources that run through the flux-array stage path (no fused stage forms with them)
-  bool flux_path_sources() const { return diffusion_active() || cooling; }
+  bool flux_path_sources() const { return diffusion_configured() || cooling; }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -333,6 +343,14 @@ struct apk_sim {
     apk_copy_plan *fine_bc[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     apk_copy_plan *flux_copy[3] = {nullptr, nullptr, nullptr};
   } amr_dev;
+  // RKL2 super-time-stepping (host/sts.cpp): the registers MY0 and Yjm2 (conserved-size buffers, allocated when rkl2 is
+  // on) and the packs presenting them; Y0 is the u1 buffer.  sts_fused: apk_amd/sts_substage = fused | arrays (the default
+  // until the fused kernel has been timed below the parent's kernels).
+  double *d_my0 = nullptr, *d_yjm2 = nullptr;
+  apk_pack *my0_pack = nullptr, *yjm2_pack = nullptr;
+  bool sts_fused = false;
+  int sts_last_s = 0;           // sub-stages of the last half step taken
+  double sts_last_ratio = 0.0;  // its 2 tau / dt_diff
   long long overlapped = 0;
   int perf_cycles = 0;        // cycles inside loop_seconds (after parthenon/time/perf_cycle_offset)
   double loop_seconds = 0.0;  // wall time of the last apk_sim_execute main loop (device synchronised)

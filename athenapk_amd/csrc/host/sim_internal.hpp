@@ -61,7 +61,7 @@ int build_prim_plans(apk_sim *s);
 void set_global_dt(apk_sim *s, double dt_est);
 struct DtEstimate {  // what one rank measured: see estimate_timestep_read / _commit
   double dt_hyp_local = kHuge;
-  double dt_diff_local = kHuge;  // the diffusive limit (unsplit diffusion)
+  double dt_diff_local = kHuge;  // the diffusive limit (diffusion/integrator = unsplit | rkl2)
   double dt_cool_local = kHuge;  // the cooling limit (tabular cooling)
   unsigned flags = 0;
 };
@@ -98,6 +98,8 @@ int pre_step(apk_sim *s);
 int turbulence_device_setup(apk_sim *s);
 int turbulence_driving(apk_sim *s, double dt, bool fill = false, bool no_prim = false);
 int do_stage(apk_sim *s, int stage);
+int sts_half_step(apk_sim *s, double tau);  // AddSTSTasks (host/sts.cpp)
+void sts_free(apk_sim *s);
 double xc(const apk_sim *s, const double x0[3], int d, int idx);
 void block_origin(const apk_sim *s, int lb, double x0[3]);
 void lw_eigensystem(double gm1, double v1, double v2, double v3, double h, double ev[5], double rem[5][5]);

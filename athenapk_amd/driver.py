@@ -614,6 +614,11 @@ class Simulation(_FmftHost, _MeshView):
         self._check(self.lib.apk_sim_estimate_timestep(self.h, C.byref(dt)))
         return dt.value
 
+    def sts_info(self):
+        """super-time-stepping (diffusion/integrator = rkl2): (sub-stages of the last half step, its ratio
+        2 tau / dt_diff, whether a sub-stage is the fused kernel or the passes over the flux arrays)"""
+        return _sts_info(self.lib, self.h)
+
     def reset_time_step(self):
         """after write_block + exchange_ghosts + fill_derived: the time step as initialize() derives it"""
         self._check(self.lib.apk_sim_reset_time_step(self.h))
@@ -626,6 +631,14 @@ def _diffusion_options(lib, h):
     if rc != L.APK_OK:
         raise L.ApkError(rc, "apk_sim_diffusion_options")
     return cfg, integ.value, cfl.value
+
+
+def _sts_info(lib, h):
+    n, ratio, fused = C.c_int(0), C.c_double(0.0), C.c_int(0)
+    rc = lib.apk_sim_sts_info(h, C.byref(n), C.byref(ratio), C.byref(fused))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_sts_info")
+    return n.value, ratio.value, bool(fused.value)
 
 
 def _units(lib, h):
@@ -695,6 +708,14 @@ class HostPlan(_FmftHost, _MeshView):
     def diffusion_options(self):
         """(lib.DiffCfg, diffusion/integrator as apk_diffint, diffusion/cfl) as the deck was parsed"""
         return _diffusion_options(self.lib, self.h)
+
+    def rkl2_max_dt_ratio(self):
+        """diffusion/rkl2_max_dt_ratio as parsed (-1 unless diffusion/integrator = rkl2)"""
+        return self.lib.apk_sim_rkl2_max_dt_ratio(self.h)
+
+    def sts_info(self):
+        """(sub-stages of the last RKL2 half step, its ratio 2 tau / dt_diff, whether sub-stages run fused)"""
+        return _sts_info(self.lib, self.h)
 
     def units(self):
         """lib.UnitsInfo: <units>, the gas composition and the EOS's efloor / eceil as parsed"""

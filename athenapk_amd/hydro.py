@@ -387,6 +387,50 @@ def EstimateDiffusionTimestep(md, cfg, cfl_diff):
     return dt.value
 
 
+def rkl2_num_stages(tau, dt_diff, strict=False):
+    """the number of sub-stages of an RKL2 half step of length tau (AddSTSTasks, hydro_driver.cpp:176-181); host only"""
+    s = C.c_int(0)
+    _check(L.load(strict).apk_rkl2_num_stages(float(tau), float(dt_diff), C.byref(s)))
+    return s.value
+
+
+def rkl2_coefficients(s_rkl, j, strict=False):
+    """(mu_j, nu_j, mu_tilde_j, gamma_tilde_j) of sub-stage j of s_rkl (hydro_driver.cpp:276-291); j = 1: (0, 0,
+    mu_tilde_1, 0) (hydro_driver.cpp:101-104); host only"""
+    v = [C.c_double(0.0) for _ in range(4)]
+    _check(L.load(strict).apk_rkl2_coefficients(int(s_rkl), int(j), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def FluxDivergence(md, out):
+    """parthenon::Update::FluxDivergence(md, out) -- call site hydro_driver.cpp:254: out.cons = -div F(md.flux)"""
+    ctx = md.ctx
+    _check(ctx.lib.apk_flux_divergence(ctx.h, md.h, out.h, _stream()), ctx.lib, ctx.h)
+
+
+def RKL2StepFirst(y0, yjm1, yjm2, my0, s_rkl, tau):
+    """RKL2StepFirst -- hydro_driver.cpp:93"""
+    ctx = yjm1.ctx
+    _check(ctx.lib.apk_rkl2_step_first(ctx.h, y0.h, yjm1.h, yjm2.h, my0.h, int(s_rkl), float(tau), _stream()), ctx.lib, ctx.h)
+
+
+def RKL2StepOther(y0, yjm1, yjm2, my0, mu_j, nu_j, mu_tilde_j, gamma_tilde_j, tau):
+    """RKL2StepOther -- hydro_driver.cpp:128; yjm1.flux holds the diffusive fluxes of Yjm1"""
+    ctx = yjm1.ctx
+    _check(ctx.lib.apk_rkl2_step_other(ctx.h, y0.h, yjm1.h, yjm2.h, my0.h, float(mu_j), float(nu_j), float(mu_tilde_j),
+                                       float(gamma_tilde_j), float(tau), _stream()), ctx.lib, ctx.h)
+
+
+def RKL2SubstageFused(y0, yjm1, yjm2, my0, cfg, coeffs, tau, first):
+    """one RKL2 sub-stage in one kernel (apk_rkl2_substage_fused): the diffusive fluxes of yjm1.prim, their divergence
+    and RKL2StepFirst (first) / RKL2StepOther; coeffs: (mu, nu, mu_tilde, gamma_tilde) as rkl2_coefficients returns"""
+    ctx = yjm1.ctx
+    regs = L.Rkl2Regs(y0.h, yjm2.h, my0.h)
+    k = L.Rkl2Coeffs(*[float(x) for x in coeffs])
+    _check(ctx.lib.apk_rkl2_substage_fused(ctx.h, yjm1.h, C.byref(regs), C.byref(cfg), C.byref(k), float(tau),
+                                           1 if first else 0, _stream()), ctx.lib, ctx.h)
+
+
 class TabularCooling:
     """cooling::TabularCooling (src/hydro/srcterms/tabular_cooling.hpp:175-250) on an apk_cooling_table.
     log_temps / log_lambdas: the table's rows as read from the file (log10 K, log10 of lambda in lambda_units_cgs);

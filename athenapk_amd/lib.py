@@ -65,6 +65,14 @@ def make_diff_cfg(conduction="none", kappa=0.0, sat_phi=0.3, viscosity="none", n
                    RESISTIVITY[resistivity], fixed, eta)
 
 
+class Rkl2Regs(C.Structure):
+    _fields_ = [("y0", C.c_void_p), ("yjm2", C.c_void_p), ("my0", C.c_void_p)]
+
+
+class Rkl2Coeffs(C.Structure):
+    _fields_ = [("mu", C.c_double), ("nu", C.c_double), ("mu_tilde", C.c_double), ("gamma_tilde", C.c_double)]
+
+
 class CoolingParams(C.Structure):
     _fields_ = [("integrator", C.c_int), ("max_iter", C.c_int), ("cfl", C.c_double), ("d_log_temp_tol", C.c_double),
                 ("d_e_tol", C.c_double), ("T_floor", C.c_double), ("lambda_units", C.c_double), ("gamma", C.c_double),
@@ -231,6 +239,12 @@ def _signatures():
         "apk_estimate_timestep": (i, [vp, vp, i, E, d, c_dp, vp]),
         "apk_calc_diff_fluxes": (i, [vp, vp, C.POINTER(DiffCfg), vp]),
         "apk_estimate_diffusion_timestep": (i, [vp, vp, C.POINTER(DiffCfg), d, c_dp, vp]),
+        "apk_rkl2_num_stages": (i, [d, d, C.POINTER(C.c_int)]),
+        "apk_rkl2_coefficients": (i, [i, i, c_dp, c_dp, c_dp, c_dp]),
+        "apk_flux_divergence": (i, [vp, vp, vp, vp]),
+        "apk_rkl2_step_first": (i, [vp, vp, vp, vp, vp, i, d, vp]),
+        "apk_rkl2_step_other": (i, [vp, vp, vp, vp, vp, d, d, d, d, d, vp]),
+        "apk_rkl2_substage_fused": (i, [vp, vp, C.POINTER(Rkl2Regs), C.POINTER(DiffCfg), C.POINTER(Rkl2Coeffs), d, i, vp]),
         "apk_cooling_table_create": (i, [vp, c_dp, c_dp, i, C.POINTER(CoolingParams), pp]),
         "apk_cooling_table_destroy": (None, [vp]),
         "apk_cooling_dedt": (i, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
@@ -304,6 +318,8 @@ def _signatures():
         "apk_sim_loop_cycles": (i, [vp]),
         "apk_sim_get_info": (i, [vp, C.POINTER(SimInfo)]),
         "apk_sim_diffusion_options": (i, [vp, C.POINTER(DiffCfg), C.POINTER(C.c_int), c_dp]),
+        "apk_sim_rkl2_max_dt_ratio": (d, [vp]),
+        "apk_sim_sts_info": (i, [vp, C.POINTER(C.c_int), c_dp, C.POINTER(C.c_int)]),
         "apk_sim_units": (i, [vp, C.POINTER(UnitsInfo)]),
         "apk_sim_cooling_options": (i, [vp, C.POINTER(C.c_int), C.POINTER(CoolingParams), C.POINTER(C.c_int)]),
         "apk_sim_cooling_table": (i, [vp, i, c_dp, i, C.POINTER(C.c_int)]),

@@ -408,7 +408,7 @@ int apk_stage_dt_flags_read(apk_ctx *ctx, double cfl, double *dt_out, unsigned *
 int apk_estimate_timestep(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos,
                           double cfl, double *dt_out, apk_stream_t stream);
 
-/* ---- unsplit diffusion (diffusion/integrator = unsplit) -----------------------------------------------------------
+/* ---- diffusion: fluxes and time step (diffusion/integrator = unsplit | rkl2) -----------------------------------------------------------
  * Option enums: numeric values = position in the reference's enum classes, src/main.hpp:40-46. */
 enum apk_conduction { APK_COND_NONE = 0, APK_COND_ISOTROPIC = 1, APK_COND_ANISOTROPIC = 2 };
 enum apk_conduction_coeff { APK_CONDC_NONE = 0, APK_CONDC_FIXED = 1, APK_CONDC_SPITZER = 2 };
@@ -449,6 +449,49 @@ int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c
  * No process enabled: *dt_out = DBL_MAX. */
 int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, double cfl_diff,
                                     double *dt_out, apk_stream_t stream);
+
+/* ---- RKL2 super-time-stepping (diffusion/integrator = rkl2) ---------------------------------------------------------
+ * Operator-split Runge-Kutta-Legendre super-time-stepping of the diffusive processes (Meyer, Balsara & Aslam 2014):
+ * AddSTSTasks, src/hydro/hydro_driver.cpp:168-344.  A half step of length tau takes s sub-stages on four registers of
+ * conserved variables: Y0 (the state on entry), Yjm1 (the pack that carries primitives and flux arrays, "base"), Yjm2
+ * and MY0 = -div F_diff(Y0).  After every sub-stage the caller exchanges the ghost zones of Yjm1 and converts it to
+ * primitives (hydro_driver.cpp:269-273, 334-338). */
+
+/* Replaces the stage count of AddSTSTasks (hydro_driver.cpp:176-181; Meyer+2014 eq. 21):
+ * s = int(0.5 * (sqrt(9 + 16 tau / dt_diff) - 1)) + 1, made odd.  Host only. */
+int apk_rkl2_num_stages(double tau, double dt_diff, int *s_rkl);
+/* Replaces the coefficients of sub-stage j of s (1 <= j <= s): j = 1 gives mu_tilde_1 = 4 / (3 (s^2 + s - 2))
+ * (hydro_driver.cpp:101-104; the others 0), j >= 2 the recursion of hydro_driver.cpp:276-291, 341-342, in the
+ * reference's operation order.  Host only. */
+int apk_rkl2_coefficients(int s_rkl, int j, double *mu, double *nu, double *mu_tilde, double *gamma_tilde);
+/* Replaces parthenon::Update::FluxDivergence<MeshData<Real>>(md, out), call site hydro_driver.cpp:254-255:
+ * out.cons <- -div F(md.flux) on interior cells, every variable; the expression and term order of
+ * apk_update_with_flux_divergence. */
+int apk_flux_divergence(apk_ctx *ctx, const apk_pack *md, const apk_pack *out, apk_stream_t stream);
+/* Replaces RKL2StepFirst(Y0, Yjm1, Yjm2, MY0, s_rkl, tau), hydro_driver.cpp:93-126:
+ * Yjm1 <- Y0 + mu_tilde_1 tau MY0, Yjm2 <- Y0 on interior cells.  The four registers are distinct arrays. */
+int apk_rkl2_step_first(apk_ctx *ctx, const apk_pack *y0, const apk_pack *yjm1, const apk_pack *yjm2, const apk_pack *my0,
+                        int s_rkl, double tau, apk_stream_t stream);
+/* Replaces RKL2StepOther(Y0, Yjm1, Yjm2, MY0, mu_j, nu_j, mu_tilde_j, gamma_tilde_j, tau), hydro_driver.cpp:128-166:
+ * Yj = mu_j Yjm1 + nu_j Yjm2 + (1 - mu_j - nu_j) Y0 + mu_tilde_j tau (-div F(Yjm1.flux)) + gamma_tilde_j tau MY0;
+ * Yjm2 <- Yjm1, Yjm1 <- Yj.  Yjm1 carries the flux arrays (zeroed, then apk_calc_diff_fluxes). */
+int apk_rkl2_step_other(apk_ctx *ctx, const apk_pack *y0, const apk_pack *yjm1, const apk_pack *yjm2, const apk_pack *my0,
+                        double mu_j, double nu_j, double mu_tilde_j, double gamma_tilde_j, double tau, apk_stream_t stream);
+
+typedef struct apk_rkl2_regs {
+  const apk_pack *y0, *yjm2, *my0; /* conserved arrays only; the shape of the pack they go with */
+} apk_rkl2_regs;
+typedef struct apk_rkl2_coeffs {
+  double mu, nu, mu_tilde, gamma_tilde; /* apk_rkl2_coefficients; the first sub-stage reads mu_tilde (= mu_tilde_1) only */
+} apk_rkl2_coeffs;
+/* One whole sub-stage in ONE kernel: replaces ResetFluxes + CalcDiffFluxes + FluxDivergence + RKL2StepFirst (first != 0;
+ * hydro_driver.cpp:234-260) or ResetFluxes + CalcDiffFluxes + RKL2StepOther (hydro_driver.cpp:306-326).  A lane owns an
+ * interior cell of md (= Yjm1), forms the diffusive fluxes through its 2 ndim faces from md.prim (one layer of ghost
+ * cells, edges too) with the arithmetic of apk_calc_diff_fluxes on zeroed arrays, takes their divergence and applies the
+ * step: in the parity build bit for bit what the sequence above leaves in Yjm1, Yjm2 (and MY0 when first).  Reads
+ * primitives, writes conserved arrays: in place, no flux arrays needed. */
+int apk_rkl2_substage_fused(apk_ctx *ctx, const apk_pack *md, const apk_rkl2_regs *regs, const apk_diff_cfg *cfg,
+                            const apk_rkl2_coeffs *coeffs, double tau, int first, apk_stream_t stream);
 
 /* ---- tabular radiative cooling (<cooling> enable_cooling = tabular) -------------------------------------------------
  * Integrator enum: numeric values = position in cooling::CoolIntegrator, tabular_cooling.hpp:96. */

@@ -182,6 +182,12 @@ int apk_sim_get_info(const apk_sim *sim, apk_sim_info *info);
 /* the <diffusion> options as parsed (hydro.cpp:538-702): the processes and coefficients, diffusion/integrator
  * (apk_diffint) and diffusion/cfl (0 when the integrator is none) */
 int apk_sim_diffusion_options(const apk_sim *sim, apk_diff_cfg *cfg, int *integrator, double *cfl_diff);
+/* diffusion/rkl2_max_dt_ratio as parsed (-1 unless diffusion/integrator = rkl2, which requires a positive one) */
+double apk_sim_rkl2_max_dt_ratio(const apk_sim *sim);
+/* super-time-stepping: what the last half step did -- its number of sub-stages and its ratio 2 tau / dt_diff (0 before
+ * the first cycle) -- and which form a sub-stage takes: 1 the fused kernel (apk_rkl2_substage_fused), 0 the passes over
+ * the flux arrays (apk_amd/sts_substage = fused | arrays) */
+int apk_sim_sts_info(const apk_sim *sim, int *s_rkl, double *ratio, int *fused);
 /* <units> (src/units.hpp) and the gas composition (hydro.cpp:482-503) as parsed.  has_units: a <units> block exists;
  * has_composition: so does hydro/He_mass_fraction (mu, mu_e, mbar, mbar_over_kb are 0 otherwise). */
 typedef struct apk_units_info {
