@@ -1610,6 +1610,7 @@ int create_common(const char *deck, const char *const *overrides, int noverrides
     for (int d = 0; d < 3; ++d)
       if ((s->mesh.bc_in[d] == BC_REFLECT || s->mesh.bc_out[d] == BC_REFLECT) && s->pkg.fluid != APK_FLUID_EULER)
         throw std::runtime_error("Reflecting boundary conditions for MHD need special treatment.");
+    tracers_initialize(s);  // <tracers> (after the hydro package, as the reference's Initialize order)
   } catch (const std::exception &e) {
     if (errbuf && errlen) std::snprintf(errbuf, errlen, "%s", e.what());
     delete s;
@@ -1722,6 +1723,7 @@ int apk_sim_create(const char *deck, const char *const *overrides, int noverride
   if ((rc = build_x1_tables(s)) != APK_OK) return bail(rc);
   if (s->mesh.ndim == 3 && (rc = build_face_table(s)) != APK_OK) return bail(rc);
   if (s->fmft && (rc = turbulence_device_setup(s)) != APK_OK) return bail(rc);
+  if (s->tracers && (rc = tracers_device_setup(s)) != APK_OK) return bail(rc);
   return APK_OK;
 }
 
@@ -1760,6 +1762,7 @@ void apk_sim_destroy(apk_sim *s) {
     dev_free(s, reinterpret_cast<double *>(s->d_face_nbr));
     for (auto &t : s->d_x1_tab) dev_free(s, static_cast<double *>(t));
     sts_free(s);
+    tracers_free(s);
     dev_free(s, s->d_acc);
     dev_free(s, s->d_phases);
     dev_free(s, s->d_cons2[0]);
@@ -1890,6 +1893,7 @@ int apk_sim_initialize(apk_sim *s) {
   double est = kHuge;
   SIM_TRY(s, estimate_timestep(s, &est));
   set_global_dt(s, est);
+  SIM_TRY(s, tracers_seed_initial(s));  // SeedInitialTracers (UserWorkBeforeLoopMesh, tracers.cpp:87, 95-186)
   return APK_OK;
 }
 
@@ -1904,6 +1908,9 @@ int apk_sim_step(apk_sim *s) {
   if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
   for (int stage = 1; stage <= s->nstages; ++stage) SIM_TRY(s, do_stage(s, stage));
   if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
+  // the tracer step: after the last stage (and the turbulence kick inside it), with the cycle's dt
+  // (hydro_driver.cpp:615-660)
+  if (s->tracers) SIM_TRY(s, tracers_cycle(s, s->dt));
   s->time += s->dt;
   s->ncycle += 1;
   s->zone_cycles += (long long)s->mesh.mb[0] * s->mesh.mb[1] * s->mesh.mb[2] * (long long)s->mesh.nblocks_total;
@@ -2375,6 +2382,7 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
   struct HstOut {
     std::string path;
     double dt, next;
+    int rows = 0;  // history rows written so far
   };
   std::vector<HstOut> outs;
   try {
@@ -2393,9 +2401,17 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     return fail(s, APK_ERR_INVALID, e.what());
   }
   SIM_TRY(s, apk_sim_initialize(s));
+  // the tracers next to every history row: <history file without .hst>.<row, 5 digits>.tracers.<field>.npy
+  auto write_tracers = [&](HstOut &o) -> int {
+    if (!s->tracers) return APK_OK;
+    char num[16];
+    std::snprintf(num, sizeof num, "%05d", o.rows++);
+    return tracers_write_outputs(s, o.path.substr(0, o.path.size() - 4) + "." + num + ".tracers");
+  };
   for (auto &o : outs) {
     if (s->rank == 0) std::remove(o.path.c_str());
     SIM_TRY(s, apk_sim_write_history(s, o.path.c_str()));
+    SIM_TRY(s, write_tracers(o));
     o.next = o.dt;
   }
   int n = 0;
@@ -2419,6 +2435,7 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     for (auto &o : outs)
       if (s->time >= o.next || last) {
         SIM_TRY(s, apk_sim_write_history(s, o.path.c_str()));
+        SIM_TRY(s, write_tracers(o));
         while (o.next <= s->time) o.next += o.dt;
       }
   }

@@ -103,6 +103,32 @@ struct FieldLoopState {  // parameters of src/pgen/field_loop.cpp:129-170; B0 no
   double rad = 0, amp = 0, vflow = 0, drat = 1.0, cos_a2 = 0, sin_a2 = 0, lambda = 0;
 };
 
+// <tracers> (src/tracers/tracers.cpp:43-93) and the rank-wide particle arrays (host/tracers.cpp)
+struct TracerState {
+  // the deck's options
+  int seed_method = APK_TRACER_SEED_NONE;
+  double per_cell = 0.0;
+  long long rng_seed = 0;
+  bool fused = true;  // apk_amd/tracer_step = fused | passes
+  int nfields = 5;
+  // particles seeded on the host and not yet on the device (random_per_block: drawn at creation, uploaded by
+  // apk_sim_initialize; a host-only sim keeps them, which is what the CPU tests read)
+  std::vector<double> hx, hy, hz;
+  std::vector<int64_t> hid;
+  std::vector<int32_t> hblock;
+  int64_t next_id = 0;  // seed method user: ids run sequentially in call order
+  // device: two sets of the arrays (the counting sort writes from one into the other), the block tables of the geometry,
+  // the counters {lost, order changed} and the sort's buckets
+  int64_t n = 0, cap = 0;
+  double *set[2] = {nullptr, nullptr};
+  int cur = 0;
+  double *d_origin = nullptr, *d_table = nullptr, *d_counters = nullptr, *d_buckets = nullptr;
+  int nbuckets = 0;
+  apk_tracer_geom geom{};
+  long long lost = 0;
+  long long steps = 0, sorts = 0;  // tracer steps taken and counting sorts run since initialisation (apk_sim_tracers_stats)
+};
+
 }  // namespace apk
 
 namespace apk {
@@ -349,6 +375,8 @@ struct apk_sim {
   double *d_my0 = nullptr, *d_yjm2 = nullptr;
   apk_pack *my0_pack = nullptr, *yjm2_pack = nullptr;
   bool sts_fused = false;
+  // tracer particles (host/tracers.cpp): null unless tracers/enabled = true
+  std::unique_ptr<apk::TracerState> tracers;
   int sts_last_s = 0;           // sub-stages of the last half step taken
   double sts_last_ratio = 0.0;  // its 2 tau / dt_diff
   long long overlapped = 0;

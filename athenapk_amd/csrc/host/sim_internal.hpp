@@ -100,6 +100,12 @@ int turbulence_driving(apk_sim *s, double dt, bool fill = false, bool no_prim = 
 int do_stage(apk_sim *s, int stage);
 int sts_half_step(apk_sim *s, double tau);  // AddSTSTasks (host/sts.cpp)
 void sts_free(apk_sim *s);
+void tracers_initialize(apk_sim *s);           // <tracers> (host/tracers.cpp), called at creation after the mesh is known
+int tracers_device_setup(apk_sim *s);          // geometry tables and counters
+int tracers_seed_initial(apk_sim *s);          // upload what the deck seeded, sort, fill (tracers.cpp:95-186)
+int tracers_cycle(apk_sim *s, double dt);      // the tracer step after the last stage (hydro_driver.cpp:615-660)
+int tracers_write_outputs(apk_sim *s, const std::string &prefix);
+void tracers_free(apk_sim *s);
 double xc(const apk_sim *s, const double x0[3], int d, int idx);
 void block_origin(const apk_sim *s, int lb, double x0[3]);
 void lw_eigensystem(double gm1, double v1, double v2, double v3, double h, double ev[5], double rem[5][5]);

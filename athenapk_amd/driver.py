@@ -624,6 +624,43 @@ class Simulation(_FmftHost, _MeshView):
         self._check(self.lib.apk_sim_reset_time_step(self.h))
         return self.dt
 
+    # ---- tracer particles (<tracers>; apk_host.h) ---------------------------------------
+    def tracers_options(self):
+        """the <tracers> block as parsed (see HostPlan.tracers_options)"""
+        return _tracers_options(self.lib, self.h)
+
+    def seed_tracers(self, x, y, z):
+        """tracers/initial_seed_method = user: particles at the given positions, ids sequential in call order; their
+        fields are filled at once"""
+        x, y, z = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+        assert x.size == y.size == z.size
+        self._check(self.lib.apk_sim_tracers_seed(self.h, x.ctypes.data_as(L.c_dp), y.ctypes.data_as(L.c_dp),
+                                                  z.ctypes.data_as(L.c_dp), x.size))
+        return self
+
+    def tracers_count(self):
+        """(active, lost): particles still in the domain, and lost through non-periodic boundaries so far"""
+        a, lost = C.c_longlong(0), C.c_longlong(0)
+        self._check(self.lib.apk_sim_tracers_count(self.h, None, C.byref(a), C.byref(lost)))
+        return a.value, lost.value
+
+    def tracers_stats(self):
+        """(tracer steps taken since initialize(), counting sorts run)"""
+        a, b = C.c_longlong(0), C.c_longlong(0)
+        self._check(self.lib.apk_sim_tracers_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def tracers(self, fields=None):
+        """dict of numpy arrays sorted by id: x, y, z, id, block (local index), active, rho, pressure, vel_x, vel_y,
+        vel_z and, with GLM-MHD, B_x, B_y, B_z (`fields`: only these, and id)"""
+        nf = self.tracers_options()["nfields"]
+        names = [n for n, _ in L.TRACER_FIELDS[:6 + nf]]
+        return _tracers_read(self.lib, self.h, names if fields is None else list(fields))
+
+    def tracers_step(self, dt):
+        """the tracer step alone on the current state (what step() runs after the last stage)"""
+        self._check(self.lib.apk_sim_tracers_step(self.h, float(dt)))
+
 
 def _diffusion_options(lib, h):
     cfg, integ, cfl = L.DiffCfg(), C.c_int(0), C.c_double(0.0)
@@ -665,6 +702,35 @@ def _cooling_table(lib, h, which):
     out = (C.c_double * max(size.value, 1))()
     lib.apk_sim_cooling_table(h, which, out, size.value, C.byref(size))
     return np.array(out[:size.value], dtype=np.float64)
+
+
+def _tracers_options(lib, h):
+    o = L.TracersOptions()
+    rc = lib.apk_sim_tracers_options(h, C.byref(o))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_tracers_options")
+    seed = {v: k for k, v in L.TRACER_SEED.items()}[o.seed_method]
+    return {"enabled": bool(o.enabled), "initial_seed_method": seed, "tracer_step": "fused" if o.fused else "passes",
+            "nfields": o.nfields, "initial_num_tracers_per_cell": o.num_tracers_per_cell, "initial_rng_seed": o.rng_seed,
+            "num_tracers_per_block": o.num_tracers_per_block}
+
+
+def _tracers_read(lib, h, names):
+    """{name: array} of the tracer arrays in `names`, sorted by id"""
+    total = C.c_longlong(0)
+    rc = lib.apk_sim_tracers_count(h, C.byref(total), None, None)
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, lib.apk_sim_last_error(h).decode())
+    raw = {}
+    for name in ("id",) + tuple(n for n in names if n != "id"):
+        slot = [q for q, (fname, _) in enumerate(L.TRACER_FIELDS) if fname == name][0]
+        a = np.zeros(total.value, dtype=L.TRACER_FIELDS[slot][1])
+        rc = lib.apk_sim_tracers_read(h, slot, a.ctypes.data_as(C.c_void_p))
+        if rc != L.APK_OK:
+            raise L.ApkError(rc, lib.apk_sim_last_error(h).decode())
+        raw[name] = a
+    order = np.argsort(raw["id"], kind="stable")
+    return {name: raw[name][order] for name in raw}
 
 
 class HostPlan(_FmftHost, _MeshView):
@@ -728,3 +794,13 @@ class HostPlan(_FmftHost, _MeshView):
     def cooling_table(self, which):
         """one array of the parsed table: "log_temps", "log_lambdas" (code units), "alpha_k", "Y_k" (Townsend)"""
         return _cooling_table(self.lib, self.h, ("log_temps", "log_lambdas", "alpha_k", "Y_k").index(which))
+
+    def tracers_options(self):
+        """<tracers> as parsed: enabled, initial_seed_method, initial_num_tracers_per_cell, initial_rng_seed,
+        num_tracers_per_block, nfields (5, or 8 with GLM-MHD) and apk_amd/tracer_step"""
+        return _tracers_options(self.lib, self.h)
+
+    def seeded_tracers(self):
+        """what tracers/initial_seed_method = random_per_block seeds on this rank (drawn on the host): x, y, z, id, block
+        sorted by id"""
+        return _tracers_read(self.lib, self.h, ["x", "y", "z", "id", "block"])

@@ -27,7 +27,7 @@ APK_FLAG_COOL_MAX_ITER = 4
 APK_FLAG_COOL_TABLE = 8
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
-                "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3")
+                "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort")
 
 APK_OK = 0
 APK_RCCL_ID_BYTES = 128
@@ -192,6 +192,29 @@ class RegionInfo(C.Structure):
                 ("src_stride", C.c_int64 * 4), ("dst_stride", C.c_int64 * 4)]
 
 
+class TracerArrays(C.Structure):
+    _fields_ = [("n", C.c_int64), ("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("id", C.c_void_p),
+                ("block", C.c_void_p), ("active", C.c_void_p), ("field", C.c_void_p * 8), ("nfields", C.c_int)]
+
+
+class TracerGeom(C.Structure):
+    _fields_ = [("xmin", C.c_double * 3), ("xmax", C.c_double * 3), ("dx", C.c_double * 3), ("block_size", C.c_double * 3),
+                ("nb", C.c_int * 3), ("periodic_lo", C.c_int * 3), ("periodic_hi", C.c_int * 3),
+                ("block_origin", C.c_void_p), ("block_table", C.c_void_p)]
+
+
+TRACER_SEED = {"none": 0, "random_per_block": 1, "user": 2}
+# apk_sim_tracers_read: field number and numpy dtype of every array
+TRACER_FIELDS = (("x", "f8"), ("y", "f8"), ("z", "f8"), ("id", "i8"), ("block", "i4"), ("active", "i4"), ("rho", "f8"),
+                 ("pressure", "f8"), ("vel_x", "f8"), ("vel_y", "f8"), ("vel_z", "f8"), ("B_x", "f8"), ("B_y", "f8"),
+                 ("B_z", "f8"))
+
+
+class TracersOptions(C.Structure):
+    _fields_ = [("enabled", C.c_int), ("seed_method", C.c_int), ("fused", C.c_int), ("nfields", C.c_int),
+                ("num_tracers_per_cell", C.c_double), ("rng_seed", C.c_longlong), ("num_tracers_per_block", C.c_longlong)]
+
+
 class AmrOpInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("level", C.c_int), ("src_kind", C.c_int), ("src_block", C.c_int),
                 ("dst_kind", C.c_int), ("dst_block", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3),
@@ -283,6 +306,11 @@ def _signatures():
         "apk_copy_plan_run": (i, [vp, vp, vp]),
         "apk_copy_plan_run_c2p": (i, [vp, vp, i, E, C.c_int64, i, vp]),
         "apk_copy_plan_run_c2p_prim_only": (i, [vp, vp, i, E, C.c_int64, i, vp]),
+        "apk_tracers_advect": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), d, vp]),
+        "apk_tracers_reown": (i, [vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), vp, vp]),
+        "apk_tracers_fill": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), vp]),
+        "apk_tracers_step_fused": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), d, vp, vp]),
+        "apk_tracers_sort": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerArrays), C.POINTER(TracerGeom), vp, i, vp]),
         "apk_kernel_timing_enable": (i, [vp, i]),
         "apk_kernel_timing_read": (i, [vp, i, c_dp, C.POINTER(ll)]),
         # apk_host.h
@@ -323,6 +351,12 @@ def _signatures():
         "apk_sim_units": (i, [vp, C.POINTER(UnitsInfo)]),
         "apk_sim_cooling_options": (i, [vp, C.POINTER(C.c_int), C.POINTER(CoolingParams), C.POINTER(C.c_int)]),
         "apk_sim_cooling_table": (i, [vp, i, c_dp, i, C.POINTER(C.c_int)]),
+        "apk_sim_tracers_options": (i, [vp, C.POINTER(TracersOptions)]),
+        "apk_sim_tracers_count": (i, [vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ll)]),
+        "apk_sim_tracers_stats": (i, [vp, C.POINTER(ll), C.POINTER(ll)]),
+        "apk_sim_tracers_read": (i, [vp, i, vp]),
+        "apk_sim_tracers_seed": (i, [vp, c_dp, c_dp, c_dp, ll]),
+        "apk_sim_tracers_step": (i, [vp, d]),
         "apk_sim_block_location": (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int * 3)]),
         "apk_sim_block_ptr": (vp, [vp, i, i]),
         "apk_sim_gather": (i, [vp, i, c_dp]),

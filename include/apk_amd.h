@@ -777,6 +777,56 @@ int apk_tag_blocks_end(apk_ctx *ctx, int nblocks, int criterion, int pending, do
 int apk_history_user_reldivb(apk_ctx *ctx, const apk_pack *md, double B0, double *out,
                              apk_stream_t stream);
 
+/* ---- tracer particles (src/tracers/tracers.cpp; uniform meshes, 3-D) ----------------------------------------------
+ * One rank-wide structure of arrays in DEVICE memory: positions, id, the index of the owning block in the pack, an
+ * active flag (0 once the particle has left through a non-periodic boundary) and the fields FillTracers interpolates
+ * (tracers.cpp:64-85), in this order: rho, pressure, vel_x, vel_y, vel_z and, with GLM-MHD (nfields = 8), B_x, B_y,
+ * B_z. */
+typedef struct apk_tracer_arrays {
+  int64_t n;
+  double *x, *y, *z;
+  int64_t *id;
+  int32_t *block;
+  int32_t *active;
+  double *field[8];
+  int nfields; /* 5 or 8 */
+} apk_tracer_arrays;
+/* The uniform block grid the particles live on.  block_origin: DEVICE array [nblocks][3], the lower interior face of
+ * every block of the pack; block_table: DEVICE array [nb[2]][nb[1]][nb[0]], block coordinates to index in the pack;
+ * block_size = cells per block times dx; periodic_lo / periodic_hi: that boundary of the domain wraps positions (every
+ * other kind of boundary loses the particle). */
+typedef struct apk_tracer_geom {
+  double xmin[3], xmax[3], dx[3], block_size[3];
+  int nb[3], periodic_lo[3], periodic_hi[3];
+  const double *block_origin;
+  const int32_t *block_table;
+} apk_tracer_geom;
+/* Replaces Tracers::AdvectTracers (tracers.cpp:189-242): Heun's method with the velocities the last fill stored on the
+ * particle, x* = x + dt v_p, v* = the primitives' velocity interpolated at x* in the particle's block, x += dt / 2
+ * (v_p + v*).  Trilinear on cell centres like interpolation::cent::linear, NOT clamped to the interior: reads prim two
+ * ghost layers deep, edges and corners included (APK_ERR_NGHOST with fewer).  Positions are left unwrapped. */
+int apk_tracers_advect(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *tracers, const apk_tracer_geom *geom,
+                       double dt, apk_stream_t stream);
+/* Replaces what the swarm's transport does on one rank after the advection (hydro_driver.cpp:615-660): positions beyond
+ * a periodic boundary wrap, particles beyond any other boundary become inactive, and every other particle gets the block
+ * that contains its position.  counters: two DEVICE words, [0] += particles lost, [1] = 1 when any particle changed its
+ * block or was lost. */
+int apk_tracers_reown(apk_ctx *ctx, const apk_tracer_arrays *tracers, const apk_tracer_geom *geom,
+                      unsigned long long *counters, apk_stream_t stream);
+/* Replaces Tracers::FillTracers (tracers.cpp:249-308): all fields interpolated at the particle's position in its
+ * block. */
+int apk_tracers_fill(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *tracers, const apk_tracer_geom *geom,
+                     apk_stream_t stream);
+/* The three of them in ONE launch (one lane per particle, both gathers; tracers.cpp:189-308 and
+ * hydro_driver.cpp:615-660).  Bit for bit what the three calls give in the -ffp-contract=off build. */
+int apk_tracers_step_fused(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *tracers, const apk_tracer_geom *geom,
+                           double dt, unsigned long long *counters, apk_stream_t stream);
+/* Counting sort of the particles by (block, interior k-plane), inactive ones last, into a second set of arrays `out`
+ * (no equivalent in the reference, whose swarms are per block).  buckets: DEVICE scratch of nbuckets = blocks x nx3 + 1
+ * words.  The order inside a bucket is arbitrary. */
+int apk_tracers_sort(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *tracers, const apk_tracer_arrays *out,
+                     const apk_tracer_geom *geom, unsigned long long *buckets, int nbuckets, apk_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
  * they are launched on.  When enabled, every kernel launch of the listed groups is
@@ -795,7 +845,9 @@ enum apk_timing_slot {
   APK_T_FUSED_DC_X1 = 9,  /* the three fused sweeps when the stage reconstructs with donor */
   APK_T_FUSED_DC_X2 = 10, /* cell (VL2 predictor, hydro.cpp:457-463); slots 0-2 then hold   */
   APK_T_FUSED_DC_X3 = 11, /* only the high-order stages                                    */
-  APK_T_COUNT = 12
+  APK_T_TRACERS = 12,     /* tracer particles: advect, re-own, fill (or the fused step) */
+  APK_T_TRACER_SORT = 13, /* ... and their counting sort (memset, histogram, scan, scatter) */
+  APK_T_COUNT = 14
 };
 int apk_kernel_timing_enable(apk_ctx *ctx, int on);
 /* total_ms / launches may be NULL */

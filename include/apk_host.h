@@ -204,6 +204,38 @@ int apk_sim_cooling_options(const apk_sim *sim, int *enabled, apk_cooling_params
 /* one array of the parsed table: which = 0 log_temps, 1 log_lambdas (code units), 2 Townsend alpha_k, 3 Townsend Y_k
  * (n_temp - 1 entries; townsend only); copies min(n, size) values into out, *size = the array's length */
 int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int *size);
+/* ---- tracer particles (<tracers>, src/tracers/tracers.cpp; csrc/host/tracers.cpp) ---------------------------------
+ * Keys (tracers.cpp:43-93, 102-118): enabled (default false), initial_seed_method = none | random_per_block | user,
+ * initial_num_tracers_per_cell, initial_rng_seed; and apk_amd/tracer_step = fused (default) | passes.  Refused at
+ * creation: nx3 == 1, parthenon/mesh/refinement != none, more than one rank, nghost < 2, an unknown seed method,
+ * random_per_block with a per-block count <= 0.  One rank, uniform meshes, no restart, no turbulence lookbacks.
+ * random_per_block draws its positions on the HOST from a stateless counter-based generator (splitmix64 keyed on
+ * (initial_rng_seed + gid, n, component), 53-bit mantissas) where the reference uses Kokkos' pool: same layout of ids
+ * (n_per_block * gid + n), other positions. */
+enum apk_tracer_seed { APK_TRACER_SEED_NONE = 0, APK_TRACER_SEED_RANDOM_PER_BLOCK = 1, APK_TRACER_SEED_USER = 2 };
+typedef struct apk_tracers_options {
+  int enabled, seed_method, fused, nfields; /* nfields: 5, or 8 with GLM-MHD (B_x, B_y, B_z) */
+  double num_tracers_per_cell;
+  long long rng_seed, num_tracers_per_block;
+} apk_tracers_options;
+/* the options as parsed (valid on a host-only sim; all zero with tracers disabled) */
+int apk_sim_tracers_options(const apk_sim *sim, apk_tracers_options *opt);
+/* particles in the arrays, of which active, and lost so far through non-periodic boundaries (total = active + lost) */
+int apk_sim_tracers_count(apk_sim *sim, long long *total, long long *active, long long *lost);
+/* tracer steps taken since apk_sim_initialize and counting sorts run (one at seeding, then one after every step in
+ * which a particle changed its block or was lost) */
+int apk_sim_tracers_stats(const apk_sim *sim, long long *steps, long long *sorts);
+/* one array in storage order (the driver keeps particles sorted by block and k-plane, not by id): field 0 x, 1 y, 2 z
+ * (doubles), 3 id (int64), 4 local block index (int32), 5 active flag (int32), 6.. rho, pressure, vel_x, vel_y, vel_z,
+ * B_x, B_y, B_z (doubles).  A host-only sim returns fields 0..4 of what the deck seeded. */
+int apk_sim_tracers_read(apk_sim *sim, int field, void *out);
+/* seed method user (ProblemSeedInitialTracers): n more particles at the given positions, ids sequential in call order;
+ * owners from the block grid, fields filled at once (tracers.cpp:173-186).  Positions outside the domain are refused. */
+int apk_sim_tracers_seed(apk_sim *sim, const double *x, const double *y, const double *z, long long n);
+/* the tracer step alone on the current state (what apk_sim_step runs after the last stage with the cycle's dt):
+ * completes primitives and ghost zones, advects, re-owns, fills, sorts when ownership changed.  For tests. */
+int apk_sim_tracers_step(apk_sim *sim, double dt);
+
 /* global block id and logical (bx,by,bz) of local block lb */
 int apk_sim_block_location(const apk_sim *sim, int lb, int *gid, int loc[3]);
 /* Mesh refinement (parthenon/mesh/refinement = static | adaptive, numlevel, derefine_count,
