@@ -249,14 +249,14 @@ struct apk_sim {
   int pending_c2p = 0;  // the exchange in flight converts ghost zones as it fills them (GHOST_C2P / GHOST_PRIM_ONLY)
   int pending_cons = 0;  // cons buffer whose ghost zones the exchange in flight fills (roles may swap meanwhile)
   // device window tables (apk_stage_args.window, 8 ints per block) of the split stages:
-  // x1 sweep: main / low slab / high slab; 3-D donor-cell stage: main / z lo,hi / y lo,hi / x lo,hi
+  // main / low slab / high slab
   struct WindowTable {
     int *d = nullptr;
     int rl = 0, rows = 0;
     bool any = false;  // some block has work in this table
   };
-  WindowTable x1win[3], dcwin[7];
-  WindowTable k3win[3];  // two-kernel stages: plane windows of the x3 sweep (main, low slab, high slab)
+  WindowTable x1win[3];  // column windows of the x1 sweep
+  WindowTable k3win[3];  // two-kernel stages: plane windows of the x3 sweep
   unsigned *d_late_regions = nullptr;  // per block: bit (sx+1)+3(sy+1)+9(sz+1) = that neighbour region is filled late
   // Direct neighbour addressing (apk_stage_args.face_neighbor; uniform 3-D meshes): per local block
   // and face the local index of the same-rank block behind it, or -1.  While every stage of the

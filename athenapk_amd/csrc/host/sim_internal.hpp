@@ -1,5 +1,6 @@
-// sim_internal.hpp -- what the translation units of the standalone host driver share (sim.cpp: set-up,
-// stage loop, C API; sim_pgen.cpp: problem generators; sim_amr.cpp: refined meshes).  Not installed.
+// sim_internal.hpp -- what the translation units of the standalone host driver share (sim.cpp: set-up
+// and C API; stage.cpp: ghost exchange and stage loop; sim_pgen.cpp: problem generators; sim_amr.cpp: refined
+// meshes).  Not installed.
 #pragma once
 
 #include "sim.hpp"
@@ -53,6 +54,7 @@ void mesh_initialize(apk_sim *s);
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);
 void dev_free(apk_sim *s, double *p);
 int build_packs(apk_sim *s);
+int ensure_trial_cons(apk_sim *s);
 int ensure_spare_prim(apk_sim *s);
 int ensure_flux_arrays(apk_sim *s);
 bool stage_can_fuse(const apk_sim *s);
@@ -85,7 +87,13 @@ int exchange_end(apk_sim *s, int c2p);
 int exchange_ghosts(apk_sim *s, int c2p = GHOST_COPY, bool skip_local = false, bool thin = false);
 int upload_window(apk_sim *s, const char *tag, const std::vector<int> &w, apk_sim::WindowTable &t);
 int build_windows(apk_sim *s);
-bool can_overlap_next(const apk_sim *s, int next);
+// what the predicates of the cycle's form (direct_neighbors, amr_direct, prim_free_cycle, rk_prim_free_cycle,
+// amr_prim_free_cycle, thin_exchange_cycle, x1_direct_kind) say, evaluated once per stage by do_stage
+struct CycleForm {
+  bool direct, amr_direct, prim_free, rk_free, amr_pf, thin;
+  int x1_kind;
+};
+bool can_overlap_next(const apk_sim *s, const CycleForm &f, int next);
 int finish_pending(apk_sim *s);
 bool direct_neighbors(const apk_sim *s);
 bool amr_faces_only(const apk_sim *s);
