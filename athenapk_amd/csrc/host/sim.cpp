@@ -1545,6 +1545,15 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
   } catch (const std::exception &e) {
     return fail(s, APK_ERR_INVALID, e.what());
   }
+  // the lookback correlations (turbulence.cpp:610-643): truncated by the initialisation, a row per cycle while this
+  // call runs
+  struct CsvScope {
+    apk_sim *s;
+    ~CsvScope() {
+      if (s->tracers) s->tracers->csv_path.clear();
+    }
+  } csv_scope{s};
+  if (s->tracers && s->tracers->lookback) s->tracers->csv_path = std::string(outdir) + "/correlations.csv";
   SIM_TRY(s, apk_sim_initialize(s));
   // the tracers next to every history row: <history file without .hst>.<row, 5 digits>.tracers.<field>.npy
   auto write_tracers = [&](HstOut &o) -> int {

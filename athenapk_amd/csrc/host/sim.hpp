@@ -127,6 +127,16 @@ struct TracerState {
   apk_tracer_geom geom{};
   long long lost = 0;
   long long steps = 0, sorts = 0;  // tracer steps taken and counting sorts run since initialisation (apk_sim_tracers_stats)
+  // apk_amd/tracer_lookback (src/pgen/turbulence.cpp:200-216, 513-647): s and sdot [12][cap] behind each set's arrays,
+  // the 26 sums behind the two counters in d_counters (one readback per cycle), a row of partial sums per workgroup
+  bool lookback = false;
+  double *d_partials = nullptr;
+  int64_t partials_cap = 0;
+  double t_lookback[APK_TRACER_N_LOOKBACK] = {0};
+  long long row_cycle = -1, row_active = 0;  // the last update: its cycle number, the particles it divided by,
+  double row_time = 0.0;                     // its time and <s>, <sdot>, corr_s[12], corr_sdot[12]
+  double row[2 + 2 * APK_TRACER_N_LOOKBACK] = {0};
+  std::string csv_path;  // apk_sim_execute: <outdir>/correlations.csv, a row per cycle (empty: no file)
 };
 
 }  // namespace apk

@@ -11,6 +11,10 @@
 // counter-based generator on the host, r(gid, n, c) = splitmix64 chained over (initial_rng_seed + gid, n, c), top 53 bits,
 // and places particle n of block gid at origin + r * block size.  Positions depend on neither the distribution of blocks
 // nor a launch shape; ids are the reference's, n_per_block * gid + n.
+//
+// Lookback histories (apk_amd/tracer_lookback; src/pgen/turbulence.cpp:200-216, 513-647): s and sdot, [12][cap] each,
+// behind the arrays of each set, allocated only with the switch on (96 B per particle without, 288 B with, GLM-MHD).
+// The host keeps t_lookback[12] and the last row; the 26 sums come back with the two counters in one copy.
 #include "sim_internal.hpp"
 
 #include <fstream>
@@ -31,9 +35,14 @@ double tracer_uniform(uint64_t key, uint64_t n, uint64_t c) {
   return (double)(u >> 11) * (1.0 / 9007199254740992.0);
 }
 
-size_t bytes_per_particle(int nf) { return sizeof(double) * (3 + nf) + sizeof(int64_t) + 2 * sizeof(int32_t); }
+constexpr int kLookback = APK_TRACER_N_LOOKBACK, kSums = APK_TRACER_N_SUMS;
 
-// the arrays of set `which` for n particles (layout: x | y | z | id | fields | block | active, each cap long)
+size_t bytes_per_particle(const TracerState &t) {
+  return sizeof(double) * (3 + t.nfields) + sizeof(int64_t) + 2 * sizeof(int32_t) + (t.lookback ? sizeof(double) * 2 * kLookback : 0);
+}
+
+// the arrays of set `which` for n particles (layout: x | y | z | id | fields | block | active, each cap long, then
+// with lookbacks s | sdot, each [12][cap])
 apk_tracer_arrays arrays_of(const TracerState &t, int which, int64_t n) {
   apk_tracer_arrays a{};
   a.n = n;
@@ -47,6 +56,12 @@ apk_tracer_arrays arrays_of(const TracerState &t, int which, int64_t n) {
   for (int f = 0; f < t.nfields; ++f) a.field[f] = p + (4 + f) * t.cap;
   a.block = reinterpret_cast<int32_t *>(p + (4 + t.nfields) * t.cap);
   a.active = a.block + t.cap;
+  if (t.lookback) {
+    a.s = p + (5 + t.nfields) * t.cap;
+    a.sdot = a.s + kLookback * t.cap;
+    a.lookback_stride = t.cap;
+    a.n_lookback = kLookback;
+  }
   return a;
 }
 
@@ -57,12 +72,20 @@ int reserve(apk_sim *s, int64_t want) {
   const int64_t cap = (std::max(want, t.cap + t.cap / 2) + 1) / 2 * 2;  // (even: the int32 arrays end on 8 bytes)
   TracerState old;  // (pointers and sizes only: what arrays_of reads)
   old.nfields = t.nfields, old.n = t.n, old.cap = t.cap, old.cur = t.cur, old.set[0] = t.set[0], old.set[1] = t.set[1];
+  old.lookback = t.lookback;
   double *fresh[2] = {nullptr, nullptr};
-  SIM_TRY(s, dev_alloc(s, "tracers", bytes_per_particle(t.nfields) * (size_t)cap, &fresh[0]));
-  const int rc = dev_alloc(s, "tracers_sorted", bytes_per_particle(t.nfields) * (size_t)cap, &fresh[1]);
+  SIM_TRY(s, dev_alloc(s, "tracers", bytes_per_particle(t) * (size_t)cap, &fresh[0]));
+  const int rc = dev_alloc(s, "tracers_sorted", bytes_per_particle(t) * (size_t)cap, &fresh[1]);
   if (rc != APK_OK) {
     dev_free(s, fresh[0]);
     return rc;
+  }
+  if (t.lookback) {  // a row of partial sums per workgroup of 256 particles (no kernel is in flight: see the sync below)
+    SIM_HIP(s, hipStreamSynchronize(hs(s)));
+    dev_free(s, t.d_partials);
+    t.d_partials = nullptr;
+    t.partials_cap = (cap + 255) / 256;
+    SIM_TRY(s, dev_alloc(s, "tracer_lookback_partials", sizeof(double) * kSums * (size_t)t.partials_cap, &t.d_partials));
   }
   t.cap = cap;
   t.set[0] = fresh[0], t.set[1] = fresh[1];
@@ -79,6 +102,10 @@ int reserve(apk_sim *s, int64_t want) {
     for (int f = 0; f < t.nfields; ++f) SIM_HIP(s, hipMemcpyAsync(to.field[f], from.field[f], nd, hipMemcpyDeviceToDevice, st));
     SIM_HIP(s, hipMemcpyAsync(to.block, from.block, nd / 2, hipMemcpyDeviceToDevice, st));
     SIM_HIP(s, hipMemcpyAsync(to.active, from.active, nd / 2, hipMemcpyDeviceToDevice, st));
+    for (int i = 0; t.lookback && i < kLookback; ++i) {
+      SIM_HIP(s, hipMemcpyAsync(to.s + i * to.lookback_stride, from.s + i * from.lookback_stride, nd, hipMemcpyDeviceToDevice, st));
+      SIM_HIP(s, hipMemcpyAsync(to.sdot + i * to.lookback_stride, from.sdot + i * from.lookback_stride, nd, hipMemcpyDeviceToDevice, st));
+    }
   }
   SIM_HIP(s, hipStreamSynchronize(hs(s)));
   dev_free(s, old.set[0]);
@@ -97,7 +124,7 @@ int owner_of(const apk_sim *s, const double x[3]) {
   return m.gid_local.at(m.Gid(bc));
 }
 
-// append particles to the device arrays (ids given), active, fields zero until the fill
+// append particles to the device arrays (ids given), active, fields zero until the fill, histories empty (zero)
 int append(apk_sim *s, const double *x, const double *y, const double *z, const int64_t *id, const int32_t *block, int64_t n) {
   TracerState &t = *s->tracers;
   if (n <= 0) return APK_OK;
@@ -114,6 +141,10 @@ int append(apk_sim *s, const double *x, const double *y, const double *z, const 
   SIM_HIP(s, hipMemcpyAsync(a.block + t.n, block, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
   SIM_HIP(s, hipMemcpyAsync(a.active + t.n, ones.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
   for (int f = 0; f < t.nfields; ++f) SIM_HIP(s, hipMemsetAsync(a.field[f] + t.n, 0, nd, st));
+  for (int i = 0; t.lookback && i < kLookback; ++i) {
+    SIM_HIP(s, hipMemsetAsync(a.s + i * a.lookback_stride + t.n, 0, nd, st));
+    SIM_HIP(s, hipMemsetAsync(a.sdot + i * a.lookback_stride + t.n, 0, nd, st));
+  }
   SIM_HIP(s, hipStreamSynchronize(st));
   t.n += n;
   return APK_OK;
@@ -156,9 +187,53 @@ int fill_particles(apk_sim *s) {
   return apk_tracers_fill(s->ctx, s->mu0(), &a, &t.geom, s->stream);
 }
 
-int read_counters(apk_sim *s, unsigned long long out[2]) {
-  SIM_HIP(s, hipMemcpyAsync(out, s->tracers->d_counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, hs(s)));
+// the two counters and, with lookbacks, the 26 sums behind them: one copy, one synchronisation
+int read_counters(apk_sim *s, unsigned long long out[2 + kSums]) {
+  const size_t words = s->tracers->lookback ? 2 + kSums : 2;
+  SIM_HIP(s, hipMemcpyAsync(out, s->tracers->d_counters, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, hs(s)));
   SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+double *lookback_sums(const TracerState &t) { return t.d_counters + 2; }
+
+// The host's part of ProblemFillTracers for the update that ran with cycle number c at time `time`
+// (turbulence.cpp:523-534, 603-641): the t_lookback cascade, highest level first, the means, and the row of the file
+int lookback_row(apk_sim *s, long long c, double time, const unsigned long long words[2 + kSums]) {
+  TracerState &t = *s->tracers;
+  for (int idx = kLookback - 1; idx >= 1; --idx)
+    if (c % (1ll << (idx - 1)) == 0) t.t_lookback[idx] = t.t_lookback[idx - 1];
+  t.t_lookback[0] = time;
+  double sums[kSums];
+  std::memcpy(sums, words + 2, sizeof sums);
+  t.row_cycle = c;
+  t.row_time = time;
+  t.row_active = (long long)t.n - t.lost;
+  const double n_active = (double)t.row_active;
+  t.row[0] = sums[2 * kLookback] / n_active;
+  t.row[1] = sums[2 * kLookback + 1] / n_active;
+  for (int q = 0; q < 2 * kLookback; ++q) t.row[2 + q] = sums[q] / n_active;
+  return APK_OK;
+}
+
+// <outdir>/correlations.csv: truncated with its header (one line; the reference's is broken over three by a misplaced
+// endl, turbulence.cpp:617-622), then a row per cycle that round-trips (the reference prints six digits)
+int lookback_csv(apk_sim *s, bool header) {
+  const TracerState &t = *s->tracers;
+  if (t.csv_path.empty() || s->rank != 0) return APK_OK;
+  FILE *f = std::fopen(t.csv_path.c_str(), header ? "w" : "a");
+  if (!f) return fail(s, APK_ERR_INVALID, "cannot write " + t.csv_path);
+  if (header) {
+    std::fprintf(f, "# cycle,time,s,sdot");
+    for (const char *var : {"corr_s", "corr_sdot", "t_lookback"})
+      for (int i = 0; i < kLookback; ++i) std::fprintf(f, ",%s[%d]", var, i);
+  } else {
+    std::fprintf(f, "%lld,%.17g", t.row_cycle, t.row_time);
+    for (double v : t.row) std::fprintf(f, ",%.17g", v);
+    for (double v : t.t_lookback) std::fprintf(f, ",%.17g", v);
+  }
+  std::fprintf(f, "\n");
+  std::fclose(f);
   return APK_OK;
 }
 
@@ -184,7 +259,17 @@ const char *kFieldNames[8] = {"rho", "pressure", "vel_x", "vel_y", "vel_z", "B_x
 
 void tracers_initialize(apk_sim *s) {
   ParameterInput &pin = s->pin;
-  if (!pin.GetOrAddBoolean("tracers", "enabled", false)) return;
+  // apk_amd/tracer_lookback: opt-in, with any problem generator (the reference: always, for problem_id = turbulence)
+  bool lookback = false;
+  if (pin.DoesParameterExist("apk_amd", "tracer_lookback")) {
+    const std::string v = pin.GetString("apk_amd", "tracer_lookback");
+    if (v != "true" && v != "false") throw std::runtime_error("apk_amd/tracer_lookback must be true or false");
+    lookback = v == "true";
+  }
+  if (!pin.GetOrAddBoolean("tracers", "enabled", false)) {
+    if (lookback) throw std::runtime_error("apk_amd/tracer_lookback = true needs tracers/enabled = true");
+    return;
+  }
   const Mesh &m = s->mesh;
   // tracers.cpp:70-71
   if (m.nx[2] <= 1) throw std::runtime_error("Tracers/swarms currently only supported/tested in 3D.");
@@ -199,6 +284,7 @@ void tracers_initialize(apk_sim *s) {
   const std::string form = pin.GetOrAddString("apk_amd", "tracer_step", "fused");
   if (form != "fused" && form != "passes") throw std::runtime_error("apk_amd/tracer_step must be fused or passes");
   t->fused = form == "fused";
+  t->lookback = lookback;
   const std::string method = pin.GetOrAddString("tracers", "initial_seed_method", "none");
   t->per_cell = pin.GetOrAddReal("tracers", "initial_num_tracers_per_cell", 0.0);
   t->rng_seed = pin.GetOrAddInteger("tracers", "initial_rng_seed", 0);
@@ -263,11 +349,12 @@ int tracers_device_setup(apk_sim *s) {
   t.nbuckets = (int)nlb * m.mb[2] + 1;
   SIM_TRY(s, dev_alloc(s, "tracer_block_origin", sizeof(double) * origin.size(), &t.d_origin));
   SIM_TRY(s, dev_alloc(s, "tracer_block_table", sizeof(int32_t) * table.size(), &t.d_table));
-  SIM_TRY(s, dev_alloc(s, "tracer_counters", 2 * sizeof(unsigned long long), &t.d_counters));
+  const size_t counter_words = t.lookback ? 2 + kSums : 2;  // (the 26 sums of the lookbacks behind the counters)
+  SIM_TRY(s, dev_alloc(s, "tracer_counters", counter_words * sizeof(unsigned long long), &t.d_counters));
   SIM_TRY(s, dev_alloc(s, "tracer_buckets", sizeof(unsigned long long) * (size_t)t.nbuckets, &t.d_buckets));
   SIM_HIP(s, hipMemcpy(t.d_origin, origin.data(), sizeof(double) * origin.size(), hipMemcpyHostToDevice));
   SIM_HIP(s, hipMemcpy(t.d_table, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
-  SIM_HIP(s, hipMemset(t.d_counters, 0, 2 * sizeof(unsigned long long)));
+  SIM_HIP(s, hipMemset(t.d_counters, 0, counter_words * sizeof(unsigned long long)));
   g.block_origin = t.d_origin;
   g.block_table = reinterpret_cast<const int32_t *>(t.d_table);
   return APK_OK;
@@ -283,10 +370,25 @@ int tracers_seed_initial(apk_sim *s) {
   t.next_id = 0;
   t.steps = t.sorts = 0;
   SIM_HIP(s, hipMemsetAsync(t.d_counters, 0, 2 * sizeof(unsigned long long), hs(s)));
+  if (t.lookback) {  // empty histories (append zeroes what it adds), no row yet, a fresh file
+    for (double &v : t.t_lookback) v = 0.0;
+    for (double &v : t.row) v = 0.0;
+    t.row_cycle = -1, t.row_active = 0, t.row_time = 0.0;
+    SIM_TRY(s, lookback_csv(s, true));
+  }
   if (t.seed_method != APK_TRACER_SEED_RANDOM_PER_BLOCK) return APK_OK;
   SIM_TRY(s, append(s, t.hx.data(), t.hy.data(), t.hz.data(), t.hid.data(), t.hblock.data(), (int64_t)t.hx.size()));
   SIM_TRY(s, sort_particles(s));
-  return fill_particles(s);  // tracers.cpp:173-186
+  SIM_TRY(s, fill_particles(s));  // tracers.cpp:173-186
+  if (!t.lookback || t.n == 0) return APK_OK;
+  // ... which end with ProblemFillTracers at cycle 0 with the sim's dt: every level shifts, s[0] = ln rho of the seeded
+  // state.  The first cycle runs with cycle number 0 again and truncates the file, so this call writes no row; what it
+  // leaves is s[1] (and t_lookback[1]) of the first row.
+  const apk_tracer_arrays a = arrays_of(t, t.cur, t.n);
+  SIM_TRY(s, apk_tracers_lookback(s->ctx, &a, 0, s->dt, t.d_partials, t.partials_cap, lookback_sums(t), s->stream));
+  unsigned long long c[2 + kSums] = {0};
+  SIM_TRY(s, read_counters(s, c));
+  return lookback_row(s, 0, s->time, c);
 }
 
 int tracers_cycle(apk_sim *s, double dt) {
@@ -298,17 +400,29 @@ int tracers_cycle(apk_sim *s, double dt) {
   SIM_TRY(s, state.complete());
   const apk_tracer_arrays a = arrays_of(t, t.cur, t.n);
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(t.d_counters);
-  if (t.fused) {
+  // the lookbacks run with the cycle being executed and the time at its start (tm.ncycle, tm.time of the task):
+  // apk_sim_step increments both after this call
+  const long long cycle = s->ncycle;
+  if (t.fused && t.lookback) {
+    SIM_TRY(s, apk_tracers_step_fused_lookback(s->ctx, s->mu0(), &a, &t.geom, dt, counters, cycle, t.d_partials, t.partials_cap,
+                                               lookback_sums(t), s->stream));
+  } else if (t.fused) {
     SIM_TRY(s, apk_tracers_step_fused(s->ctx, s->mu0(), &a, &t.geom, dt, counters, s->stream));
   } else {
     SIM_TRY(s, apk_tracers_advect(s->ctx, s->mu0(), &a, &t.geom, dt, s->stream));
     SIM_TRY(s, apk_tracers_reown(s->ctx, &a, &t.geom, counters, s->stream));
     SIM_TRY(s, apk_tracers_fill(s->ctx, s->mu0(), &a, &t.geom, s->stream));
+    if (t.lookback)  // the reference's task order: ProblemFillTracers after FillTracers (hydro_driver.cpp:654-658)
+      SIM_TRY(s, apk_tracers_lookback(s->ctx, &a, cycle, dt, t.d_partials, t.partials_cap, lookback_sums(t), s->stream));
   }
   t.steps += 1;
-  unsigned long long c[2] = {0, 0};
+  unsigned long long c[2 + kSums] = {0};
   SIM_TRY(s, read_counters(s, c));
   t.lost = (long long)c[0];
+  if (t.lookback) {
+    SIM_TRY(s, lookback_row(s, cycle, s->time, c));
+    SIM_TRY(s, lookback_csv(s, false));
+  }
   if (c[1] != 0ull) {  // ownership changed: restore the order by (block, k-plane)
     SIM_HIP(s, hipMemsetAsync(counters + 1, 0, sizeof(unsigned long long), hs(s)));
     SIM_TRY(s, sort_particles(s));
@@ -353,6 +467,8 @@ void tracers_free(apk_sim *s) {
   dev_free(s, t.d_table);
   dev_free(s, t.d_counters);
   dev_free(s, t.d_buckets);
+  dev_free(s, t.d_partials);
+  t.d_partials = nullptr;
   t.set[0] = t.set[1] = t.d_origin = t.d_table = t.d_counters = t.d_buckets = nullptr;
 }
 
@@ -443,6 +559,38 @@ int apk_sim_tracers_seed(apk_sim *s, const double *x, const double *y, const dou
   t.next_id += n;
   SIM_TRY(s, sort_particles(s));
   return fill_particles(s);
+}
+
+int apk_sim_tracer_lookback_options(const apk_sim *s, int *enabled, int *n_lookback) {
+  if (!s) return APK_ERR_INVALID;
+  if (enabled) *enabled = s->tracers && s->tracers->lookback ? 1 : 0;
+  if (n_lookback) *n_lookback = kLookback;
+  return APK_OK;
+}
+
+int apk_sim_tracer_lookbacks_read(apk_sim *s, int which, double *out) {
+  if (!s || s->host_only || !out || which < 0 || which > 1) return APK_ERR_INVALID;
+  if (!s->tracers || !s->tracers->lookback) return fail(s, APK_ERR_INVALID, "tracer lookbacks are not enabled (apk_amd/tracer_lookback = true)");
+  TracerState &t = *s->tracers;
+  if (t.n == 0) return APK_OK;
+  const apk_tracer_arrays a = arrays_of(t, t.cur, t.n);
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  SIM_HIP(s, hipMemcpy2D(out, sizeof(double) * (size_t)t.n, which == 0 ? a.s : a.sdot, sizeof(double) * (size_t)a.lookback_stride,
+                         sizeof(double) * (size_t)t.n, kLookback, hipMemcpyDeviceToHost));
+  return APK_OK;
+}
+
+int apk_sim_tracer_correlations(const apk_sim *s, long long *cycle, double *time, long long *n_active, double *row) {
+  if (!s || !s->tracers || !s->tracers->lookback) return APK_ERR_INVALID;
+  const TracerState &t = *s->tracers;
+  if (cycle) *cycle = t.row_cycle;
+  if (time) *time = t.row_time;
+  if (n_active) *n_active = t.row_active;
+  if (row) {
+    std::memcpy(row, t.row, sizeof t.row);
+    std::memcpy(row + 2 + 2 * kLookback, t.t_lookback, sizeof t.t_lookback);
+  }
+  return APK_OK;
 }
 
 int apk_sim_tracers_step(apk_sim *s, double dt) {

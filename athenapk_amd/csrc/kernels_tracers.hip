@@ -4,7 +4,10 @@
 //   Tracers::FillTracers        src/tracers/tracers.cpp:249-308   rho, v, p (and B) interpolated at the new position
 // as three kernels (apk_tracers_advect, apk_tracers_reown, apk_tracers_fill) and as ONE (apk_tracers_step_fused): one lane
 // owns one particle and does both gathers in the same launch.  All four call the same device functions, so that the two
-// forms agree bit for bit in the strict (-ffp-contract=off) build.
+// forms agree bit for bit in the strict (-ffp-contract=off) build.  With lookback histories a fourth task,
+//   turbulence::ProblemFillTracers  src/pgen/turbulence.cpp:557-584  s = ln rho and sdot at 12 lookback levels, 26 sums
+// as a kernel of its own (apk_tracers_lookback) and inside the fused step (apk_tracers_step_fused_lookback), again
+// through one device function.
 //
 // Interpolation: trilinear on cell centres (Parthenon's interpolation::cent::linear).  Per direction, with x0 the lower
 // interior face of the block and il counted from the first interior cell,
@@ -22,6 +25,20 @@
 //                     once, 8 variables x 8 B = 64 B per particle (1/8 per cell: 512 B), the rest are L2 hits
 // so 216 B per particle at one per cell (hydro: 5 fields, 40 B of mesh, 168 B).  The three-kernel form reads and writes
 // x, y, z, block and active once more in each of its extra kernels: + 28 + 24 (advect) + 32 (re-own) = 84 B.
+//
+// Lookback histories (apk_amd/tracer_lookback; src/pgen/turbulence.cpp:513-647), the floor again and not a measurement:
+//   histories         read s[12] and sdot[12] = 24 loads                                                      192 B
+//                     written: level 0 and the levels that shift this cycle.  Level i >= 1 shifts when the cycle number
+//                     is a multiple of 2^(i-1): on average 1 + 1/2 + 1/4 + ... ~ 2 of them, so about 3 levels x 2 arrays
+//                     x 8 B                                                                                   ~48-64 B
+//                     (192 B if every level were stored; a level that does not shift is read, never written)
+//   partial sums      26 doubles per workgroup of 256 particles                                                 0.8 B
+// so about 250 B on top of the step; the standalone kernel (the passes, and the seed-time call) reads rho and active
+// again, + 12 B.  The counting sort carries all 24 values: + 192 B read and 192 B written per sort.
+// The sums use no atomic: every lane forms a term (exact zeros for inactive and out-of-range lanes), the wave adds it
+// with the shuffle pattern of kernels_block.hip (wave_sum), lane 0 of the four waves leaves it in LDS, and 26 lanes add
+// the four in wave order and store the workgroup's row of partials[nworkgroups][26] with ordinary vector stores;
+// tracers_lookback_sum_kernel (26 workgroups, one per sum, a stride loop over the rows) adds the rows.
 //
 // Locality: apk_tracers_sort is a counting sort by (block, interior k-plane) -- histogram, one-workgroup scan, scatter
 // through atomics on the bucket cursors (the order inside a bucket is arbitrary: no result depends on it, the accessors
@@ -99,15 +116,70 @@ APK_DEV bool tracer_reown(const apk_tracer_geom &g, double x[3], int &b) {
   return true;
 }
 
-APK_DEV void tracer_fill(const PackView &pv, const apk_tracer_geom &g, const apk_tracer_arrays &a, int64_t n, int b, const double x[3]) {
+// returns the density it stored (the lookback update of the fused step takes it from the register)
+APK_DEV double tracer_fill(const PackView &pv, const apk_tracer_geom &g, const apk_tracer_arrays &a, int64_t n, int b, const double x[3]) {
   const TracerInterp t = tracer_locate(pv, g, b, x[0], x[1], x[2]);
   const double *__restrict__ w = pv.blocks[b].prim;
   // field order: rho, pressure, vel_x, vel_y, vel_z, B_x, B_y, B_z
-  a.field[0][n] = tracer_gather(w + IDN * pv.sn, t, pv.sj, pv.sk);
+  const double rho = tracer_gather(w + IDN * pv.sn, t, pv.sj, pv.sk);
+  a.field[0][n] = rho;
   a.field[1][n] = tracer_gather(w + IPR * pv.sn, t, pv.sj, pv.sk);
   for (int d = 0; d < 3; ++d) a.field[2 + d][n] = tracer_gather(w + (IV1 + d) * pv.sn, t, pv.sj, pv.sk);
   if (a.nfields == 8)
     for (int d = 0; d < 3; ++d) a.field[5 + d][n] = tracer_gather(w + (IB1 + d) * pv.sn, t, pv.sj, pv.sk);
+  return rho;
+}
+
+// ---- lookback histories (turbulence.cpp:557-584) ---------------------------------------------------------------------
+constexpr int NLB = APK_TRACER_N_LOOKBACK, NSUMS = APK_TRACER_N_SUMS;
+
+// The update of one active particle: s and sd come back holding the particle's new levels.  shift: bit idx set = level
+// idx takes level idx - 1 this cycle -- a kernel argument, so the branches are scalar; a level that does not shift is
+// read and not written.
+APK_DEV void tracer_lookback_update(const apk_tracer_arrays &a, int64_t n, unsigned shift, double rho, double dt,
+                                    double (&s)[NLB], double (&sd)[NLB]) {
+  double *__restrict__ ps = a.s + n;
+  double *__restrict__ pd = a.sdot + n;
+  const int64_t L = a.lookback_stride;
+#pragma unroll
+  for (int i = 0; i < NLB; ++i) s[i] = ps[i * L], sd[i] = pd[i * L];
+#pragma unroll
+  for (int i = NLB - 1; i >= 1; --i)  // highest level first: a level receives the OLD value of the level below it
+    if ((shift >> i) & 1u) {
+      s[i] = s[i - 1], sd[i] = sd[i - 1];
+      ps[i * L] = s[i], pd[i * L] = sd[i];
+    }
+  s[0] = log(rho);
+  sd[0] = (s[0] - s[1]) / dt;
+  ps[0] = s[0], pd[0] = sd[0];
+}
+
+// The workgroup's 26 partial sums of s[0] s[i], sd[0] sd[i], s[0], sd[0] into row[26]; a lane without an active particle
+// passes zeros.  Every lane of the workgroup must call it.
+APK_DEV void tracer_lookback_partials(const double (&s)[NLB], const double (&sd)[NLB], double *__restrict__ row) {
+  __shared__ double part[4][NSUMS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < NSUMS; ++q) {
+    const double term = q < NLB ? s[0] * s[q] : q < 2 * NLB ? sd[0] * sd[q - NLB] : q == 2 * NLB ? s[0] : sd[0];
+    double v = term;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) part[wave][q] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NSUMS) {
+    const int q = threadIdx.x;
+    row[q] = ((part[0][q] + part[1][q]) + part[2][q]) + part[3][q];
+  }
+}
+
+// the 12-bit shift mask of a cycle number (turbulence.cpp:562-571): level idx shifts when cycle % 2^(idx-1) == 0
+unsigned tracer_shift_mask(long long cycle) {
+  unsigned m = 0;
+  for (int idx = 1; idx < NLB; ++idx)
+    if (cycle % (1ll << (idx - 1)) == 0) m |= 1u << idx;
+  return m;
 }
 
 // particle of this lane: grid x, 64-bit (more particles than 65535 x 256 must survive)
@@ -151,10 +223,11 @@ __global__ void __launch_bounds__(256) tracers_fill_kernel(PackView pv, apk_trac
   tracer_fill(pv, g, a, n, a.block[n], x);
 }
 
-__global__ void __launch_bounds__(256) tracers_step_fused_kernel(PackView pv, apk_tracer_geom g, apk_tracer_arrays a, double dt,
-                                                                 unsigned long long *counters) {
-  const int64_t n = tracer_index();
-  if (n >= a.n || !a.active[n]) return;
+// one particle through advect, re-own and fill; false when the lane has no particle, an inactive one or one lost in this
+// step; rho: the density the fill stored
+APK_DEV bool tracer_step_fused(const PackView &pv, const apk_tracer_geom &g, const apk_tracer_arrays &a, double dt,
+                               unsigned long long *counters, int64_t n, double &rho) {
+  if (n >= a.n || !a.active[n]) return false;
   double x[3] = {a.x[n], a.y[n], a.z[n]};
   const double vp[3] = {a.field[2][n], a.field[3][n], a.field[4][n]};
   const int b0 = a.block[n];
@@ -166,11 +239,47 @@ __global__ void __launch_bounds__(256) tracers_step_fused_kernel(PackView pv, ap
   if (!kept) {  // (a lost particle keeps the position it left with, unwrapped, as the passes leave it)
     a.x[n] = xa[0], a.y[n] = xa[1], a.z[n] = xa[2];
     a.active[n] = 0;
-    return;
+    return false;
   }
   a.x[n] = x[0], a.y[n] = x[1], a.z[n] = x[2];
   a.block[n] = b;
-  tracer_fill(pv, g, a, n, b, x);
+  rho = tracer_fill(pv, g, a, n, b, x);
+  return true;
+}
+
+// LOOKBACK: the histories' update and the workgroup's partial sums in the same launch (every lane stays to the end)
+template <bool LOOKBACK>
+__global__ void __launch_bounds__(256) tracers_step_fused_kernel(PackView pv, apk_tracer_geom g, apk_tracer_arrays a, double dt,
+                                                                 unsigned long long *counters, unsigned shift, double *partials) {
+  const int64_t n = tracer_index();
+  double rho = 1.0;
+  const bool live = tracer_step_fused(pv, g, a, dt, counters, n, rho);
+  if constexpr (LOOKBACK) {
+    double s[NLB] = {0}, sd[NLB] = {0};
+    if (live) tracer_lookback_update(a, n, shift, rho, dt, s, sd);
+    tracer_lookback_partials(s, sd, partials + (int64_t)blockIdx.x * NSUMS);
+  }
+}
+
+// the update alone, on the rho the fill stored (the passes' fourth kernel, and the seed-time call)
+__global__ void __launch_bounds__(256) tracers_lookback_kernel(apk_tracer_arrays a, double dt, unsigned shift, double *partials) {
+  const int64_t n = tracer_index();
+  double s[NLB] = {0}, sd[NLB] = {0};
+  if (n < a.n && a.active[n]) tracer_lookback_update(a, n, shift, a.field[0][n], dt, s, sd);
+  tracer_lookback_partials(s, sd, partials + (int64_t)blockIdx.x * NSUMS);
+}
+
+// sums26[q] = sum over the rows of partials[nrows][26]: workgroup q, lanes stride over the rows, then wave and LDS
+__global__ void __launch_bounds__(256) tracers_lookback_sum_kernel(const double *__restrict__ partials, int64_t nrows, double *sums26) {
+  __shared__ double part[4];
+  const int q = blockIdx.x;
+  double v = 0.0;
+  for (int64_t r = threadIdx.x; r < nrows; r += 256) v += partials[r * NSUMS + q];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) sums26[q] = ((part[0] + part[1]) + part[2]) + part[3];
 }
 
 // ---- counting sort by (block, interior k-plane) ----------------------------------------------------------------------
@@ -227,6 +336,11 @@ __global__ void __launch_bounds__(256) tracers_scatter_kernel(PackView pv, apk_t
   out.block[m] = a.block[n];
   out.active[m] = a.active[n];
   for (int f = 0; f < a.nfields; ++f) out.field[f][m] = a.field[f][n];
+  if (a.s)
+    for (int i = 0; i < NLB; ++i) {
+      out.s[i * out.lookback_stride + m] = a.s[i * a.lookback_stride + n];
+      out.sdot[i * out.lookback_stride + m] = a.sdot[i * a.lookback_stride + n];
+    }
 }
 
 hipStream_t tr_stream(apk_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
@@ -239,6 +353,8 @@ int tracer_check(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *a, c
     for (int f = 0; f < a->nfields; ++f)
       if (!a->field[f]) return set_err(ctx, APK_ERR_INVALID, "tracers: null field array");
   }
+  if (a->s && (!a->sdot || a->n_lookback != NLB || a->lookback_stride < a->n))
+    return set_err(ctx, APK_ERR_INVALID, "tracers: lookback histories need sdot, 12 levels and a stride >= n");
   if (!g->block_origin || !g->block_table) return set_err(ctx, APK_ERR_INVALID, "tracers: geometry without its tables");
   if (md) {
     const PackView &v = md->view;
@@ -249,6 +365,18 @@ int tracer_check(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *a, c
     for (const apk_block_desc &b : md->h_blocks)
       if (!b.prim) return set_err(ctx, APK_ERR_INVALID, "tracers: pack without primitives");
   }
+  return APK_OK;
+}
+
+// what the lookback update reads of the arrays, and its scratch: one row of partials per workgroup of 256 particles
+int lookback_check(apk_ctx *ctx, const apk_tracer_arrays *a, long long cycle, const double *partials, long long npartials_cap,
+                   const double *sums26) {
+  if (!ctx || !a || a->n < 0 || cycle < 0 || !sums26) return set_err(ctx, APK_ERR_INVALID, "tracers lookback: bad argument");
+  if (!a->s || !a->sdot || a->n_lookback != NLB || a->lookback_stride < a->n)
+    return set_err(ctx, APK_ERR_INVALID, "tracers lookback: histories need s, sdot, 12 levels and a stride >= n");
+  if (a->n > 0 && (!a->active || !a->field[0])) return set_err(ctx, APK_ERR_INVALID, "tracers lookback: null particle array");
+  if (a->n > 0 && (!partials || npartials_cap < (a->n + 255) / 256))
+    return set_err(ctx, APK_ERR_INVALID, "tracers lookback: partials must hold a row per 256 particles");
   return APK_OK;
 }
 
@@ -314,7 +442,31 @@ int apk_tracers_step_fused(apk_ctx *ctx, const apk_pack *md, const apk_tracer_ar
   if (rc != APK_OK) return rc;
   if (!counters) return set_err(ctx, APK_ERR_INVALID, "apk_tracers_step_fused: no counters");
   if (a->n == 0) return APK_OK;
-  APK_TRACER_LAUNCH(ctx, tracers_step_fused_kernel, a->n, stream, md->view, *g, *a, dt, counters);
+  APK_TRACER_LAUNCH(ctx, tracers_step_fused_kernel<false>, a->n, stream, md->view, *g, *a, dt, counters, 0u, (double *)nullptr);
+  return APK_OK;
+}
+
+int apk_tracers_lookback(apk_ctx *ctx, const apk_tracer_arrays *a, long long cycle, double dt, double *partials,
+                         long long npartials_cap, double *sums26, apk_stream_t stream) {
+  const int rc = lookback_check(ctx, a, cycle, partials, npartials_cap, sums26);
+  if (rc != APK_OK) return rc;
+  if (a->n > 0) APK_TRACER_LAUNCH(ctx, tracers_lookback_kernel, a->n, stream, *a, dt, tracer_shift_mask(cycle), partials);
+  APK_TRACER_LAUNCH(ctx, tracers_lookback_sum_kernel, (int64_t)256 * NSUMS, stream, partials, (a->n + 255) / 256, sums26);
+  return APK_OK;
+}
+
+int apk_tracers_step_fused_lookback(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *a, const apk_tracer_geom *g,
+                                    double dt, unsigned long long *counters, long long cycle, double *partials,
+                                    long long npartials_cap, double *sums26, apk_stream_t stream) {
+  if (!md) return set_err(ctx, APK_ERR_INVALID, "apk_tracers_step_fused_lookback: bad argument");
+  int rc = tracer_check(ctx, md, a, g);
+  if (rc != APK_OK) return rc;
+  if (!counters) return set_err(ctx, APK_ERR_INVALID, "apk_tracers_step_fused_lookback: no counters");
+  if ((rc = lookback_check(ctx, a, cycle, partials, npartials_cap, sums26)) != APK_OK) return rc;
+  if (a->n > 0)
+    APK_TRACER_LAUNCH(ctx, tracers_step_fused_kernel<true>, a->n, stream, md->view, *g, *a, dt, counters, tracer_shift_mask(cycle),
+                      partials);
+  APK_TRACER_LAUNCH(ctx, tracers_lookback_sum_kernel, (int64_t)256 * NSUMS, stream, partials, (a->n + 255) / 256, sums26);
   return APK_OK;
 }
 

@@ -658,8 +658,38 @@ class Simulation(_FmftHost, _MeshView):
         return _tracers_read(self.lib, self.h, names if fields is None else list(fields))
 
     def tracers_step(self, dt):
-        """the tracer step alone on the current state (what step() runs after the last stage)"""
+        """the tracer step alone on the current state (what step() runs after the last stage); with lookbacks, their
+        update with the sim's current cycle number and time"""
         self._check(self.lib.apk_sim_tracers_step(self.h, float(dt)))
+
+    def tracer_lookback_options(self):
+        """apk_amd/tracer_lookback as parsed (see HostPlan.tracer_lookback_options)"""
+        return _tracer_lookback_options(self.lib, self.h)
+
+    def tracer_lookbacks(self):
+        """the lookback histories sorted by id like tracers(): id, s and sdot [n][12], level 0 the current cycle and
+        level i the value of 2^(i-1) cycles' spacing (turbulence.cpp:200-216)"""
+        n = sum(self.tracers_count())
+        raw_id = np.zeros(n, dtype=np.int64)
+        self._check(self.lib.apk_sim_tracers_read(self.h, 3, raw_id.ctypes.data_as(C.c_void_p)))
+        order = np.argsort(raw_id, kind="stable")
+        out = {"id": raw_id[order]}
+        for which, name in enumerate(("s", "sdot")):
+            a = np.zeros((L.TRACER_N_LOOKBACK, n))
+            self._check(self.lib.apk_sim_tracer_lookbacks_read(self.h, which, a.ctypes.data_as(L.c_dp)))
+            out[name] = np.ascontiguousarray(a.T[order])
+        return out
+
+    def tracer_correlations(self):
+        """the row of the last lookback update (one line of correlations.csv): cycle, time, n_active, the means s and
+        sdot, corr_s[12] = <s(t) s(t - tau_i)>, corr_sdot[12] and t_lookback[12]; cycle = -1 before any update"""
+        cycle, n_active, time = C.c_longlong(0), C.c_longlong(0), C.c_double(0.0)
+        row = (C.c_double * (2 + 3 * L.TRACER_N_LOOKBACK))()
+        self._check(self.lib.apk_sim_tracer_correlations(self.h, C.byref(cycle), C.byref(time), C.byref(n_active), row))
+        v = np.array(row[:])
+        n = L.TRACER_N_LOOKBACK
+        return {"cycle": cycle.value, "time": time.value, "n_active": n_active.value, "s": v[0], "sdot": v[1],
+                "corr_s": v[2:2 + n], "corr_sdot": v[2 + n:2 + 2 * n], "t_lookback": v[2 + 2 * n:]}
 
 
 def _diffusion_options(lib, h):
@@ -713,6 +743,14 @@ def _tracers_options(lib, h):
     return {"enabled": bool(o.enabled), "initial_seed_method": seed, "tracer_step": "fused" if o.fused else "passes",
             "nfields": o.nfields, "initial_num_tracers_per_cell": o.num_tracers_per_cell, "initial_rng_seed": o.rng_seed,
             "num_tracers_per_block": o.num_tracers_per_block}
+
+
+def _tracer_lookback_options(lib, h):
+    en, n = C.c_int(0), C.c_int(0)
+    rc = lib.apk_sim_tracer_lookback_options(h, C.byref(en), C.byref(n))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_tracer_lookback_options")
+    return {"enabled": bool(en.value), "n_lookback": n.value}
 
 
 def _tracers_read(lib, h, names):
@@ -799,6 +837,10 @@ class HostPlan(_FmftHost, _MeshView):
         """<tracers> as parsed: enabled, initial_seed_method, initial_num_tracers_per_cell, initial_rng_seed,
         num_tracers_per_block, nfields (5, or 8 with GLM-MHD) and apk_amd/tracer_step"""
         return _tracers_options(self.lib, self.h)
+
+    def tracer_lookback_options(self):
+        """apk_amd/tracer_lookback as parsed: enabled, and n_lookback (12 levels: 0, 1, 2, 4, ... 1024 cycles)"""
+        return _tracer_lookback_options(self.lib, self.h)
 
     def seeded_tracers(self):
         """what tracers/initial_seed_method = random_per_block seeds on this rank (drawn on the host): x, y, z, id, block

@@ -378,6 +378,29 @@ def CalcDiffFluxes(md, cfg):
     _check(ctx.lib.apk_calc_diff_fluxes(ctx.h, md.h, C.byref(cfg), _stream()), ctx.lib, ctx.h)
 
 
+def TracersLookback(ctx, rho, active, s, sdot, cycle, dt):
+    """the device part of turbulence::ProblemFillTracers -- src/pgen/turbulence.cpp:557-584 -- for cycle number `cycle`
+    on torch tensors: rho [n] float64, active [n] int32, s and sdot [12][n] float64 (updated in place).  Returns the 26
+    sums over the active particles as a float64 tensor: corr_s[12], corr_sdot[12], sum s[0], sum sdot[0] (not divided by
+    their number)."""
+    n = rho.numel()
+    for a in (rho, active, s, sdot):
+        assert a.is_cuda and a.is_contiguous()
+    assert rho.dtype == torch.float64 and active.dtype == torch.int32 and active.numel() == n
+    assert s.dtype == sdot.dtype == torch.float64 and tuple(s.shape) == tuple(sdot.shape) == (L.TRACER_N_LOOKBACK, n)
+    arr = L.TracerArrays()
+    arr.n, arr.nfields = n, 5
+    arr.active = active.data_ptr()
+    arr.field[0] = rho.data_ptr()
+    arr.s, arr.sdot, arr.lookback_stride, arr.n_lookback = s.data_ptr(), sdot.data_ptr(), n, L.TRACER_N_LOOKBACK
+    rows = (n + 255) // 256
+    partials = torch.empty((max(rows, 1), L.TRACER_N_SUMS), dtype=torch.float64, device=rho.device)
+    sums = torch.empty(L.TRACER_N_SUMS, dtype=torch.float64, device=rho.device)
+    _check(ctx.lib.apk_tracers_lookback(ctx.h, C.byref(arr), int(cycle), float(dt), partials.data_ptr(), rows,
+                                        sums.data_ptr(), _stream()), ctx.lib, ctx.h)
+    return sums
+
+
 def EstimateDiffusionTimestep(md, cfg, cfl_diff):
     """the diffusive limit of Hydro::EstimateTimestep -- src/hydro/hydro.cpp:935-949"""
     ctx = md.ctx

@@ -194,7 +194,8 @@ class RegionInfo(C.Structure):
 
 class TracerArrays(C.Structure):
     _fields_ = [("n", C.c_int64), ("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("id", C.c_void_p),
-                ("block", C.c_void_p), ("active", C.c_void_p), ("field", C.c_void_p * 8), ("nfields", C.c_int)]
+                ("block", C.c_void_p), ("active", C.c_void_p), ("field", C.c_void_p * 8), ("nfields", C.c_int),
+                ("s", C.c_void_p), ("sdot", C.c_void_p), ("lookback_stride", C.c_int64), ("n_lookback", C.c_int)]
 
 
 class TracerGeom(C.Structure):
@@ -203,6 +204,8 @@ class TracerGeom(C.Structure):
                 ("block_origin", C.c_void_p), ("block_table", C.c_void_p)]
 
 
+TRACER_N_LOOKBACK = 12  # APK_TRACER_N_LOOKBACK
+TRACER_N_SUMS = 26      # APK_TRACER_N_SUMS: corr_s[12], corr_sdot[12], sum s, sum sdot
 TRACER_SEED = {"none": 0, "random_per_block": 1, "user": 2}
 # apk_sim_tracers_read: field number and numpy dtype of every array
 TRACER_FIELDS = (("x", "f8"), ("y", "f8"), ("z", "f8"), ("id", "i8"), ("block", "i4"), ("active", "i4"), ("rho", "f8"),
@@ -311,6 +314,8 @@ def _signatures():
         "apk_tracers_fill": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), vp]),
         "apk_tracers_step_fused": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), d, vp, vp]),
         "apk_tracers_sort": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerArrays), C.POINTER(TracerGeom), vp, i, vp]),
+        "apk_tracers_lookback": (i, [vp, C.POINTER(TracerArrays), ll, d, vp, ll, vp, vp]),
+        "apk_tracers_step_fused_lookback": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), d, vp, ll, vp, ll, vp, vp]),
         "apk_kernel_timing_enable": (i, [vp, i]),
         "apk_kernel_timing_read": (i, [vp, i, c_dp, C.POINTER(ll)]),
         # apk_host.h
@@ -357,6 +362,9 @@ def _signatures():
         "apk_sim_tracers_read": (i, [vp, i, vp]),
         "apk_sim_tracers_seed": (i, [vp, c_dp, c_dp, c_dp, ll]),
         "apk_sim_tracers_step": (i, [vp, d]),
+        "apk_sim_tracer_lookback_options": (i, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "apk_sim_tracer_lookbacks_read": (i, [vp, i, c_dp]),
+        "apk_sim_tracer_correlations": (i, [vp, C.POINTER(ll), c_dp, C.POINTER(ll), c_dp]),
         "apk_sim_block_location": (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int * 3)]),
         "apk_sim_block_ptr": (vp, [vp, i, i]),
         "apk_sim_gather": (i, [vp, i, c_dp]),

@@ -781,7 +781,11 @@ int apk_history_user_reldivb(apk_ctx *ctx, const apk_pack *md, double B0, double
  * One rank-wide structure of arrays in DEVICE memory: positions, id, the index of the owning block in the pack, an
  * active flag (0 once the particle has left through a non-periodic boundary) and the fields FillTracers interpolates
  * (tracers.cpp:64-85), in this order: rho, pressure, vel_x, vel_y, vel_z and, with GLM-MHD (nfields = 8), B_x, B_y,
- * B_z. */
+ * B_z.  s, sdot: the lookback histories of s = ln rho and ds/dt (src/pgen/turbulence.cpp:200-216), structure of arrays
+ * [n_lookback][lookback_stride] with the level outermost, level i holding the value of 2^(i-1) cycles' spacing (level 0:
+ * the current cycle); s == NULL means "no histories", and every entry point then does what it does without them. */
+#define APK_TRACER_N_LOOKBACK 12 /* turbulence.cpp:204: 0, 1, 2, 4, ... 1024 cycles */
+#define APK_TRACER_N_SUMS 26     /* corr_s[12], corr_sdot[12], sum s, sum sdot */
 typedef struct apk_tracer_arrays {
   int64_t n;
   double *x, *y, *z;
@@ -790,6 +794,9 @@ typedef struct apk_tracer_arrays {
   int32_t *active;
   double *field[8];
   int nfields; /* 5 or 8 */
+  double *s, *sdot;
+  int64_t lookback_stride; /* >= n */
+  int n_lookback;          /* APK_TRACER_N_LOOKBACK when s != NULL */
 } apk_tracer_arrays;
 /* The uniform block grid the particles live on.  block_origin: DEVICE array [nblocks][3], the lower interior face of
  * every block of the pack; block_table: DEVICE array [nb[2]][nb[1]][nb[0]], block coordinates to index in the pack;
@@ -826,6 +833,22 @@ int apk_tracers_step_fused(apk_ctx *ctx, const apk_pack *md, const apk_tracer_ar
  * words.  The order inside a bucket is arbitrary. */
 int apk_tracers_sort(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *tracers, const apk_tracer_arrays *out,
                      const apk_tracer_geom *geom, unsigned long long *buckets, int nbuckets, apk_stream_t stream);
+/* Replaces the device part of turbulence::ProblemFillTracers (src/pgen/turbulence.cpp:557-584) for cycle number
+ * `cycle` >= 0: per active particle, level idx = 11 ... 1 of s and sdot takes the value of level idx - 1 when
+ * cycle % 2^(idx-1) == 0 (a level that does not shift is read, not written), then s[0] = log(rho) of field[0] and
+ * sdot[0] = (s[0] - s[1]) / dt; and the sums over active particles, without atomics: every workgroup of 256 particles
+ * writes its 26 partial sums to partials[workgroup][26] (DEVICE scratch of npartials_cap rows >= (n + 255) / 256), and a
+ * second kernel adds the rows into sums26 (DEVICE): [0..11] sum s[0] s[i], [12..23] sum sdot[0] sdot[i], [24] sum s[0],
+ * [25] sum sdot[0].  NOT divided by the number of active particles (turbulence.cpp:605-608 is the caller's).  Reads of
+ * `tracers` only n, active, field[0] and the histories.  Does not synchronise. */
+int apk_tracers_lookback(apk_ctx *ctx, const apk_tracer_arrays *tracers, long long cycle, double dt, double *partials,
+                         long long npartials_cap, double *sums26, apk_stream_t stream);
+/* apk_tracers_step_fused and apk_tracers_lookback in ONE launch plus the small summing kernel (tracers.cpp:189-308,
+ * hydro_driver.cpp:615-660 and turbulence.cpp:557-584): the update uses the rho the fill just computed.  tracers->s
+ * must not be NULL.  Bit for bit what the separate calls leave in the particle arrays in the -ffp-contract=off build. */
+int apk_tracers_step_fused_lookback(apk_ctx *ctx, const apk_pack *md, const apk_tracer_arrays *tracers,
+                                    const apk_tracer_geom *geom, double dt, unsigned long long *counters, long long cycle,
+                                    double *partials, long long npartials_cap, double *sums26, apk_stream_t stream);
 
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
@@ -845,7 +868,7 @@ enum apk_timing_slot {
   APK_T_FUSED_DC_X1 = 9,  /* the three fused sweeps when the stage reconstructs with donor */
   APK_T_FUSED_DC_X2 = 10, /* cell (VL2 predictor, hydro.cpp:457-463); slots 0-2 then hold   */
   APK_T_FUSED_DC_X3 = 11, /* only the high-order stages                                    */
-  APK_T_TRACERS = 12,     /* tracer particles: advect, re-own, fill (or the fused step) */
+  APK_T_TRACERS = 12,     /* tracer particles: advect, re-own, fill (or the fused step), lookbacks */
   APK_T_TRACER_SORT = 13, /* ... and their counting sort (memset, histogram, scan, scatter) */
   APK_T_COUNT = 14
 };

@@ -208,7 +208,7 @@ int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int
  * Keys (tracers.cpp:43-93, 102-118): enabled (default false), initial_seed_method = none | random_per_block | user,
  * initial_num_tracers_per_cell, initial_rng_seed; and apk_amd/tracer_step = fused (default) | passes.  Refused at
  * creation: nx3 == 1, parthenon/mesh/refinement != none, more than one rank, nghost < 2, an unknown seed method,
- * random_per_block with a per-block count <= 0.  One rank, uniform meshes, no restart, no turbulence lookbacks.
+ * random_per_block with a per-block count <= 0.  One rank, uniform meshes, no restart.
  * random_per_block draws its positions on the HOST from a stateless counter-based generator (splitmix64 keyed on
  * (initial_rng_seed + gid, n, component), 53-bit mantissas) where the reference uses Kokkos' pool: same layout of ids
  * (n_per_block * gid + n), other positions. */
@@ -235,6 +235,21 @@ int apk_sim_tracers_seed(apk_sim *sim, const double *x, const double *y, const d
 /* the tracer step alone on the current state (what apk_sim_step runs after the last stage with the cycle's dt):
  * completes primitives and ghost zones, advects, re-owns, fills, sorts when ownership changed.  For tests. */
 int apk_sim_tracers_step(apk_sim *sim, double dt);
+/* ---- tracer lookback histories and their correlations (src/pgen/turbulence.cpp:200-216, 513-647) --------------------
+ * apk_amd/tracer_lookback = true | false (default false; anything else, and true without tracers/enabled = true, is
+ * refused at creation).  Opt-in and independent of the problem generator, where the reference turns it on for
+ * problem_id = turbulence whenever tracers are on.  Every particle then carries APK_TRACER_N_LOOKBACK levels of
+ * s = ln rho and sdot; the update runs once when the deck's particles are seeded (cycle 0, the sim's dt;
+ * tracers.cpp:183-186) and after the fill of every tracer step (hydro_driver.cpp:654-658) with the cycle number and the
+ * time at the START of the cycle.  Particles of apk_sim_tracers_seed start with empty (zero) histories: no update runs
+ * at user seeding.  apk_sim_execute writes <outdir>/correlations.csv: one '#' header line and one row per cycle,
+ * cycle,time,s,sdot,corr_s[0..11],corr_sdot[0..11],t_lookback[0..11], %.17g. */
+int apk_sim_tracer_lookback_options(const apk_sim *sim, int *enabled, int *n_lookback);
+/* the histories in storage order like apk_sim_tracers_read: which = 0 s, 1 sdot; out[n_lookback][particles] */
+int apk_sim_tracer_lookbacks_read(apk_sim *sim, int which, double *out);
+/* the row of the last update (turbulence.cpp:603-641): the cycle number and time it ran with, the active particles it
+ * divided by, and row[38] = <s>, <sdot>, corr_s[12], corr_sdot[12], t_lookback[12].  *cycle = -1 before any update. */
+int apk_sim_tracer_correlations(const apk_sim *sim, long long *cycle, double *time, long long *n_active, double *row);
 
 /* global block id and logical (bx,by,bz) of local block lb */
 int apk_sim_block_location(const apk_sim *sim, int lb, int *gid, int loc[3]);
