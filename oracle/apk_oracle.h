@@ -11,8 +11,10 @@
  * -ffp-contract=off, it is the canonical IEEE result the HIP kernels are compared to.
  *
  * Pinning status (see DESIGN.md "Oracle"):
- *  - pointwise known answers recorded from the reference's own headers in SURVEY.md 8(c)
- *    (PLM/PPM/WENOZ/LimO3 probe stencils, one HLLD flux vector) -> tests/golden/survey_probes.json
+ *  - pointwise: the reference's own headers compiled against stand-in names (oracle/ref/ -> oracle/_ref/ref_vectors):
+ *    recon.c, riemann.c and the ConsToPrim of block.c equal it bit for bit on tests/golden/reference_vectors.npz
+ *    and, where the reference tree is present, on fresh inputs (tests/test_reference_vectors.py); the five probe
+ *    values of SURVEY.md 8(c) are kept in tests/golden/survey_probes.json
  *  - the reference's own regression bounds (hydro linear wave VL2+PLM+HLLE 128x64x64
  *    RMS-L1 <= 1.547584e-08, tst/regression/test_suites/convergence/convergence.py:163;
  *    GLM-MHD RK3+WENOZ+HLLE 256x128x128 <= 6.14e-12, mhd_convergence.py:167)

@@ -78,6 +78,53 @@ def build(fast=False, force=False):
     return path
 
 
+REF_DIR = os.path.join(_HERE, "_ref")
+REF_BIN = os.path.join(REF_DIR, "ref_vectors")
+REF_SRC_DEFAULT = "/root/reference"
+
+
+def reference_tree():
+    """the reference checkout (APK_REFERENCE_SRC, or the default place), or None where there is none"""
+    root = os.environ.get("APK_REFERENCE_SRC", REF_SRC_DEFAULT)
+    return root if os.path.isfile(os.path.join(root, "src", "hydro", "rsolvers", "rsolvers.hpp")) else None
+
+
+def build_ref(force=False):
+    """Compile oracle/_ref/ref_vectors (the reference's own header-only arithmetic against the stand-in names of
+    oracle/ref/standin, recipe oracle/ref/Makefile).  Returns its path, or None when the reference tree is absent.
+    The binary is ignored by git and is never built from anything but the tree it was given."""
+    root = reference_tree()
+    if root is None:
+        return None
+    recipe = os.path.join(_HERE, "ref")
+    srcs = [os.path.join(recipe, f) for f in ("ref_vectors.cpp", "Makefile", os.path.join("standin", "apk_standin.hpp"))]
+    stale = (not os.path.exists(REF_BIN)) or any(os.path.getmtime(s) > os.path.getmtime(REF_BIN) for s in srcs)
+    if force or stale:
+        cmd = ["make", "-C", recipe, "-s", "APK_REFERENCE_SRC=" + root]
+        subprocess.run(cmd + (["-B"] if force else []), check=True, stdout=subprocess.DEVNULL)
+    return REF_BIN
+
+
+def ref_binary():
+    """path of an already built oracle/_ref/ref_vectors (it travels with the tree to machines that lack the
+    reference), or None"""
+    return REF_BIN if os.path.isfile(REF_BIN) and os.access(REF_BIN, os.X_OK) else None
+
+
+def ref_run(args, *arrays, path=None):
+    """Pipe fp64 arrays through the reference binary in a child process; returns its output as a flat fp64 array.
+    args: the subcommand and its arguments (oracle/ref/ref_vectors.cpp); floats are passed with 17 digits."""
+    path = path or ref_binary()
+    if path is None:
+        raise FileNotFoundError("oracle/_ref/ref_vectors is not built (oracle.build_ref())")
+    argv = [path] + [repr(float(a)) if isinstance(a, float) else str(a) for a in args]
+    data = b"".join(np.ascontiguousarray(a, dtype="<f8").tobytes() for a in arrays)
+    r = subprocess.run(argv, input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    if r.returncode != 0:
+        raise RuntimeError("ref_vectors %s: exit %d: %s" % (" ".join(argv[1:]), r.returncode, r.stderr.decode()[-500:]))
+    return np.frombuffer(r.stdout, dtype="<f8").astype(np.float64)
+
+
 def _declare(lib):
     d, i, l, p = C.c_double, C.c_int, C.c_long, c_dp
     G, E = C.POINTER(Geom), C.POINTER(Eos)

@@ -1,0 +1,1 @@
+#include "../apk_standin.hpp" // forwarding file: see apk_standin.hpp

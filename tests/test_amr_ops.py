@@ -312,15 +312,26 @@ def test_pressure_gradient_and_time_step_from_the_conserved_state(request, nx, n
     p0 = 0.5 * (sorted(vals)[-1] + sorted(vals)[-2])
     want_t, want_v = hydro.TagBlocks(ref, "pressure_gradient", p0)
     assert np.all(np.isfinite(want_v)) and len(set(want_t)) > 1
+    # ... and directly against the oracle on the filled state (not only against the HIP passes it replaces): ConsToPrim
+    # of every cell, the pressure-gradient criterion and tag of every block, the time step
+    _, w_orc, bad = H.orc_c2p(fluid, g, filled, H.O.make_eos(5.0 / 3.0))
+    orc = [H.O.tag("pressure_gradient", g, np.ascontiguousarray(w_orc[b]), p0) for b in range(nb)]
+    orc_t, orc_v, orc_dt = [o[0] for o in orc], [o[1] for o in orc], 0.3 * H.orc_min_dt(fluid, g, w_orc, 5.0 / 3.0)
+    assert bad == 0 and len(set(orc_t)) > 1
     for state, table in ((filled, None), (poisoned, dtab), (filled, dtab)):
         md = hydro.MeshData(ctx, nx, ng, nh, dx=tuple(g.dx), nblocks=nb, cons=state, prim=np.full_like(cons, np.nan), with_flux=False)
         t, v, dt = hydro.TagBlocksDtFromCons(md, fluid, eos, 0.3, p0, face_neighbor=table)
         assert np.all(np.isnan(md.prim_host()))                      # (nothing stored)
         if strict:
             assert list(v) == list(want_v) and list(t) == list(want_t) and dt == want_dt
+            assert list(v) == orc_v and list(t) == orc_t and dt == orc_dt, "differs from the oracle"
         else:
             np.testing.assert_allclose(v, want_v, rtol=1e-13)
             assert list(t) == list(want_t) and abs(dt - want_dt) <= 4e-16 * want_dt
+            print("product build against the oracle: criterion rel %.3e, dt rel %.3e" % (
+                np.max(np.abs(np.array(v) - orc_v) / np.array(orc_v)), abs(dt - orc_dt) / orc_dt))
+            np.testing.assert_allclose(v, orc_v, rtol=1e-13, err_msg="differs from the oracle")
+            assert list(t) == orc_t and abs(dt - orc_dt) <= 4e-16 * orc_dt, "differs from the oracle"
     with pytest.raises(hydro.L.ApkError):
         hydro.TagBlocksDtFromCons(md, fluid, hydro.L.make_eos(5.0 / 3.0, pfloor=1e-9), 0.3, p0)
     wide = hydro.MeshData(ctx, (128, 128, 8), ng, nh, dx=tuple(g.dx), nblocks=1, with_flux=False)
@@ -409,6 +420,29 @@ def test_boundary_plane_fluxes_from_the_conserved_state(request, strict, fluid, 
                 assert np.array_equal(got, want)
             else:
                 np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-13)
+    # ... and directly against the oracle (not only against the HIP passes it replaces): ConsToPrim of the state, then
+    # the fluxes of every listed plane
+    g = H.geom(fluid, nx, ng, 0, (0.1, 0.2, 0.3))
+    _, w_orc, bad = H.orc_c2p(fluid, g, cons, H.O.make_eos(gamma))
+    assert bad == 0
+    fl_orc = H.orc_fluxes(fluid, recon, riemann, g, w_orc, gamma, 1.3)
+    listed, planes = set(codes.cpu().tolist()), 0
+    for d in range(3):
+        for got in (own.flux_host(d), other.flux_host(d)):
+            for blk in range(nb):
+                for side in (0, 1):
+                    if 6 * blk + 2 * d + side not in listed:
+                        continue
+                    sl = [blk, slice(None)] + [slice(ng, ng + nx[q]) for q in (2, 1, 0)]
+                    sl[4 - d] = ng + (nx[d] if side else 0)
+                    sl = tuple(sl)
+                    assert np.abs(fl_orc[d][sl]).max() > 0
+                    if strict:
+                        assert np.array_equal(got[sl], fl_orc[d][sl]), "plane %d of block %d differs from the oracle" % (2 * d + side, blk)
+                    else:
+                        np.testing.assert_allclose(got[sl], fl_orc[d][sl], rtol=1e-12, atol=1e-13)
+                    planes += 1
+    assert planes == 2 * len(listed)
     floored = hydro.L.make_eos(gamma, pfloor=1e-9)
     with pytest.raises(hydro.L.ApkError):
         hydro.CalculateFluxes(own, fluid, recon, riemann, floored, 1.3, boundary=True, face_list=codes, from_cons=own)

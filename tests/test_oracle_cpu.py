@@ -1,5 +1,9 @@
 """CPU tests of the oracle (no GPU): pins against the reference's own numbers, then
-structural properties that any correct restatement must have."""
+structural properties that any correct restatement must have.
+
+The five probe values of (1) are the ones SURVEY 8(c) recorded; the systematic comparison with the reference's
+own compiled headers (oracle/_ref/ref_vectors: every reconstruction, Riemann solver and ConsToPrim, stored vectors and
+20 000 fresh inputs per family where the reference tree is present) is tests/test_reference_vectors.py."""
 import ctypes as C
 import json
 import os
