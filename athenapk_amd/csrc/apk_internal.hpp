@@ -182,10 +182,12 @@ int launch_fofc_mark(const PackView &u0, const PackView &u1, int fluid, double g
                      double gam1, double beta_dt, int attempt, unsigned char *d_mark,
                      unsigned long long *d_count, hipStream_t s);
 int launch_count_unphysical(const PackView &u0, int fluid, unsigned long long *d_count, hipStream_t s);
-// unsplit diffusion (kernels_diffusion.hip); cond: 0 none, 1 isotropic, 2 anisotropic (fixed coefficients)
+// unsplit diffusion (kernels_diffusion.hip); cond: apk_conduction; spitzer: NULL for the fixed coefficient kappa, else
+// the Spitzer numbers (kappa is then not read)
 int launch_diff_fluxes(const PackView &pv, int cond, bool visc, bool res, double kappa, double sat_prefac, double nu,
-                       double eta, hipStream_t s);
-int launch_cond_dt(const PackView &pv, double kappa, double sat_prefac, unsigned long long *d_min_bits, hipStream_t s);
+                       double eta, const apk_spitzer_cfg *spitzer, hipStream_t s);
+int launch_cond_dt(const PackView &pv, int cond, double kappa, double sat_prefac, const apk_spitzer_cfg *spitzer,
+                   unsigned long long *d_min_bits, hipStream_t s);
 // RKL2 super-time-stepping (kernels_sts.hip); the registers are DEVICE arrays of block descriptors of the shape of `yjm1`
 int launch_flux_divergence(const PackView &pv, const apk_block_desc *out, hipStream_t s);
 int launch_rkl2_step_first(const PackView &yjm1, const apk_block_desc *y0, const apk_block_desc *yjm2, const apk_block_desc *my0,
@@ -194,7 +196,8 @@ int launch_rkl2_step_other(const PackView &yjm1, const apk_block_desc *y0, const
                            double mu, double nu, double mu_tilde, double gamma_tilde, double tau, hipStream_t s);
 int launch_rkl2_substage_fused(const PackView &yjm1, const apk_block_desc *y0, const apk_block_desc *yjm2, const apk_block_desc *my0,
                                int cond, bool visc, bool res, double kappa, double sat_prefac, double nu_visc, double eta,
-                               double mu, double nu, double mu_tilde, double gamma_tilde, double tau, bool first, hipStream_t s);
+                               const apk_spitzer_cfg *spitzer, double mu, double nu, double mu_tilde, double gamma_tilde,
+                               double tau, bool first, hipStream_t s);
 int launch_fofc_fix(const PackView &u0, int fluid, double gamma, double c_h,
                     const unsigned char *d_mark, hipStream_t s);
 int launch_copy_regions(const apk_copy_plan &plan, hipStream_t s, int c2p_fluid = 0, const apk_eos *eos = nullptr,

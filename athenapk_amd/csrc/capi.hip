@@ -567,16 +567,27 @@ int apk_estimate_timestep(apk_ctx *ctx, const apk_pack *md, int fluid, const apk
 }
 
 namespace {
-// the subset of CalcDiffFluxes this library implements (diffusion.cpp:18-53 with fixed coefficients)
-int check_diff_cfg(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c) {
+// the subset of CalcDiffFluxes this library implements (diffusion.cpp:18-53): fixed coefficients, and Spitzer conduction
+// where the caller hands in its numbers.  *sp: what the launchers get -- `spitzer` where the configuration reads it
+int check_diff_cfg(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c, const apk_spitzer_cfg *spitzer,
+                   const apk_spitzer_cfg **sp) {
+  *sp = nullptr;
   if (!c) return set_err(ctx, APK_ERR_INVALID, "diffusion: cfg is NULL");
   if (c->conduction < APK_COND_NONE || c->conduction > APK_COND_ANISOTROPIC || c->viscosity < APK_VISC_NONE ||
       c->viscosity > APK_VISC_ISOTROPIC || c->resistivity < APK_RES_NONE || c->resistivity > APK_RES_OHMIC)
     return set_err(ctx, APK_ERR_INVALID, "diffusion: unknown process");
-  if ((c->conduction != APK_COND_NONE && c->conduction_coeff != APK_CONDC_FIXED) ||
-      (c->viscosity != APK_VISC_NONE && c->viscosity_coeff != APK_VISCC_FIXED) ||
+  if (c->conduction != APK_COND_NONE && c->conduction_coeff == APK_CONDC_SPITZER) {
+    if (!spitzer)
+      return set_err(ctx, APK_ERR_UNSUPPORTED, "diffusion: Spitzer conduction needs its units (an apk_spitzer_cfg, the _v2 entry points)");
+    if (!(spitzer->coeff_code > 0.0) || !(spitzer->mbar > 0.0) || !(spitzer->k_boltzmann > 0.0))
+      return set_err(ctx, APK_ERR_INVALID, "diffusion: apk_spitzer_cfg members must be positive");
+    *sp = spitzer;
+  } else if (c->conduction != APK_COND_NONE && c->conduction_coeff != APK_CONDC_FIXED) {
+    return set_err(ctx, APK_ERR_UNSUPPORTED, "diffusion: unknown conduction coefficient");
+  }
+  if ((c->viscosity != APK_VISC_NONE && c->viscosity_coeff != APK_VISCC_FIXED) ||
       (c->resistivity != APK_RES_NONE && c->resistivity_coeff != APK_RESC_FIXED))
-    return set_err(ctx, APK_ERR_UNSUPPORTED, "diffusion: only fixed coefficients are supported (Spitzer needs units)");
+    return set_err(ctx, APK_ERR_UNSUPPORTED, "diffusion: viscosity and resistivity support fixed coefficients only");
   if ((c->resistivity != APK_RES_NONE || c->conduction == APK_COND_ANISOTROPIC) && md->view.nhydro != 9)
     return set_err(ctx, APK_ERR_INVALID, "diffusion: resistivity and anisotropic conduction need a GLM-MHD pack");
   if (md->view.ng < 1) return set_err(ctx, APK_ERR_NGHOST, "diffusion: needs one ghost layer");
@@ -585,13 +596,19 @@ int check_diff_cfg(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c) {
 }  // namespace
 
 int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, apk_stream_t stream) {
+  return apk_calc_diff_fluxes_v2(ctx, md, cfg, nullptr, stream);
+}
+
+int apk_calc_diff_fluxes_v2(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, const apk_spitzer_cfg *spitzer,
+                            apk_stream_t stream) {
   if (!ctx || !md) return set_err(ctx, APK_ERR_INVALID, "apk_calc_diff_fluxes: bad argument");
-  int rc = check_diff_cfg(ctx, md, cfg);
+  const apk_spitzer_cfg *sp;
+  int rc = check_diff_cfg(ctx, md, cfg, spitzer, &sp);
   if (rc != APK_OK) return rc;
   for (int d = 0; d < md->view.ndim; ++d)
     if (!md->have_flux[d]) return set_err(ctx, APK_ERR_INVALID, "apk_calc_diff_fluxes: pack has no flux arrays");
   rc = launch_diff_fluxes(md->view, cfg->conduction, cfg->viscosity != APK_VISC_NONE, cfg->resistivity != APK_RES_NONE,
-                          cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, cfg->mom_diff_coeff, cfg->ohm_diff_coeff,
+                          cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, cfg->mom_diff_coeff, cfg->ohm_diff_coeff, sp,
                           as_stream(stream));
   if (rc != APK_OK) return set_err(ctx, rc, "diffusion flux kernel launch failed", hipGetLastError());
   return APK_OK;
@@ -599,8 +616,14 @@ int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c
 
 int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, double cfl_diff,
                                     double *dt_out, apk_stream_t stream) {
+  return apk_estimate_diffusion_timestep_v2(ctx, md, cfg, nullptr, cfl_diff, dt_out, stream);
+}
+
+int apk_estimate_diffusion_timestep_v2(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg,
+                                       const apk_spitzer_cfg *spitzer, double cfl_diff, double *dt_out, apk_stream_t stream) {
   if (!ctx || !md || !dt_out) return set_err(ctx, APK_ERR_INVALID, "apk_estimate_diffusion_timestep: bad argument");
-  int rc = check_diff_cfg(ctx, md, cfg);
+  const apk_spitzer_cfg *sp;
+  int rc = check_diff_cfg(ctx, md, cfg, spitzer, &sp);
   if (rc != APK_OK) return rc;
   const double huge = std::numeric_limits<double>::max();
   const PackView &v = md->view;
@@ -613,16 +636,16 @@ int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_
     return cfl_diff * fac * m;
   };
   double dt = huge;
-  if (cfg->conduction == APK_COND_ISOTROPIC) {
+  if (cfg->conduction == APK_COND_ISOTROPIC && !sp) {
     dt = std::fmin(dt, iso_fixed(cfg->thermal_diff_coeff));
-  } else if (cfg->conduction == APK_COND_ANISOTROPIC) {
+  } else if (cfg->conduction != APK_COND_NONE) {  // the general branch: anisotropic, or Spitzer
     hipStream_t s = as_stream(stream);
     unsigned long long bits;
     std::memcpy(&bits, &huge, sizeof(bits));
     auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
     h[0] = bits;
     APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_u64, h, sizeof(bits), hipMemcpyHostToDevice, s));
-    rc = launch_cond_dt(v, cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, ctx->d_u64, s);
+    rc = launch_cond_dt(v, cfg->conduction, cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, sp, ctx->d_u64, s);
     if (rc != APK_OK) return set_err(ctx, rc, "conduction dt kernel launch failed", hipGetLastError());
     APK_HIP_TRY(ctx, hipMemcpyAsync(h + 1, ctx->d_u64, sizeof(bits), hipMemcpyDeviceToHost, s));
     APK_HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -688,15 +711,22 @@ int apk_rkl2_step_other(apk_ctx *ctx, const apk_pack *y0, const apk_pack *yjm1, 
 
 int apk_rkl2_substage_fused(apk_ctx *ctx, const apk_pack *md, const apk_rkl2_regs *regs, const apk_diff_cfg *cfg,
                             const apk_rkl2_coeffs *coeffs, double tau, int first, apk_stream_t stream) {
+  return apk_rkl2_substage_fused_v2(ctx, md, regs, cfg, nullptr, coeffs, tau, first, stream);
+}
+
+int apk_rkl2_substage_fused_v2(apk_ctx *ctx, const apk_pack *md, const apk_rkl2_regs *regs, const apk_diff_cfg *cfg,
+                               const apk_spitzer_cfg *spitzer, const apk_rkl2_coeffs *coeffs, double tau, int first,
+                               apk_stream_t stream) {
   if (!regs || !coeffs) return set_err(ctx, APK_ERR_INVALID, "apk_rkl2_substage_fused: bad argument");
   int rc = check_rkl2_regs(ctx, "apk_rkl2_substage_fused: bad argument", regs->y0, md, regs->yjm2, regs->my0);
   if (rc != APK_OK) return rc;
-  if ((rc = check_diff_cfg(ctx, md, cfg)) != APK_OK) return rc;
+  const apk_spitzer_cfg *sp;
+  if ((rc = check_diff_cfg(ctx, md, cfg, spitzer, &sp)) != APK_OK) return rc;
   for (const apk_block_desc &b : md->h_blocks)
     if (!b.prim) return set_err(ctx, APK_ERR_INVALID, "apk_rkl2_substage_fused: the pack has no primitives");
   rc = launch_rkl2_substage_fused(md->view, regs->y0->d_blocks, regs->yjm2->d_blocks, regs->my0->d_blocks, cfg->conduction,
                                   cfg->viscosity != APK_VISC_NONE, cfg->resistivity != APK_RES_NONE, cfg->thermal_diff_coeff,
-                                  cfg->conduction_sat_prefac, cfg->mom_diff_coeff, cfg->ohm_diff_coeff, coeffs->mu, coeffs->nu,
+                                  cfg->conduction_sat_prefac, cfg->mom_diff_coeff, cfg->ohm_diff_coeff, sp, coeffs->mu, coeffs->nu,
                                   coeffs->mu_tilde, coeffs->gamma_tilde, tau, first != 0, as_stream(stream));
   if (rc != APK_OK) return set_err(ctx, rc, "fused RKL2 sub-stage kernel launch failed", hipGetLastError());
   return APK_OK;

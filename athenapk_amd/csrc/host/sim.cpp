@@ -139,13 +139,14 @@ void hydro_initialize(apk_sim *s) {
   cooling_initialize(s);
 }
 
-// <diffusion> (src/hydro/hydro.cpp:538-702): the fixed-coefficient processes with the unsplit integrator.  What this
+// <diffusion> (src/hydro/hydro.cpp:538-702): the fixed-coefficient processes and Spitzer conduction.  What this
 // path does not implement is refused instead of being ignored: a deck that asks for diffusion must not run inviscid.
 void diffusion_initialize(apk_sim *s) {
   ParameterInput &pin = s->pin;
   HydroPackage &pkg = s->pkg;
   apk_diff_cfg &c = pkg.diff;
   c = apk_diff_cfg{};
+  pkg.spitzer = apk_spitzer_cfg{};
   const std::string conduction = pin.GetOrAddString("diffusion", "conduction", "none");
   if (conduction == "isotropic") c.conduction = APK_COND_ISOTROPIC;
   else if (conduction == "anisotropic") c.conduction = APK_COND_ANISOTROPIC;
@@ -154,8 +155,17 @@ void diffusion_initialize(apk_sim *s) {
     const std::string coeff = pin.GetOrAddString("diffusion", "conduction_coeff", "none");
     const double sat_phi = pin.GetOrAddReal("diffusion", "conduction_sat_phi", 0.3);
     if (coeff == "spitzer") {
-      throw std::runtime_error("Spitzer thermal conduction requires units and gas composition (not part of this path); "
-                               "use diffusion/conduction_coeff = fixed.");
+      const UnitsState &u = pkg.units;
+      if (!u.has_composition)
+        throw std::runtime_error("Spitzer thermal conduction requires units and gas composition. Please set a 'units' "
+                                 "block and the 'hydro/He_mass_fraction' in the input file.");
+      c.conduction_coeff = APK_CONDC_SPITZER;
+      // default: a fully ionized hydrogen plasma with a Coulomb logarithm of 40, 1.84e-5 / ln Lambda = 4.6e-7; to code
+      // units with no temperature conversion, [T_phys] = [T_code] (hydro.cpp:575-581)
+      double spitzer_coeff = pin.GetOrAddReal("diffusion", "spitzer_cond_in_erg_by_s_K_cm", 4.6e-7);
+      spitzer_coeff *= u.erg() / (u.s() * u.cm());
+      pkg.spitzer = apk_spitzer_cfg{spitzer_coeff, u.mbar, u.k_boltzmann()};
+      c.conduction_sat_prefac = 6.86 * std::sqrt(u.mu) * sat_phi;  // eq (7) of Cowie & McKee 1977, T_e = T_i (hydro.cpp:589-593)
     } else if (coeff == "fixed") {
       c.conduction_coeff = APK_CONDC_FIXED;
       c.thermal_diff_coeff = pin.GetReal("diffusion", "thermal_diff_coeff_code");
@@ -447,7 +457,8 @@ int estimate_timestep_read(apk_sim *s, DtEstimate *e) {
   // the diffusive limit (hydro.cpp:935-963; unsplit: min_dt = min(dt_hyp, dt_diff); rkl2: see estimate_timestep_commit)
   if (s->pkg.diffusion_configured()) {
     if (s->prim_stale) SIM_TRY(s, sync_ghosts(s));  // (the estimate reads stored primitives)
-    SIM_TRY(s, apk_estimate_diffusion_timestep(s->ctx, s->mu0(), &s->pkg.diff, s->pkg.cfl_diff, &e->dt_diff_local, s->stream));
+    SIM_TRY(s, apk_estimate_diffusion_timestep_v2(s->ctx, s->mu0(), &s->pkg.diff, s->pkg.spitzer_cfg(), s->pkg.cfl_diff,
+                                                  &e->dt_diff_local, s->stream));
   }
   // the cooling limit (hydro.cpp:926-933): joins min_dt, not dt_hyp (so c_h is untouched)
   if (s->pkg.cooling) {
@@ -1106,6 +1117,13 @@ int apk_sim_diffusion_options(const apk_sim *s, apk_diff_cfg *cfg, int *integrat
   *cfg = s->pkg.diff;
   *integrator = s->pkg.diffint;
   *cfl_diff = s->pkg.cfl_diff;
+  return APK_OK;
+}
+
+int apk_sim_spitzer_options(const apk_sim *s, int *enabled, apk_spitzer_cfg *cfg) {
+  if (!s || !enabled || !cfg) return APK_ERR_INVALID;
+  *enabled = s->pkg.spitzer_cfg() ? 1 : 0;
+  *cfg = s->pkg.spitzer;
   return APK_OK;
 }
 

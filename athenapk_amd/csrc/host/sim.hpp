@@ -51,6 +51,11 @@ struct HydroPackage {
   apk_flux_cfg flux_first_stage{}, flux_other_stage{};
   // <diffusion> (hydro.cpp:538-702): the processes, diffint and cfl_diff
   apk_diff_cfg diff{};
+  // conduction_coeff = spitzer (hydro.cpp:567-593): what ThermalDiffusivity::Get needs, next to `diff`; all 0 otherwise
+  apk_spitzer_cfg spitzer{};
+  const apk_spitzer_cfg *spitzer_cfg() const {
+    return (diff.conduction != APK_COND_NONE && diff.conduction_coeff == APK_CONDC_SPITZER) ? &spitzer : nullptr;
+  }
   int diffint = APK_DIFFINT_NONE;
   double cfl_diff = 0.0;
   // diffusion/rkl2_max_dt_ratio (hydro.cpp:686-689); rkl2 is accepted only with a positive ratio

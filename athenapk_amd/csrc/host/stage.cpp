@@ -786,7 +786,7 @@ static int run_flux_array_stage(apk_sim *s, const Stage &st) {
   SIM_TRY(s, apk_calculate_fluxes_tight(s->ctx, s->mu0(), st.cfg, &pkg.eos, pkg.c_h, s->stream));
   // the diffusive fluxes are added at the end of CalculateFluxes (hydro.cpp:1202-1205): FOFC's LLF fluxes, where it
   // corrects a cell, replace whole face fluxes after that
-  if (pkg.diffusion_in_fluxes()) SIM_TRY(s, apk_calc_diff_fluxes(s->ctx, s->mu0(), &pkg.diff, s->stream));
+  if (pkg.diffusion_in_fluxes()) SIM_TRY(s, apk_calc_diff_fluxes_v2(s->ctx, s->mu0(), &pkg.diff, pkg.spitzer_cfg(), s->stream));
   if (pkg.first_order_flux_correct) {
     long long nfix = 0;
     SIM_TRY(s, apk_first_order_flux_correct(s->ctx, s->mu0(), s->mu1(), pkg.fluid, &pkg.eos, pkg.c_h, st.g0, st.g1,

@@ -91,11 +91,11 @@ int sts_half_step(apk_sim *s, double tau) {
       return fail(s, APK_ERR_INVALID, "sts_half_step: coefficients");
     if (s->sts_fused) {
       const apk_rkl2_regs regs{y0, s->yjm2_pack, s->my0_pack};
-      SIM_TRY(s, apk_rkl2_substage_fused(s->ctx, base, &regs, &pkg.diff, &k, tau, j == 1 ? 1 : 0, s->stream));
+      SIM_TRY(s, apk_rkl2_substage_fused_v2(s->ctx, base, &regs, &pkg.diff, pkg.spitzer_cfg(), &k, tau, j == 1 ? 1 : 0, s->stream));
     } else {
       // ResetFluxes, CalcDiffFluxes, then FluxDivergence + RKL2StepFirst or RKL2StepOther (hydro_driver.cpp:234-260, 306-326)
       for (int d = 0; d < s->mesh.ndim; ++d) SIM_HIP(s, hipMemsetAsync(s->d_flux[d], 0, field_bytes, hs(s)));
-      SIM_TRY(s, apk_calc_diff_fluxes(s->ctx, base, &pkg.diff, s->stream));
+      SIM_TRY(s, apk_calc_diff_fluxes_v2(s->ctx, base, &pkg.diff, pkg.spitzer_cfg(), s->stream));
       if (j == 1) {
         SIM_TRY(s, apk_flux_divergence(s->ctx, base, s->my0_pack, s->stream));
         SIM_TRY(s, apk_rkl2_step_first(s->ctx, y0, base, s->yjm2_pack, s->my0_pack, s_rkl, tau, s->stream));

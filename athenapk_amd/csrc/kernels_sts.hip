@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(256) rkl2_step_other_kernel(PackView pv, const
 }
 
 // The fused sub-stage.  pv: Yjm1 (prim: its primitives, ghost zones in sync; cons: updated in place).
-template <int NDIM, int COND, bool VISC, bool RES>
+template <int NDIM, int COND, bool VISC, bool RES, int COEFF>
 __global__ void __launch_bounds__(256) rkl2_substage_fused_kernel(PackView pv, const apk_block_desc *y0b, const apk_block_desc *yjm2b,
                                                                   const apk_block_desc *my0b, DiffCoeffs c, Rkl2Coeffs k, double tau,
                                                                   int first, int b0) {
@@ -106,15 +106,19 @@ __global__ void __launch_bounds__(256) rkl2_substage_fused_kernel(PackView pv, c
   // (forming one direction at a time between scheduling barriers was tried to shorten the live ranges of the 3-D kernel
   // with every process: it spilled 156 B per lane where this form uses 488 registers and no scratch)
   DiffFaceFlux lo[3] = {}, hi[3] = {};
-  diff_face<0, COND, VISC, RES>(w, sn, sj, sk, blk.dx, NDIM, c, lo[0]);
-  diff_face<0, COND, VISC, RES>(w + 1, sn, sj, sk, blk.dx, NDIM, c, hi[0]);
+  // the diffusivity of this cell and of its 2 ndim neighbours, each formed once (7 evaluations for 6 faces; chi of a cell
+  // is one value wherever it is formed, so the faces are those of the flux-array pass); a fixed coefficient: c.kappa
+  auto chi = [&](int64_t o) { return diff_chi<COEFF>(c, w[IPR * sn + o], w[IDN * sn + o]); };
+  const double chi0 = chi(0);
+  diff_face<0, COND, VISC, RES>(w, sn, sj, sk, blk.dx, NDIM, c, chi0, chi(-1), lo[0]);
+  diff_face<0, COND, VISC, RES>(w + 1, sn, sj, sk, blk.dx, NDIM, c, chi(1), chi0, hi[0]);
   if constexpr (NDIM >= 2) {
-    diff_face<1, COND, VISC, RES>(w, sn, sj, sk, blk.dx, NDIM, c, lo[1]);
-    diff_face<1, COND, VISC, RES>(w + sj, sn, sj, sk, blk.dx, NDIM, c, hi[1]);
+    diff_face<1, COND, VISC, RES>(w, sn, sj, sk, blk.dx, NDIM, c, chi0, chi(-sj), lo[1]);
+    diff_face<1, COND, VISC, RES>(w + sj, sn, sj, sk, blk.dx, NDIM, c, chi(sj), chi0, hi[1]);
   }
   if constexpr (NDIM == 3) {
-    diff_face<2, COND, VISC, RES>(w, sn, sj, sk, blk.dx, NDIM, c, lo[2]);
-    diff_face<2, COND, VISC, RES>(w + sk, sn, sj, sk, blk.dx, NDIM, c, hi[2]);
+    diff_face<2, COND, VISC, RES>(w, sn, sj, sk, blk.dx, NDIM, c, chi0, chi(-sk), lo[2]);
+    diff_face<2, COND, VISC, RES>(w + sk, sn, sj, sk, blk.dx, NDIM, c, chi(sk), chi0, hi[2]);
   }
   double area[3], vol;
   block_areas(blk, area, vol);
@@ -165,17 +169,19 @@ using FusedKernel = void (*)(PackView, const apk_block_desc *, const apk_block_d
                              Rkl2Coeffs, double, int, int);
 
 template <int NDIM>
-FusedKernel pick_fused(int cond, bool visc, bool res) {
-#define APK_STS_PICK(C)                                                               \
-  if (cond == C) {                                                                    \
-    if (visc && res) return rkl2_substage_fused_kernel<NDIM, C, true, true>;          \
-    if (visc) return rkl2_substage_fused_kernel<NDIM, C, true, false>;                \
-    if (res) return rkl2_substage_fused_kernel<NDIM, C, false, true>;                 \
-    return rkl2_substage_fused_kernel<NDIM, C, false, false>;                         \
+FusedKernel pick_fused(int cond, int coeff, bool visc, bool res) {
+#define APK_STS_PICK(C, K)                                                            \
+  if (cond == C && coeff == K) {                                                      \
+    if (visc && res) return rkl2_substage_fused_kernel<NDIM, C, true, true, K>;       \
+    if (visc) return rkl2_substage_fused_kernel<NDIM, C, true, false, K>;             \
+    if (res) return rkl2_substage_fused_kernel<NDIM, C, false, true, K>;              \
+    return rkl2_substage_fused_kernel<NDIM, C, false, false, K>;                      \
   }
-  APK_STS_PICK(COND_NONE)
-  APK_STS_PICK(COND_ISO)
-  APK_STS_PICK(COND_ANISO)
+  APK_STS_PICK(COND_NONE, COEFF_FIXED)
+  APK_STS_PICK(COND_ISO, COEFF_FIXED)
+  APK_STS_PICK(COND_ANISO, COEFF_FIXED)
+  APK_STS_PICK(COND_ISO_GEN, COEFF_SPITZER)
+  APK_STS_PICK(COND_ANISO, COEFF_SPITZER)
 #undef APK_STS_PICK
   return nullptr;
 }
@@ -215,14 +221,18 @@ int launch_rkl2_step_other(const PackView &yjm1, const apk_block_desc *y0, const
   });
 }
 
-// cond: 0 none, 1 isotropic (fixed), 2 anisotropic (fixed), as launch_diff_fluxes
+// cond, spitzer: as launch_diff_fluxes
 int launch_rkl2_substage_fused(const PackView &yjm1, const apk_block_desc *y0, const apk_block_desc *yjm2, const apk_block_desc *my0,
                                int cond, bool visc, bool res, double kappa, double sat_prefac, double nu_visc, double eta,
-                               double mu, double nu, double mu_tilde, double gamma_tilde, double tau, bool first, hipStream_t s) {
-  const DiffCoeffs c{kappa, sat_prefac, nu_visc, eta};
+                               const apk_spitzer_cfg *spitzer, double mu, double nu, double mu_tilde, double gamma_tilde,
+                               double tau, bool first, hipStream_t s) {
+  const DiffCoeffs c = diff_coeffs(cond, kappa, sat_prefac, nu_visc, eta, spitzer);
+  const int coeff = diff_coeff_kind(cond, spitzer);
+  cond = diff_cond_mode(cond, spitzer);
   const Rkl2Coeffs k{mu, nu, mu_tilde, gamma_tilde};
-  const FusedKernel kern = yjm1.ndim == 1 ? pick_fused<1>(cond, visc, res)
-                                          : (yjm1.ndim == 2 ? pick_fused<2>(cond, visc, res) : pick_fused<3>(cond, visc, res));
+  const FusedKernel kern = yjm1.ndim == 1 ? pick_fused<1>(cond, coeff, visc, res)
+                                          : (yjm1.ndim == 2 ? pick_fused<2>(cond, coeff, visc, res)
+                                                            : pick_fused<3>(cond, coeff, visc, res));
   if (!kern) return APK_ERR_INVALID;
   return for_block_chunks(yjm1, [&](dim3 grid, int b0) {
     hipLaunchKernelGGL(kern, grid, dim3(64, 4, 1), 0, s, yjm1, y0, yjm2, my0, c, k, tau, first ? 1 : 0, b0);

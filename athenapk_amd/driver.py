@@ -619,6 +619,11 @@ class Simulation(_FmftHost, _MeshView):
         2 tau / dt_diff, whether a sub-stage is the fused kernel or the passes over the flux arrays)"""
         return _sts_info(self.lib, self.h)
 
+    def spitzer_options(self):
+        """lib.SpitzerCfg (the converted coefficient, mbar, k_boltzmann; code units) as the deck was parsed, or None
+        unless diffusion/conduction_coeff = spitzer"""
+        return _spitzer_options(self.lib, self.h)
+
     def reset_time_step(self):
         """after write_block + exchange_ghosts + fill_derived: the time step as initialize() derives it"""
         self._check(self.lib.apk_sim_reset_time_step(self.h))
@@ -698,6 +703,14 @@ def _diffusion_options(lib, h):
     if rc != L.APK_OK:
         raise L.ApkError(rc, "apk_sim_diffusion_options")
     return cfg, integ.value, cfl.value
+
+
+def _spitzer_options(lib, h):
+    en, cfg = C.c_int(0), L.SpitzerCfg()
+    rc = lib.apk_sim_spitzer_options(h, C.byref(en), C.byref(cfg))
+    if rc != L.APK_OK:
+        raise L.ApkError(rc, "apk_sim_spitzer_options")
+    return cfg if en.value else None
 
 
 def _sts_info(lib, h):
@@ -820,6 +833,11 @@ class HostPlan(_FmftHost, _MeshView):
     def sts_info(self):
         """(sub-stages of the last RKL2 half step, its ratio 2 tau / dt_diff, whether sub-stages run fused)"""
         return _sts_info(self.lib, self.h)
+
+    def spitzer_options(self):
+        """lib.SpitzerCfg (the converted coefficient, mbar, k_boltzmann; code units) as the deck was parsed, or None
+        unless diffusion/conduction_coeff = spitzer"""
+        return _spitzer_options(self.lib, self.h)
 
     def units(self):
         """lib.UnitsInfo: <units>, the gas composition and the EOS's efloor / eceil as parsed"""

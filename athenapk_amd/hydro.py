@@ -371,11 +371,15 @@ def EstimateTimestep(md, fluid, eos, cfl):
     return dt.value
 
 
-def CalcDiffFluxes(md, cfg):
+def CalcDiffFluxes(md, cfg, spitzer=None):
     """CalcDiffFluxes(hydro_pkg, md) -- src/hydro/diffusion/diffusion.cpp:18; cfg: lib.DiffCfg (lib.make_diff_cfg).
-    Adds the diffusive fluxes into md.flux[d]."""
+    Adds the diffusive fluxes into md.flux[d].  spitzer: lib.SpitzerCfg for conduction_coeff = spitzer
+    (apk_calc_diff_fluxes_v2); None: the fixed-coefficient entry point."""
     ctx = md.ctx
-    _check(ctx.lib.apk_calc_diff_fluxes(ctx.h, md.h, C.byref(cfg), _stream()), ctx.lib, ctx.h)
+    if spitzer is None:
+        _check(ctx.lib.apk_calc_diff_fluxes(ctx.h, md.h, C.byref(cfg), _stream()), ctx.lib, ctx.h)
+    else:
+        _check(ctx.lib.apk_calc_diff_fluxes_v2(ctx.h, md.h, C.byref(cfg), C.byref(spitzer), _stream()), ctx.lib, ctx.h)
 
 
 def TracersLookback(ctx, rho, active, s, sdot, cycle, dt):
@@ -401,12 +405,16 @@ def TracersLookback(ctx, rho, active, s, sdot, cycle, dt):
     return sums
 
 
-def EstimateDiffusionTimestep(md, cfg, cfl_diff):
-    """the diffusive limit of Hydro::EstimateTimestep -- src/hydro/hydro.cpp:935-949"""
+def EstimateDiffusionTimestep(md, cfg, cfl_diff, spitzer=None):
+    """the diffusive limit of Hydro::EstimateTimestep -- src/hydro/hydro.cpp:935-949; spitzer: as CalcDiffFluxes"""
     ctx = md.ctx
     dt = C.c_double(0.0)
-    _check(ctx.lib.apk_estimate_diffusion_timestep(ctx.h, md.h, C.byref(cfg), float(cfl_diff), C.byref(dt), _stream()),
-           ctx.lib, ctx.h)
+    if spitzer is None:
+        _check(ctx.lib.apk_estimate_diffusion_timestep(ctx.h, md.h, C.byref(cfg), float(cfl_diff), C.byref(dt), _stream()),
+               ctx.lib, ctx.h)
+    else:
+        _check(ctx.lib.apk_estimate_diffusion_timestep_v2(ctx.h, md.h, C.byref(cfg), C.byref(spitzer), float(cfl_diff),
+                                                          C.byref(dt), _stream()), ctx.lib, ctx.h)
     return dt.value
 
 
@@ -444,14 +452,19 @@ def RKL2StepOther(y0, yjm1, yjm2, my0, mu_j, nu_j, mu_tilde_j, gamma_tilde_j, ta
                                        float(gamma_tilde_j), float(tau), _stream()), ctx.lib, ctx.h)
 
 
-def RKL2SubstageFused(y0, yjm1, yjm2, my0, cfg, coeffs, tau, first):
+def RKL2SubstageFused(y0, yjm1, yjm2, my0, cfg, coeffs, tau, first, spitzer=None):
     """one RKL2 sub-stage in one kernel (apk_rkl2_substage_fused): the diffusive fluxes of yjm1.prim, their divergence
-    and RKL2StepFirst (first) / RKL2StepOther; coeffs: (mu, nu, mu_tilde, gamma_tilde) as rkl2_coefficients returns"""
+    and RKL2StepFirst (first) / RKL2StepOther; coeffs: (mu, nu, mu_tilde, gamma_tilde) as rkl2_coefficients returns;
+    spitzer: as CalcDiffFluxes"""
     ctx = yjm1.ctx
     regs = L.Rkl2Regs(y0.h, yjm2.h, my0.h)
     k = L.Rkl2Coeffs(*[float(x) for x in coeffs])
-    _check(ctx.lib.apk_rkl2_substage_fused(ctx.h, yjm1.h, C.byref(regs), C.byref(cfg), C.byref(k), float(tau),
-                                           1 if first else 0, _stream()), ctx.lib, ctx.h)
+    if spitzer is None:
+        _check(ctx.lib.apk_rkl2_substage_fused(ctx.h, yjm1.h, C.byref(regs), C.byref(cfg), C.byref(k), float(tau),
+                                               1 if first else 0, _stream()), ctx.lib, ctx.h)
+    else:
+        _check(ctx.lib.apk_rkl2_substage_fused_v2(ctx.h, yjm1.h, C.byref(regs), C.byref(cfg), C.byref(spitzer), C.byref(k),
+                                                  float(tau), 1 if first else 0, _stream()), ctx.lib, ctx.h)
 
 
 class TabularCooling:

@@ -65,6 +65,17 @@ def make_diff_cfg(conduction="none", kappa=0.0, sat_phi=0.3, viscosity="none", n
                    RESISTIVITY[resistivity], fixed, eta)
 
 
+class SpitzerCfg(C.Structure):
+    _fields_ = [("coeff_code", C.c_double), ("mbar", C.c_double), ("k_boltzmann", C.c_double)]
+
+
+def make_spitzer_cfg(coeff_code, mbar, k_boltzmann):
+    """apk_spitzer_cfg, all in code units: the Spitzer coefficient (spitzer_cond_in_erg_by_s_K_cm * erg / (s cm)), mbar
+    = mu * atomic_mass_unit and k_boltzmann (hydro.cpp:577-586).  Goes with a lib.DiffCfg whose conduction_coeff is
+    DIFF_COEFF["spitzer"] and whose conduction_sat_prefac is 6.86 sqrt(mu) phi (hydro.cpp:589-593)."""
+    return SpitzerCfg(float(coeff_code), float(mbar), float(k_boltzmann))
+
+
 class Rkl2Regs(C.Structure):
     _fields_ = [("y0", C.c_void_p), ("yjm2", C.c_void_p), ("my0", C.c_void_p)]
 
@@ -265,12 +276,16 @@ def _signatures():
         "apk_estimate_timestep": (i, [vp, vp, i, E, d, c_dp, vp]),
         "apk_calc_diff_fluxes": (i, [vp, vp, C.POINTER(DiffCfg), vp]),
         "apk_estimate_diffusion_timestep": (i, [vp, vp, C.POINTER(DiffCfg), d, c_dp, vp]),
+        "apk_calc_diff_fluxes_v2": (i, [vp, vp, C.POINTER(DiffCfg), C.POINTER(SpitzerCfg), vp]),
+        "apk_estimate_diffusion_timestep_v2": (i, [vp, vp, C.POINTER(DiffCfg), C.POINTER(SpitzerCfg), d, c_dp, vp]),
         "apk_rkl2_num_stages": (i, [d, d, C.POINTER(C.c_int)]),
         "apk_rkl2_coefficients": (i, [i, i, c_dp, c_dp, c_dp, c_dp]),
         "apk_flux_divergence": (i, [vp, vp, vp, vp]),
         "apk_rkl2_step_first": (i, [vp, vp, vp, vp, vp, i, d, vp]),
         "apk_rkl2_step_other": (i, [vp, vp, vp, vp, vp, d, d, d, d, d, vp]),
         "apk_rkl2_substage_fused": (i, [vp, vp, C.POINTER(Rkl2Regs), C.POINTER(DiffCfg), C.POINTER(Rkl2Coeffs), d, i, vp]),
+        "apk_rkl2_substage_fused_v2": (i, [vp, vp, C.POINTER(Rkl2Regs), C.POINTER(DiffCfg), C.POINTER(SpitzerCfg),
+                                           C.POINTER(Rkl2Coeffs), d, i, vp]),
         "apk_cooling_table_create": (i, [vp, c_dp, c_dp, i, C.POINTER(CoolingParams), pp]),
         "apk_cooling_table_destroy": (None, [vp]),
         "apk_cooling_dedt": (i, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
@@ -351,6 +366,7 @@ def _signatures():
         "apk_sim_loop_cycles": (i, [vp]),
         "apk_sim_get_info": (i, [vp, C.POINTER(SimInfo)]),
         "apk_sim_diffusion_options": (i, [vp, C.POINTER(DiffCfg), C.POINTER(C.c_int), c_dp]),
+        "apk_sim_spitzer_options": (i, [vp, C.POINTER(C.c_int), C.POINTER(SpitzerCfg)]),
         "apk_sim_rkl2_max_dt_ratio": (d, [vp]),
         "apk_sim_sts_info": (i, [vp, C.POINTER(C.c_int), c_dp, C.POINTER(C.c_int)]),
         "apk_sim_units": (i, [vp, C.POINTER(UnitsInfo)]),

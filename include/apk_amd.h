@@ -420,8 +420,10 @@ enum apk_diffint { APK_DIFFINT_NONE = 0, APK_DIFFINT_UNSPLIT = 1, APK_DIFFINT_RK
 
 /* The "Hydro" params of the diffusive processes (hydro.cpp:538-702): the ThermalDiffusivity, MomentumDiffusivity and
  * OhmicDiffusivity objects with a fixed coefficient, and conduction_sat_prefac (5 * diffusion/conduction_sat_phi for a
- * fixed coefficient, hydro.cpp:595-604).  A process set to *_NONE is off.  Only the *_FIXED coefficients are supported
- * (Spitzer needs units: APK_ERR_UNSUPPORTED). */
+ * fixed coefficient, 6.86 * sqrt(mu) * phi for Spitzer, hydro.cpp:589-604).  A process set to *_NONE is off.  The entry
+ * points that take this struct alone are the fixed-coefficient ones: conduction_coeff = APK_CONDC_SPITZER is
+ * APK_ERR_UNSUPPORTED there; the *_v2 entry points below take the Spitzer numbers next to it.  Spitzer resistivity is
+ * refused everywhere, as in the reference (hydro.cpp:662-665). */
 typedef struct apk_diff_cfg {
   int conduction, conduction_coeff; /* apk_conduction, apk_conduction_coeff */
   double thermal_diff_coeff;        /* diffusion/thermal_diff_coeff_code */
@@ -449,6 +451,31 @@ int apk_calc_diff_fluxes(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *c
  * No process enabled: *dt_out = DBL_MAX. */
 int apk_estimate_diffusion_timestep(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, double cfl_diff,
                                     double *dt_out, apk_stream_t stream);
+
+/* What ThermalDiffusivity::Get (conduction.cpp:28-42) needs for conduction_coeff = APK_CONDC_SPITZER, in code units:
+ *   T_cgs = mbar / k_boltzmann * p / rho;  kappa = coeff_code * T_cgs^(5/2);  chi = kappa * mbar / k_boltzmann / rho
+ * each left to right.  T^(5/2) is evaluated as T * T * sqrt(T) (three correctly rounded operations) where the reference
+ * calls std::pow: within 3 ulp of it, and the same bits in every build and in the tests' restatement. */
+typedef struct apk_spitzer_cfg {
+  double coeff_code;  /* diffusion/spitzer_cond_in_erg_by_s_K_cm * erg / (s * cm) in code units (hydro.cpp:577-581) */
+  double mbar;        /* mu * atomic_mass_unit in code units (the "mbar" param, hydro.cpp:500) */
+  double k_boltzmann; /* Units::k_boltzmann() in code units */
+} apk_spitzer_cfg;
+
+/* apk_calc_diff_fluxes with the whole dispatch of CalcDiffFluxes (diffusion.cpp:18-53): isotropic conduction with a
+ * fixed coefficient is ThermalFluxIsoFixed; isotropic Spitzer and anisotropic conduction with either coefficient are
+ * ThermalFluxGeneral (conduction.cpp:265-471; its isotropic branch :344-346 uses the lim4 transverse gradients too, and
+ * a collapsed direction contributes 0 to |grad T|).  spitzer == NULL: exactly apk_calc_diff_fluxes (which forwards
+ * here).  cfg->conduction_coeff = APK_CONDC_SPITZER reads `spitzer` instead of cfg->thermal_diff_coeff: NULL is
+ * APK_ERR_UNSUPPORTED, a member that is not positive APK_ERR_INVALID.  `spitzer` is not read otherwise. */
+int apk_calc_diff_fluxes_v2(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg, const apk_spitzer_cfg *spitzer,
+                            apk_stream_t stream);
+/* apk_estimate_diffusion_timestep with the general branch of EstimateConductionTimestep (conduction.cpp:93-181) for
+ * Spitzer: per interior cell with a temperature gradient, dx_d^2 / chi(p, rho) (isotropic; no TINY_NUMBER there) or the
+ * anisotropic expression with chi(p, rho) of the cell, the flux_classic / flux_sat > 100 early return included.  Both
+ * are device min-reductions (synchronises `stream`).  `spitzer` as above. */
+int apk_estimate_diffusion_timestep_v2(apk_ctx *ctx, const apk_pack *md, const apk_diff_cfg *cfg,
+                                       const apk_spitzer_cfg *spitzer, double cfl_diff, double *dt_out, apk_stream_t stream);
 
 /* ---- RKL2 super-time-stepping (diffusion/integrator = rkl2) ---------------------------------------------------------
  * Operator-split Runge-Kutta-Legendre super-time-stepping of the diffusive processes (Meyer, Balsara & Aslam 2014):
@@ -492,6 +519,11 @@ typedef struct apk_rkl2_coeffs {
  * primitives, writes conserved arrays: in place, no flux arrays needed. */
 int apk_rkl2_substage_fused(apk_ctx *ctx, const apk_pack *md, const apk_rkl2_regs *regs, const apk_diff_cfg *cfg,
                             const apk_rkl2_coeffs *coeffs, double tau, int first, apk_stream_t stream);
+/* The same with the fluxes of apk_calc_diff_fluxes_v2; `spitzer` as there (NULL: exactly apk_rkl2_substage_fused, which
+ * forwards here).  The diffusivity of the lane's cell and of each of its 2 ndim neighbours is formed once. */
+int apk_rkl2_substage_fused_v2(apk_ctx *ctx, const apk_pack *md, const apk_rkl2_regs *regs, const apk_diff_cfg *cfg,
+                               const apk_spitzer_cfg *spitzer, const apk_rkl2_coeffs *coeffs, double tau, int first,
+                               apk_stream_t stream);
 
 /* ---- tabular radiative cooling (<cooling> enable_cooling = tabular) -------------------------------------------------
  * Integrator enum: numeric values = position in cooling::CoolIntegrator, tabular_cooling.hpp:96. */

@@ -182,6 +182,10 @@ int apk_sim_get_info(const apk_sim *sim, apk_sim_info *info);
 /* the <diffusion> options as parsed (hydro.cpp:538-702): the processes and coefficients, diffusion/integrator
  * (apk_diffint) and diffusion/cfl (0 when the integrator is none) */
 int apk_sim_diffusion_options(const apk_sim *sim, apk_diff_cfg *cfg, int *integrator, double *cfl_diff);
+/* diffusion/conduction_coeff = spitzer as parsed (hydro.cpp:567-593): *enabled whether Spitzer conduction is on, and
+ * then the converted coefficient (diffusion/spitzer_cond_in_erg_by_s_K_cm, default 4.6e-7, times erg / (s cm) in code
+ * units), mbar and k_boltzmann -- what the driver hands to the *_v2 diffusion entry points; all 0 otherwise */
+int apk_sim_spitzer_options(const apk_sim *sim, int *enabled, apk_spitzer_cfg *cfg);
 /* diffusion/rkl2_max_dt_ratio as parsed (-1 unless diffusion/integrator = rkl2, which requires a positive one) */
 double apk_sim_rkl2_max_dt_ratio(const apk_sim *sim);
 /* super-time-stepping: what the last half step did -- its number of sub-stages and its ratio 2 tau / dt_diff (0 before
