@@ -1,0 +1,374 @@
+// cluster.cpp -- problem_id = cluster in the standalone host driver: the options of ProblemInitPackageData
+// (src/pgen/cluster.cpp:114-250) for the slice built here, what is refused of the rest, the problem generator
+// (cluster.cpp:469-550, 630-653), the per-block origins of the gravity source and the C entries of include/apk_host.h.
+// The model itself (ClusterGravity, ACCEPTEntropyProfile, HydrostaticEquilibriumSphere) is host/cluster_model.cpp.
+#include <cerrno>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+
+#include "cluster.hpp"
+#include "sim_internal.hpp"
+
+namespace apk {
+
+// Units (src/units.hpp:20-47, 99-133): the constants the cluster problem converts its defaults with
+namespace {
+namespace cgs {
+constexpr double kev = 1.60218e-9;                     // erg
+constexpr double km_s = 1e5;                           // cm / s
+constexpr double kpc = 3.0856775809623245e+21;         // cm
+constexpr double mpc = 3.0856775809623245e+24;         // cm
+constexpr double msun = 1.98841586e+33;                // g
+constexpr double gravitational_constant = 6.67408e-08;  // cm^3 / (g s^2)
+}  // namespace cgs
+}  // namespace
+double UnitsState::gravitational_constant() const {
+  return cgs::gravitational_constant / (std::pow(code_length_cgs, 3) / (code_mass_cgs * std::pow(code_time_cgs, 2)));
+}
+double UnitsState::msun() const { return cgs::msun / code_mass_cgs; }
+double UnitsState::kpc() const { return cgs::kpc / code_length_cgs; }
+double UnitsState::mpc() const { return cgs::mpc / code_length_cgs; }
+double UnitsState::km_s() const { return cgs::km_s / (code_length_cgs / code_time_cgs); }
+double UnitsState::kev() const { return cgs::kev / code_energy_cgs(); }
+double UnitsState::g() const { return 1.0 / code_mass_cgs; }
+
+namespace host {
+
+namespace {
+
+const char *kGrav = "problem/cluster/gravity";
+const char *kHse = "problem/cluster/hydrostatic_equilibrium";
+
+[[noreturn]] void refuse(const std::string &key, const std::string &why) {
+  throw std::runtime_error("problem_id = cluster: " + key + " " + why);
+}
+
+// what the cluster generator would do and this path does not: refused, never ignored
+void refuse_unbuilt(apk_sim *s) {
+  ParameterInput &pin = s->pin;
+  const double inf = std::numeric_limits<double>::infinity();
+  if (pin.GetOrAddString("parthenon/mesh", "refinement", "none") != "none")
+    refuse("parthenon/mesh/refinement", "must be none: the cluster problem runs on uniform meshes only (static refinement included)");
+  if (s->mesh.nx[2] == 1) refuse("parthenon/mesh/nx3", "= 1: the cluster problem is three-dimensional");
+  if (s->mesh.nx[1] == 1) refuse("parthenon/mesh/nx2", "= 1: the cluster problem is three-dimensional");
+  if (pin.GetOrAddReal("problem/cluster/agn_feedback", "fixed_power", 0.0) != 0.0)
+    refuse("problem/cluster/agn_feedback/fixed_power", "must be 0: AGN feedback is not implemented");
+  if (pin.DoesBlockExist("problem/cluster/agn_triggering") &&
+      pin.GetOrAddString("problem/cluster/agn_triggering", "triggering_mode", "NONE") != "NONE")
+    refuse("problem/cluster/agn_triggering/triggering_mode", "must be NONE: AGN triggering is not implemented");
+  if (pin.DoesBlockExist("problem/cluster/magnetic_tower"))
+    refuse("problem/cluster/magnetic_tower", "is not implemented: remove the block");
+  if (pin.DoesBlockExist("problem/cluster/stellar_feedback"))
+    refuse("problem/cluster/stellar_feedback", "is not implemented: remove the block");
+  // (the reference's default is ENABLED: the deck has to say that it runs without)
+  if (!pin.GetOrAddBoolean("problem/cluster/snia_feedback", "disabled", false))
+    refuse("problem/cluster/snia_feedback/disabled", "must be true: SNIa feedback is not implemented, and the reference enables it by default");
+  const struct {
+    const char *key;
+    double def;
+  } clips[] = {{"clip_r", -1.0}, {"dfloor", -1.0}, {"vceil", inf}, {"vAceil", inf}, {"Tceil", inf}};
+  for (const auto &c : clips)
+    if (pin.GetOrAddReal("problem/cluster/clips", c.key, c.def) != c.def)
+      refuse(std::string("problem/cluster/clips/") + c.key, "must keep its default: the cluster clips are not implemented");
+  if (pin.GetOrAddReal("problem/cluster/init_perturb", "sigma_v", 0.0) != 0.0)
+    refuse("problem/cluster/init_perturb/sigma_v", "must be 0: initial velocity perturbations are not implemented");
+  if (pin.GetOrAddReal("problem/cluster/init_perturb", "sigma_b", 0.0) != 0.0)
+    refuse("problem/cluster/init_perturb/sigma_b", "must be 0: initial field perturbations are not implemented");
+  if (pin.GetOrAddBoolean("problem/cluster/dipole_b_field", "init_dipole_b_field", false))
+    refuse("problem/cluster/dipole_b_field/init_dipole_b_field", "must be false: the dipole field is not implemented");
+  if (pin.DoesBlockExist("problem/cluster/reductions"))
+    refuse("problem/cluster/reductions", "is not implemented: remove the block");
+}
+
+HeSphere sphere_of(const apk_cluster_options &o) {
+  HeSphere sp;
+  sp.gravity = o.gravity;
+  sp.k_0 = o.k_0, sp.k_100 = o.k_100, sp.r_k = o.r_k, sp.alpha_k = o.alpha_k;
+  sp.mh = o.mh, sp.k_boltzmann = o.k_boltzmann, sp.mu = o.mu, sp.mu_e = o.mu_e;
+  sp.r_fix = o.r_fix, sp.rho_fix = o.rho_fix, sp.r_sampling = o.r_sampling;
+  return sp;
+}
+
+// the block's own radial mesh (generate_P_rho_profile(ib, jb, kb, coords)), cell centres from xc()
+HeProfile block_profile(apk_sim *s, int lb) {
+  LevelDxScope level_dx_scope(s, lb);
+  const Mesh &m = s->mesh;
+  double x0[3];
+  block_origin(s, lb, x0);
+  std::vector<double> x1, x2, x3;
+  for (int i = m.is; i <= m.ie; ++i) x1.push_back(xc(s, x0, 0, i));
+  for (int j = m.js; j <= m.je; ++j) x2.push_back(xc(s, x0, 1, j));
+  for (int k = m.ks; k <= m.ke; ++k) x3.push_back(xc(s, x0, 2, k));
+  return he_generate_block_profile(sphere_of(s->cluster), x1.data(), (int)x1.size(), x2.data(), (int)x2.size(), x3.data(),
+                                   (int)x3.size(), s->dx);
+}
+
+bool sphere_available(const apk_sim *s) { return s->cluster.enabled && s->pkg.units.has_composition; }
+
+}  // namespace
+
+void cluster_initialize(apk_sim *s) {
+  ParameterInput &pin = s->pin;
+  const UnitsState &u = s->pkg.units;
+  apk_cluster_options &o = s->cluster;
+  o = apk_cluster_options{};
+  // a deck of another problem with only its problem_id switched: the generator is known only together with its blocks
+  // (the reference would abort on the first required key, problem/cluster/gravity/gravity_srcterm)
+  if (pin.BlocksWithPrefix("problem/cluster").empty())
+    throw std::runtime_error("unknown job/problem_id: cluster is known only together with its <problem/cluster/...> blocks, and "
+                             "this deck has none (problem/cluster/gravity/gravity_srcterm is required)");
+  refuse_unbuilt(s);
+  o.enabled = 1;
+  o.gravitational_constant = u.gravitational_constant();
+  o.msun = u.msun(), o.kpc = u.kpc(), o.mpc = u.mpc(), o.km_s = u.km_s(), o.kev = u.kev();
+
+  // uniform gas (cluster.cpp:120-136) and uniform field (cluster.cpp:142-154)
+  o.init_uniform_gas = pin.GetOrAddBoolean("problem/cluster/uniform_gas", "init_uniform_gas", false) ? 1 : 0;
+  if (o.init_uniform_gas) {
+    o.uniform_gas_rho = pin.GetReal("problem/cluster/uniform_gas", "rho");
+    o.uniform_gas_ux = pin.GetReal("problem/cluster/uniform_gas", "ux");
+    o.uniform_gas_uy = pin.GetReal("problem/cluster/uniform_gas", "uy");
+    o.uniform_gas_uz = pin.GetReal("problem/cluster/uniform_gas", "uz");
+    o.uniform_gas_pres = pin.GetReal("problem/cluster/uniform_gas", "pres");
+  }
+  o.init_uniform_b_field = pin.GetOrAddBoolean("problem/cluster/uniform_b_field", "init_uniform_b_field", false) ? 1 : 0;
+  if (o.init_uniform_b_field) {
+    if (s->pkg.fluid != APK_FLUID_GLMMHD)
+      refuse("problem/cluster/uniform_b_field/init_uniform_b_field", "needs hydro/fluid = glmmhd");
+    o.uniform_b_field_bx = pin.GetReal("problem/cluster/uniform_b_field", "bx");
+    o.uniform_b_field_by = pin.GetReal("problem/cluster/uniform_b_field", "by");
+    o.uniform_b_field_bz = pin.GetReal("problem/cluster/uniform_b_field", "bz");
+  }
+
+  // ClusterGravity::ClusterGravity (cluster_gravity.hpp:115-165)
+  ClusterGravityInput gi;
+  gi.include_nfw_g = pin.GetOrAddBoolean(kGrav, "include_nfw_g", false);
+  const std::string which_bcg_g_str = pin.GetOrAddString(kGrav, "which_bcg_g", "NONE");
+  if (which_bcg_g_str == "NONE") gi.which_bcg_g = APK_BCG_NONE;
+  else if (which_bcg_g_str == "HERNQUIST") gi.which_bcg_g = APK_BCG_HERNQUIST;
+  else throw std::runtime_error("### FATAL ERROR in function [InitUserMeshData]\nUnknown BCG type " + which_bcg_g_str +
+                                " (problem/cluster/gravity/which_bcg_g)");
+  gi.include_smbh_g = pin.GetOrAddBoolean(kGrav, "include_smbh_g", false);
+  gi.gravitational_constant = o.gravitational_constant;
+  gi.hubble_parameter = pin.GetOrAddReal("problem/cluster", "hubble_parameter", 70 * u.km_s() / u.mpc());
+  gi.m_nfw_200 = pin.GetOrAddReal(kGrav, "m_nfw_200", 8.5e14 * u.msun());
+  gi.c_nfw = pin.GetOrAddReal(kGrav, "c_nfw", 6.81);
+  gi.alpha_bcg_s = pin.GetOrAddReal(kGrav, "alpha_bcg_s", 0.1);
+  gi.beta_bcg_s = pin.GetOrAddReal(kGrav, "beta_bcg_s", 1.43);
+  gi.m_bcg_s = pin.GetOrAddReal(kGrav, "m_bcg_s", 7.5e10 * u.msun());
+  gi.r_bcg_s = pin.GetOrAddReal(kGrav, "r_bcg_s", 4 * u.kpc());
+  gi.m_smbh = pin.GetOrAddReal(kGrav, "m_smbh", 3.4e8 * u.msun());
+  gi.g_smoothing_radius = pin.GetOrAddReal(kGrav, "g_smoothing_radius", 0.0);
+  o.gravity = cluster_gravity_constants(gi);
+  o.include_nfw_g = gi.include_nfw_g, o.which_bcg_g = gi.which_bcg_g, o.include_smbh_g = gi.include_smbh_g;
+  o.hubble_parameter = gi.hubble_parameter;
+  o.m_nfw_200 = gi.m_nfw_200, o.c_nfw = gi.c_nfw, o.alpha_bcg_s = gi.alpha_bcg_s, o.beta_bcg_s = gi.beta_bcg_s;
+  o.m_bcg_s = gi.m_bcg_s, o.r_bcg_s = gi.r_bcg_s, o.m_smbh = gi.m_smbh, o.g_smoothing_radius = gi.g_smoothing_radius;
+  o.gravity_srcterm = pin.GetBoolean(kGrav, "gravity_srcterm") ? 1 : 0;  // (required, cluster.cpp:183-184)
+  if (o.gravity_srcterm && s->pkg.diffint == APK_DIFFINT_RKL2)
+    refuse("problem/cluster/gravity/gravity_srcterm", "= true is not supported with diffusion/integrator = rkl2");
+  if (o.gravity_srcterm && gi.include_nfw_g && !(o.gravity.r_nfw_s > 0.0))
+    refuse("problem/cluster/gravity/m_nfw_200", "and c_nfw must give a positive NFW scale radius");
+  if (o.gravity_srcterm && gi.which_bcg_g == APK_BCG_HERNQUIST && !(gi.r_bcg_s > 0.0))
+    refuse("problem/cluster/gravity/r_bcg_s", "must be positive");
+  s->pkg.gravity_srcterm = o.gravity_srcterm != 0;
+
+  // ACCEPTEntropyProfile (entropy_profiles.hpp:25-34)
+  o.k_0 = pin.GetOrAddReal("problem/cluster/entropy_profile", "k_0", 20 * u.kev() * u.cm() * u.cm());
+  o.k_100 = pin.GetOrAddReal("problem/cluster/entropy_profile", "k_100", 120 * u.kev() * u.cm() * u.cm());
+  o.r_k = pin.GetOrAddReal("problem/cluster/entropy_profile", "r_k", 100 * u.kpc());
+  o.alpha_k = pin.GetOrAddReal("problem/cluster/entropy_profile", "alpha_k", 1.75);
+
+  // HydrostaticEquilibriumSphere (hydrostatic_equilibrium_sphere.cpp:38-87)
+  o.mh = u.mh();
+  o.k_boltzmann = u.k_boltzmann();
+  o.mu = u.mu, o.mu_e = u.mu_e;  // (0 without a composition)
+  o.r_fix = pin.GetOrAddReal(kHse, "r_fix", 1953.9724519818478 * u.kpc());
+  o.rho_fix = pin.GetOrAddReal(kHse, "rho_fix", 8.607065015897638e-30 * u.g() / std::pow(u.kpc(), 3));
+  o.r_sampling = pin.GetOrAddReal(kHse, "r_sampling", 4.0);
+  o.test_he_sphere = pin.GetOrAddBoolean(kHse, "test_he_sphere", false) ? 1 : 0;
+  if (o.test_he_sphere) {
+    o.test_he_sphere_r_start = pin.GetOrAddReal(kHse, "test_he_sphere_r_start", 1e-3 * u.kpc());
+    o.test_he_sphere_r_end = pin.GetOrAddReal(kHse, "test_he_sphere_r_end", 4000 * u.kpc());
+    o.test_he_sphere_n_r = pin.GetOrAddInteger(kHse, "test_he_sphere_n_r", 4000);
+  }
+  if (!o.init_uniform_gas || o.test_he_sphere) {
+    // (the reference reads mu and mu_e from the package and aborts when they are missing, hydrostatic_equilibrium_sphere.cpp:49-50)
+    if (!u.has_composition)
+      refuse("problem/cluster/uniform_gas/init_uniform_gas", "= false: the hydrostatic sphere requires units and gas composition. "
+             "Set a 'units' block and 'hydro/He_mass_fraction' in the input file.");
+    if (!(o.r_sampling > 0.0)) refuse("problem/cluster/hydrostatic_equilibrium/r_sampling", "must be positive");
+    if (!(o.r_k > 0.0)) refuse("problem/cluster/entropy_profile/r_k", "must be positive");
+    if (o.test_he_sphere) {
+      if (o.test_he_sphere_n_r < 2) refuse("problem/cluster/hydrostatic_equilibrium/test_he_sphere_n_r", "must be at least 2");
+      // (as in the reference the profile is generated when the package is built: a deck whose r_fix the test mesh does
+      // not bracket fails here)
+      (void)he_generate_profile(sphere_of(o), o.test_he_sphere_r_start, o.test_he_sphere_r_end, (unsigned)o.test_he_sphere_n_r);
+    }
+  }
+}
+
+// cluster::ProblemGenerator (cluster.cpp:469-550) and, with GLM-MHD, the uniform field (cluster.cpp:630-653; the
+// vector potential of the tower and the dipole is zero here, so its curl adds exact zeros)
+void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u) {
+  const Mesh &m = s->mesh;
+  const apk_cluster_options &o = s->cluster;
+  const bool mhd = s->pkg.fluid == APK_FLUID_GLMMHD;
+  const double gm1 = s->pkg.eos.gamma - 1.0;
+  auto at = [&](int n, int k, int j, int i) -> double & { return u[n * m.sn + k * m.sk + j * m.sj + i]; };
+  double x0[3];
+  block_origin(s, lb, x0);
+  if (o.init_uniform_gas) {
+    const double rho = o.uniform_gas_rho, ux = o.uniform_gas_ux, uy = o.uniform_gas_uy, uz = o.uniform_gas_uz;
+    const double pres = o.uniform_gas_pres;
+    const double Mx = rho * ux, My = rho * uy, Mz = rho * uz;
+    const double E = rho * (0.5 * (ux * ux + uy * uy + uz * uz) + pres / (gm1 * rho));
+    for (int k = m.ks; k <= m.ke; ++k)
+      for (int j = m.js; j <= m.je; ++j)
+        for (int i = m.is; i <= m.ie; ++i) {
+          at(0, k, j, i) = rho;
+          at(1, k, j, i) = Mx;
+          at(2, k, j, i) = My;
+          at(3, k, j, i) = Mz;
+          at(4, k, j, i) = E;
+        }
+  } else {
+    const HeProfile prof = block_profile(s, lb);
+    for (int k = m.ks; k <= m.ke; ++k)
+      for (int j = m.js; j <= m.je; ++j)
+        for (int i = m.is; i <= m.ie; ++i) {
+          const double x1 = xc(s, x0, 0, i), x2 = xc(s, x0, 1, j), x3 = xc(s, x0, 2, k);
+          const double r = std::sqrt(x1 * x1 + x2 * x2 + x3 * x3);
+          const double P_r = prof.P_from_r(r);
+          const double rho_r = prof.rho_from_r(r);
+          at(0, k, j, i) = rho_r;  // zero initial velocity
+          at(4, k, j, i) = P_r / gm1;
+        }
+  }
+  if (mhd && o.init_uniform_b_field) {
+    const double bx = o.uniform_b_field_bx, by = o.uniform_b_field_by, bz = o.uniform_b_field_bz;
+    for (int k = m.ks; k <= m.ke; ++k)
+      for (int j = m.js; j <= m.je; ++j)
+        for (int i = m.is; i <= m.ie; ++i) {
+          at(5, k, j, i) = bx;
+          at(6, k, j, i) = by;
+          at(7, k, j, i) = bz;
+          at(4, k, j, i) += 0.5 * (bx * bx + by * by + bz * bz);
+        }
+  }
+}
+
+// the origins apk_gravity_src takes: every local block's lower interior corner, then the mesh's lower corner
+int cluster_device_setup(apk_sim *s) {
+  const Mesh &m = s->mesh;
+  const int nlb = (int)m.local_gids.size();
+  std::vector<double> h(3 * ((size_t)nlb + 1));
+  for (int lb = 0; lb < nlb; ++lb) {
+    double x0[3];
+    block_origin(s, lb, x0);
+    for (int d = 0; d < 3; ++d) h[3 * (size_t)lb + d] = s->xmin[d] + x0[d] * s->dx[d];
+    // the kernel rebuilds the block's first global index from the corner: the cell centres it then forms must be xc()'s
+    for (int d = 0; d < 3; ++d)
+      if (std::rint((h[3 * (size_t)lb + d] - s->xmin[d]) / s->dx[d]) != x0[d])
+        return fail(s, APK_ERR_INVALID, "cluster gravity: a block's corner does not give back its global cell index");
+  }
+  for (int d = 0; d < 3; ++d) h[3 * (size_t)nlb + d] = s->xmin[d];
+  SIM_TRY(s, dev_alloc(s, "block_xmin", h.size() * sizeof(double), &s->d_block_xmin));
+  SIM_HIP(s, hipMemcpy(s->d_block_xmin, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  return APK_OK;
+}
+
+// PRhoProfile::write_to_ostream (hydrostatic_equilibrium_sphere.cpp:92-119), every number with %.17g
+int cluster_write_test_profile(apk_sim *s, const std::string &path) {
+  const apk_cluster_options &o = s->cluster;
+  if (!o.enabled || !o.test_he_sphere || s->rank != 0) return APK_OK;
+  try {
+    const HeProfile prof = he_generate_profile(sphere_of(o), o.test_he_sphere_r_start, o.test_he_sphere_r_end, (unsigned)o.test_he_sphere_n_r);
+    const size_t n = (size_t)prof.n_r;
+    std::vector<double> col(9 * n);
+    prof.columns(col.data());
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail(s, APK_ERR_INVALID, "cannot open " + path);
+    for (size_t i = 0; i < n; ++i) {
+      for (int c = 0; c < 9; ++c) std::fprintf(f, c ? " %.17g" : "%.17g", col[c * n + i]);
+      std::fprintf(f, "\n");
+    }
+    std::fclose(f);
+  } catch (const std::exception &e) {
+    return fail(s, APK_ERR_INVALID, e.what());
+  }
+  return APK_OK;
+}
+
+}  // namespace host
+}  // namespace apk
+
+using namespace apk;
+using namespace apk::host;
+
+extern "C" {
+
+int apk_sim_cluster_options(const apk_sim *s, apk_cluster_options *opt) {
+  if (!s || !opt) return APK_ERR_INVALID;
+  *opt = s->cluster;
+  return APK_OK;
+}
+
+int apk_sim_he_sphere_profile(apk_sim *s, double r_start, double r_end, int n_r, double *out) {
+  if (!s || !out) return APK_ERR_INVALID;
+  if (!sphere_available(s)) return fail(s, APK_ERR_INVALID, "he_sphere_profile needs problem_id = cluster with units and gas composition");
+  if (n_r < 2) return fail(s, APK_ERR_INVALID, "he_sphere_profile: n_r must be at least 2");
+  try {
+    he_generate_profile(sphere_of(s->cluster), r_start, r_end, (unsigned)n_r).columns(out);
+  } catch (const std::exception &e) {
+    return fail(s, APK_ERR_INVALID, e.what());
+  }
+  return APK_OK;
+}
+
+int apk_sim_block_he_profile(apk_sim *s, int lb, double *r, double *p, int n, int *size) {
+  if (!s || !size || lb < 0 || lb >= (int)s->mesh.local_gids.size()) return APK_ERR_INVALID;
+  if (!sphere_available(s)) return fail(s, APK_ERR_INVALID, "block_he_profile needs problem_id = cluster with units and gas composition");
+  try {
+    const HeProfile prof = block_profile(s, lb);
+    *size = prof.n_r;
+    for (int i = 0; i < n && i < prof.n_r; ++i) {
+      if (r) r[i] = prof.r[i];
+      if (p) p[i] = prof.p[i];
+    }
+  } catch (const std::exception &e) {
+    return fail(s, APK_ERR_INVALID, e.what());
+  }
+  return APK_OK;
+}
+
+int apk_sim_pgen_block(apk_sim *s, int lb, double *out) {
+  if (!s || !out || lb < 0 || lb >= (int)s->mesh.local_gids.size()) return APK_ERR_INVALID;
+  if (s->problem_id == "turbulence") return fail(s, APK_ERR_INVALID, "the turbulence generator fills all blocks at once");
+  const Mesh &m = s->mesh;
+  try {
+    std::vector<double> u((size_t)m.nvar * m.sn);
+    pgen_block(s, lb, u);
+    size_t q = 0;
+    for (int n = 0; n < m.nvar; ++n)
+      for (int k = m.ks; k <= m.ke; ++k)
+        for (int j = m.js; j <= m.je; ++j)
+          for (int i = m.is; i <= m.ie; ++i) out[q++] = u[n * m.sn + k * m.sk + j * m.sj + i];
+  } catch (const std::exception &e) {
+    return fail(s, APK_ERR_INVALID, e.what());
+  }
+  return APK_OK;
+}
+
+int apk_sim_gravity_src(apk_sim *s, double beta_dt) {
+  if (!s || s->host_only) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "gravity_src needs problem_id = cluster with problem/cluster/gravity/gravity_srcterm = true");
+  SIM_TRY(s, sync_ghosts(s));  // (materialises the stored primitives when the cycle kept them out of memory)
+  SIM_TRY(s, apk_gravity_src(s->ctx, s->mu0(), &s->cluster.gravity, s->d_block_xmin, beta_dt, s->stream));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+}  // extern "C"

@@ -373,8 +373,8 @@ int ensure_flux_arrays(apk_sim *s) {
 bool stage_can_fuse(const apk_sim *s) {
   // (refined meshes included: the coarse-fine flux correction is applied after the fused stage from
   // boundary-plane fluxes, see amr_flux_fix)
-  // (diffusion: the stages run through the flux arrays, whose face fluxes the diffusive ones are added to; cooling: the
-  // source acts between the update and ConsToPrim, which the fused stages do in one sweep)
+  // (diffusion: the stages run through the flux arrays, whose face fluxes the diffusive ones are added to; cooling and
+  // the cluster's gravity: the source acts between the update and ConsToPrim, which the fused stages do in one sweep)
   return s->fused && !s->pkg.first_order_flux_correct && s->pkg.riemann != APK_RS_NONE &&
          s->pkg.riemann != APK_RS_LLF && !s->pkg.flux_path_sources();
 }
@@ -757,6 +757,7 @@ int create_common(const char *deck, const char *const *overrides, int noverrides
       throw std::runtime_error("Only hydro runs are supported for LW implosion problem generator.");
     else if (s->problem_id == "turbulence") turbulence_setup(s);
     else if (s->problem_id == "diffusion") diffusion_check(s);
+    else if (s->problem_id == "cluster") cluster_initialize(s);
     else if (s->problem_id != "sod" && s->problem_id != "orszag_tang" && s->problem_id != "synthetic" &&
              s->problem_id != "blast" && s->problem_id != "lw_implode" && s->problem_id != "cpaw" &&
              s->problem_id != "advection" && s->problem_id != "field_loop" && s->problem_id != "kh" &&
@@ -881,6 +882,7 @@ int apk_sim_create(const char *deck, const char *const *overrides, int noverride
   if (s->mesh.ndim == 3 && (rc = build_face_table(s)) != APK_OK) return bail(rc);
   if (s->fmft && (rc = turbulence_device_setup(s)) != APK_OK) return bail(rc);
   if (s->tracers && (rc = tracers_device_setup(s)) != APK_OK) return bail(rc);
+  if (s->pkg.gravity_srcterm && (rc = cluster_device_setup(s)) != APK_OK) return bail(rc);
   return APK_OK;
 }
 
@@ -921,6 +923,7 @@ void apk_sim_destroy(apk_sim *s) {
     tracers_free(s);
     dev_free(s, s->d_acc);
     dev_free(s, s->d_phases);
+    dev_free(s, s->d_block_xmin);
     dev_free(s, s->d_cons2[0]);
     dev_free(s, s->d_prim2[0]);
     dev_free(s, s->d_prim2[1]);
@@ -1573,6 +1576,8 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
   } csv_scope{s};
   if (s->tracers && s->tracers->lookback) s->tracers->csv_path = std::string(outdir) + "/correlations.csv";
   SIM_TRY(s, apk_sim_initialize(s));
+  // problem/cluster/hydrostatic_equilibrium/test_he_sphere: the reference writes the file when it builds the package
+  SIM_TRY(s, cluster_write_test_profile(s, std::string(outdir) + "/test_he_sphere.dat"));
   // the tracers next to every history row: <history file without .hst>.<row, 5 digits>.tracers.<field>.npy
   auto write_tracers = [&](HstOut &o) -> int {
     if (!s->tracers) return APK_OK;

@@ -27,6 +27,8 @@ struct UnitsState {
   double code_energy_cgs() const;
   // constants and scales in code units
   double k_boltzmann() const, mh() const, atomic_mass_unit() const, erg() const, cm() const, s() const;
+  // (what the cluster problem converts its defaults with, host/cluster.cpp)
+  double gravitational_constant() const, msun() const, kpc() const, mpc() const, km_s() const, kev() const, g() const;
 };
 
 // "Hydro" StateDescriptor params (names as in hydro.cpp)
@@ -81,7 +83,9 @@ struct HydroPackage {
   CoolingTableHost cool_table;
   double cool_table_hash = 0.0;
   // the unsplit sources that run through the flux-array stage path (no fused stage forms with them)
-  bool flux_path_sources() const { return diffusion_configured() || cooling; }
+  // problem/cluster/gravity/gravity_srcterm: the static field acts as the problem's unsplit source (host/cluster.cpp)
+  bool gravity_srcterm = false;
+  bool flux_path_sources() const { return diffusion_configured() || cooling || gravity_srcterm; }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -167,6 +171,8 @@ struct apk_sim {
   apk::LinearWaveMhdState lwm;
   apk::CpawState cpaw;
   apk::FieldLoopState floop;
+  apk_cluster_options cluster{};     // problem_id = cluster as parsed (host/cluster.cpp)
+  double *d_block_xmin = nullptr;    // [nblocks + 1][3]: what apk_gravity_src takes (allocated with gravity_srcterm)
   bool host_only = false;
   bool fused = true;
   int rank = 0, nranks = 1;

@@ -51,6 +51,10 @@ void diffusion_initialize(apk_sim *s);  // <diffusion>, called by hydro_initiali
 void units_initialize(apk_sim *s);      // <units> and hydro/He_mass_fraction (host/cooling.cpp)
 void cooling_initialize(apk_sim *s);    // <cooling> (host/cooling.cpp), called by hydro_initialize
 void mesh_initialize(apk_sim *s);
+void cluster_initialize(apk_sim *s);    // problem_id = cluster (host/cluster.cpp), called at creation after the mesh is known
+void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u);  // its generator, called by pgen_block
+int cluster_device_setup(apk_sim *s);   // the per-block origins of the gravity source
+int cluster_write_test_profile(apk_sim *s, const std::string &path);  // test_he_sphere.dat
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);
 void dev_free(apk_sim *s, double *p);
 int build_packs(apk_sim *s);

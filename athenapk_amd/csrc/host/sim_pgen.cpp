@@ -396,6 +396,10 @@ void pgen_block(apk_sim *s, int lb, std::vector<double> &u) {
   const bool mhd = pkg.fluid == APK_FLUID_GLMMHD;
   const double gm1 = pkg.eos.gamma - 1.0;
   ParameterInput &pin = s->pin;
+  if (s->problem_id == "cluster") {  // src/pgen/cluster.cpp:469-550 (host/cluster.cpp)
+    cluster_pgen_block(s, lb, u);
+    return;
+  }
   double sod[7] = {0};
   if (s->problem_id == "sod") {  // src/pgen/sod.cpp:24-30
     sod[0] = pin.GetOrAddReal("problem/sod", "rho_l", 1.0);

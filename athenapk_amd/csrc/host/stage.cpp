@@ -802,6 +802,10 @@ static int run_flux_array_stage(apk_sim *s, const Stage &st) {
   // the other unsplit source (AddUnsplitSources, hydro.cpp:227-246): after the update and the Dedner source, before
   // the exchange and ConsToPrim of the stage (and before the turbulence kick of the last stage)
   if (pkg.cooling) SIM_TRY(s, apk_tabular_cooling_src(s->ctx, s->mu0(), s->cool_tab, pkg.fluid, st.beta_dt, s->stream));
+  // ProblemSourceUnsplit comes last (hydro.cpp:241-243): the cluster's static gravity (cluster.cpp:63-74), with the
+  // density and velocity of the stage's input -- the primitives this pack still holds
+  if (pkg.gravity_srcterm)
+    SIM_TRY(s, apk_gravity_src(s->ctx, s->mu0(), &s->cluster.gravity, s->d_block_xmin, st.beta_dt, s->stream));
   return APK_OK;
 }
 

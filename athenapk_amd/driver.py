@@ -104,6 +104,47 @@ class _FmftHost:
         return out
 
 
+class _ClusterHost:
+    """The cluster problem's host model (job/problem_id = cluster; csrc/host/cluster.cpp); works on host-only sims too."""
+
+    HE_COLUMNS = ("r", "P", "K", "rho", "n", "ne", "T", "g", "dP_dr")
+
+    def _cluster_check(self, rc):
+        if rc != L.APK_OK:
+            raise L.ApkError(rc, self.lib.apk_sim_last_error(self.h).decode())
+
+    def cluster_options(self):
+        """lib.ClusterOptions: the parsed flags and parameters of <problem/cluster/...>, the constants of src/units.hpp
+        in code units, and `gravity`, the lib.ClusterGravity constants apk_gravity_src takes"""
+        o = L.ClusterOptions()
+        self._cluster_check(self.lib.apk_sim_cluster_options(self.h, C.byref(o)))
+        return o
+
+    def he_sphere_profile(self, r_start, r_end, n_r):
+        """the hydrostatic sphere integrated on n_r equidistant radii: a dict of the columns of the reference's
+        test_he_sphere.dat, r, P, K, rho, n, ne, T, g, dP_dr"""
+        out = np.zeros((9, int(n_r)))
+        self._cluster_check(self.lib.apk_sim_he_sphere_profile(self.h, float(r_start), float(r_end), int(n_r),
+                                                               out.ctypes.data_as(L.c_dp)))
+        return dict(zip(self.HE_COLUMNS, out))
+
+    def block_he_profile(self, lb):
+        """(r, P) of the radial mesh local block lb integrates for its own initial state"""
+        size = C.c_int(0)
+        self._cluster_check(self.lib.apk_sim_block_he_profile(self.h, int(lb), None, None, 0, C.byref(size)))
+        r, p = np.zeros(size.value), np.zeros(size.value)
+        self._cluster_check(self.lib.apk_sim_block_he_profile(self.h, int(lb), r.ctypes.data_as(L.c_dp),
+                                                              p.ctypes.data_as(L.c_dp), size.value, C.byref(size)))
+        return r, p
+
+    def pgen_block(self, lb):
+        """the problem generator's conserved state of local block lb, interior cells: [nvar][nx3][nx2][nx1] of the block"""
+        nf = self.info
+        out = np.zeros((nf.nhydro + nf.nscalars, nf.mb[2], nf.mb[1], nf.mb[0]))
+        self._cluster_check(self.lib.apk_sim_pgen_block(self.h, int(lb), out.ctypes.data_as(L.c_dp)))
+        return out
+
+
 class _MeshView:
     """Block placement and ghost-exchange plans of a sim handle (valid without a GPU)."""
 
@@ -186,7 +227,7 @@ class _MeshView:
         return self.info
 
 
-class Simulation(_FmftHost, _MeshView):
+class Simulation(_FmftHost, _ClusterHost, _MeshView):
     """apk_sim: deck + overrides -> mesh partition, packs, ghost plans, stage loop (C++).
 
     COLLECTIVE accessors on N > 1 ranks: read_block / write_block / gather / history / turbulence_history / reldivb and
@@ -624,6 +665,12 @@ class Simulation(_FmftHost, _MeshView):
         unless diffusion/conduction_coeff = spitzer"""
         return _spitzer_options(self.lib, self.h)
 
+    def gravity_src(self, beta_dt):
+        """the cluster problem's gravity source (apk_gravity_src) once on the current state: conserved momentum and
+        energy of the interior cells, with the density and velocity of the stored primitives"""
+        self._check(self.lib.apk_sim_gravity_src(self.h, float(beta_dt)))
+        return self
+
     def reset_time_step(self):
         """after write_block + exchange_ghosts + fill_derived: the time step as initialize() derives it"""
         self._check(self.lib.apk_sim_reset_time_step(self.h))
@@ -784,7 +831,7 @@ def _tracers_read(lib, h, names):
     return {name: raw[name][order] for name in raw}
 
 
-class HostPlan(_FmftHost, _MeshView):
+class HostPlan(_FmftHost, _ClusterHost, _MeshView):
     """Host-only view of a rank's mesh partition and ghost-exchange plan (no GPU needed)."""
 
     def __init__(self, deck, overrides=(), rank=0, nranks=1, strict=False):

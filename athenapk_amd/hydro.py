@@ -536,6 +536,34 @@ class TabularCooling:
         return out.cpu().numpy(), valid.cpu().numpy().astype(bool)
 
 
+def make_cluster_gravity(include_nfw=False, which_bcg="NONE", include_smbh=False, r_nfw_s=1.0, g_const_nfw=0.0,
+                         r_bcg_s=1.0, g_const_bcg=0.0, g_const_smbh=0.0, smoothing_r=0.0):
+    """lib.ClusterGravity: ClusterGravity's members in code units (cluster_gravity.hpp:29-53)"""
+    return L.ClusterGravity(int(bool(include_nfw)), L.CLUSTER_BCG[which_bcg], int(bool(include_smbh)), float(r_nfw_s),
+                            float(g_const_nfw), float(r_bcg_s), float(g_const_bcg), float(g_const_smbh),
+                            float(smoothing_r))
+
+
+def ClusterGFromR(ctx, gravity, r):
+    """ClusterGravity::g_from_r(r) -- cluster_gravity.hpp:173-201, pointwise on the device: a numpy array"""
+    tr = torch.from_numpy(np.ascontiguousarray(r, dtype=np.float64).ravel()).to(torch.device("cuda"))
+    out = torch.empty_like(tr)
+    _check(ctx.lib.apk_gravity_g_from_r(ctx.h, C.byref(gravity), tr.data_ptr(), out.data_ptr(), tr.numel(), _stream()),
+           ctx.lib, ctx.h)
+    return out.cpu().numpy()
+
+
+def GravitationalFieldSrcTerm(md, gravity, block_xmin, beta_dt):
+    """GravitationalFieldSrcTerm(md, beta_dt, gravity) -- gravitational_field.hpp:25-64 on md.cons with md.prim.
+    block_xmin: [nblocks + 1][3], the blocks' lower interior corners and, last, the mesh's lower corner"""
+    ctx = md.ctx
+    bx = np.ascontiguousarray(block_xmin, dtype=np.float64)
+    assert bx.shape == (md.nblocks + 1, 3)
+    t = torch.from_numpy(bx).to(torch.device("cuda"))
+    _check(ctx.lib.apk_gravity_src(ctx.h, md.h, C.byref(gravity), t.data_ptr(), float(beta_dt), _stream()), ctx.lib, ctx.h)
+    torch.cuda.current_stream().synchronize()  # (t is released on return)
+
+
 def FirstOrderFluxCorrect(u0, u1, fluid, eos, c_h, gam0, gam1, beta_dt):
     """Hydro::FirstOrderFluxCorrect<fluid>(u0,u1,gam0,gam1,beta_dt) -- hydro.cpp:1223"""
     ctx = u0.ctx

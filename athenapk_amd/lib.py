@@ -27,7 +27,7 @@ APK_FLAG_COOL_MAX_ITER = 4
 APK_FLAG_COOL_TABLE = 8
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
-                "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort")
+                "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort", "gravity")
 
 APK_OK = 0
 APK_RCCL_ID_BYTES = 128
@@ -96,6 +96,32 @@ def make_cooling_params(integrator="rk12", max_iter=100, cfl=0.1, d_log_temp_tol
     return CoolingParams(COOL_INTEGRATOR[integrator], int(max_iter), float(cfl), float(d_log_temp_tol), float(d_e_tol),
                          float(T_floor), float(lambda_units), float(gamma), float(mbar_over_kb), float(He_mass_fraction),
                          float(mh))
+
+
+# which_bcg_g of the cluster problem (apk_cluster_bcg; cluster::BCG)
+CLUSTER_BCG = {"NONE": 0, "HERNQUIST": 1}
+
+
+class ClusterGravity(C.Structure):
+    """apk_cluster_gravity: ClusterGravity's members in code units (cluster_gravity.hpp:29-53)"""
+    _fields_ = [("include_nfw", C.c_int), ("which_bcg", C.c_int), ("include_smbh", C.c_int), ("r_nfw_s", C.c_double),
+                ("g_const_nfw", C.c_double), ("r_bcg_s", C.c_double), ("g_const_bcg", C.c_double),
+                ("g_const_smbh", C.c_double), ("smoothing_r", C.c_double)]
+
+
+class ClusterOptions(C.Structure):
+    """apk_cluster_options: problem_id = cluster as parsed (include/apk_host.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("enabled", "include_nfw_g", "which_bcg_g", "include_smbh_g", "gravity_srcterm",
+                                        "init_uniform_gas", "init_uniform_b_field", "test_he_sphere",
+                                        "test_he_sphere_n_r")] +
+                [(n, C.c_double) for n in ("hubble_parameter", "m_nfw_200", "c_nfw", "alpha_bcg_s", "beta_bcg_s", "m_bcg_s",
+                                           "r_bcg_s", "m_smbh", "g_smoothing_radius", "k_0", "k_100", "r_k", "alpha_k",
+                                           "r_fix", "rho_fix", "r_sampling", "test_he_sphere_r_start",
+                                           "test_he_sphere_r_end", "uniform_gas_rho", "uniform_gas_ux", "uniform_gas_uy",
+                                           "uniform_gas_uz", "uniform_gas_pres", "uniform_b_field_bx",
+                                           "uniform_b_field_by", "uniform_b_field_bz", "mh", "k_boltzmann", "mu", "mu_e",
+                                           "gravitational_constant", "msun", "kpc", "mpc", "km_s", "kev")] +
+                [("gravity", ClusterGravity)])
 
 
 class UnitsInfo(C.Structure):
@@ -291,6 +317,8 @@ def _signatures():
         "apk_cooling_dedt": (i, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
         "apk_tabular_cooling_src": (i, [vp, vp, vp, i, d, vp]),
         "apk_estimate_cooling_timestep": (i, [vp, vp, vp, c_dp, vp]),
+        "apk_gravity_src": (i, [vp, vp, C.POINTER(ClusterGravity), vp, d, vp]),
+        "apk_gravity_g_from_r": (i, [vp, C.POINTER(ClusterGravity), vp, vp, C.c_int64, vp]),
         "apk_first_order_flux_correct": (i, [vp, vp, vp, i, E, d, d, d, d, C.POINTER(ll), vp]),
         "apk_count_unphysical": (i, [vp, vp, i, C.POINTER(ll), vp]),
         "apk_history": (i, [vp, vp, i, c_dp, vp]),
@@ -372,6 +400,11 @@ def _signatures():
         "apk_sim_units": (i, [vp, C.POINTER(UnitsInfo)]),
         "apk_sim_cooling_options": (i, [vp, C.POINTER(C.c_int), C.POINTER(CoolingParams), C.POINTER(C.c_int)]),
         "apk_sim_cooling_table": (i, [vp, i, c_dp, i, C.POINTER(C.c_int)]),
+        "apk_sim_cluster_options": (i, [vp, C.POINTER(ClusterOptions)]),
+        "apk_sim_he_sphere_profile": (i, [vp, d, d, i, c_dp]),
+        "apk_sim_block_he_profile": (i, [vp, i, c_dp, c_dp, i, C.POINTER(C.c_int)]),
+        "apk_sim_pgen_block": (i, [vp, i, c_dp]),
+        "apk_sim_gravity_src": (i, [vp, d]),
         "apk_sim_tracers_options": (i, [vp, C.POINTER(TracersOptions)]),
         "apk_sim_tracers_count": (i, [vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ll)]),
         "apk_sim_tracers_stats": (i, [vp, C.POINTER(ll), C.POINTER(ll)]),

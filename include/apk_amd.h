@@ -882,6 +882,29 @@ int apk_tracers_step_fused_lookback(apk_ctx *ctx, const apk_pack *md, const apk_
                                     const apk_tracer_geom *geom, double dt, unsigned long long *counters, long long cycle,
                                     double *partials, long long npartials_cap, double *sums26, apk_stream_t stream);
 
+/* ---- static gravity of the cluster problem (src/pgen/cluster/cluster_gravity.hpp) -----------------------------------
+ * ClusterGravity's members in code units: which components act, and their constants with G and the masses rolled in
+ * (the constructor's arithmetic is done by the host, csrc/host/cluster.cpp). */
+enum apk_cluster_bcg { APK_BCG_NONE = 0, APK_BCG_HERNQUIST = 1 };
+typedef struct apk_cluster_gravity {
+  int include_nfw, which_bcg, include_smbh;
+  double r_nfw_s, g_const_nfw, r_bcg_s, g_const_bcg, g_const_smbh, smoothing_r;
+} apk_cluster_gravity;
+
+/* Replaces GravitationalFieldSrcTerm<ClusterGravity> (src/hydro/srcterms/gravitational_field.hpp:25-64), called with
+ * beta_dt by ProblemSourceUnsplit, the last of AddUnsplitSources (hydro.cpp:227-246).  Interior cells of every block:
+ *   r = sqrt(x^2 + y^2 + z^2), src = (r == 0) ? 0 : beta_dt * prim.rho * g_from_r(r) / r,
+ *   cons.M_d -= src * x_d, cons.E -= src * (x vx + y vy + z vz)      (rho, v: md's stored primitives)
+ * block_xmin: device, [nblocks + 1][3] -- rows 0 .. nblocks-1 the lower interior corner of each block, the last row the
+ * lower corner of the whole mesh.  The centre of interior cell i_d of a block is the number the host's generators use,
+ *   x_d = xmin_d + ((g_d + i_d) + 1/2) dx_d,   g_d = rint((corner_d - xmin_d) / dx_d) the block's first global cell,
+ * which is corner_d + (i_d + 1/2) dx_d up to rounding (and exactly that for the blocks at the mesh's lower corner). */
+int apk_gravity_src(apk_ctx *ctx, const apk_pack *md, const apk_cluster_gravity *gravity, const double *block_xmin,
+                    double beta_dt, apk_stream_t stream);
+/* ClusterGravity::g_from_r (cluster_gravity.hpp:173-201) at n radii: device arrays r -> g.  For tests. */
+int apk_gravity_g_from_r(apk_ctx *ctx, const apk_cluster_gravity *gravity, const double *r, double *g, int64_t n,
+                         apk_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
  * they are launched on.  When enabled, every kernel launch of the listed groups is
@@ -902,7 +925,8 @@ enum apk_timing_slot {
   APK_T_FUSED_DC_X3 = 11, /* only the high-order stages                                    */
   APK_T_TRACERS = 12,     /* tracer particles: advect, re-own, fill (or the fused step), lookbacks */
   APK_T_TRACER_SORT = 13, /* ... and their counting sort (memset, histogram, scan, scatter) */
-  APK_T_COUNT = 14
+  APK_T_GRAVITY = 14,     /* the static gravity source (apk_gravity_src) */
+  APK_T_COUNT = 15
 };
 int apk_kernel_timing_enable(apk_ctx *ctx, int on);
 /* total_ms / launches may be NULL */

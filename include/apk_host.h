@@ -208,6 +208,44 @@ int apk_sim_cooling_options(const apk_sim *sim, int *enabled, apk_cooling_params
 /* one array of the parsed table: which = 0 log_temps, 1 log_lambdas (code units), 2 Townsend alpha_k, 3 Townsend Y_k
  * (n_temp - 1 entries; townsend only); copies min(n, size) values into out, *size = the array's length */
 int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int *size);
+/* ---- the cluster problem (job/problem_id = cluster; src/pgen/cluster.cpp, csrc/host/cluster.cpp) ------------------
+ * The slice built here: static gravity (NFW + Hernquist BCG + SMBH) as an unsplit source, the ACCEPT-like entropy
+ * profile and the hydrostatic-equilibrium sphere, or uniform gas; a uniform field with GLM-MHD.  Keys and defaults are
+ * the reference's (<problem/cluster>, .../gravity, .../entropy_profile, .../hydrostatic_equilibrium, .../uniform_gas,
+ * .../uniform_b_field).  Refused at creation, each with a message naming the key: refined meshes, nx2 = 1 or nx3 = 1,
+ * agn_feedback/fixed_power != 0, agn_triggering other than NONE, magnetic_tower, stellar_feedback, snia_feedback unless
+ * disabled = true, any clips key off its default, init_perturb/sigma_v or sigma_b != 0, dipole_b_field, reductions, the
+ * sphere without <units> and hydro/He_mass_fraction, uniform_b_field without GLM-MHD, gravity_srcterm with
+ * diffusion/integrator = rkl2.  All entries below work on a host-only sim. */
+typedef struct apk_cluster_options {
+  int enabled; /* problem_id = cluster */
+  int include_nfw_g, which_bcg_g, include_smbh_g, gravity_srcterm;
+  int init_uniform_gas, init_uniform_b_field, test_he_sphere, test_he_sphere_n_r;
+  double hubble_parameter;
+  double m_nfw_200, c_nfw, alpha_bcg_s, beta_bcg_s, m_bcg_s, r_bcg_s, m_smbh, g_smoothing_radius;
+  double k_0, k_100, r_k, alpha_k;
+  double r_fix, rho_fix, r_sampling, test_he_sphere_r_start, test_he_sphere_r_end;
+  double uniform_gas_rho, uniform_gas_ux, uniform_gas_uy, uniform_gas_uz, uniform_gas_pres;
+  double uniform_b_field_bx, uniform_b_field_by, uniform_b_field_bz;
+  double mh, k_boltzmann, mu, mu_e; /* what the sphere takes from Units and the composition (0 without them) */
+  /* src/units.hpp in code units */
+  double gravitational_constant, msun, kpc, mpc, km_s, kev;
+  apk_cluster_gravity gravity; /* ClusterGravity's members */
+} apk_cluster_options;
+int apk_sim_cluster_options(const apk_sim *sim, apk_cluster_options *opt);
+/* HydrostaticEquilibriumSphere::generate_P_rho_profile(r_start, r_end, n_r) and the columns PRhoProfile::
+ * write_to_ostream derives from it: out[9][n_r] = r, P, K, rho, n, ne, T, g, dP_dr */
+int apk_sim_he_sphere_profile(apk_sim *sim, double r_start, double r_end, int n_r, double *out);
+/* the radial mesh local block lb integrates for itself (generate_P_rho_profile(ib, jb, kb, coords)): copies min(n,
+ * size) values into r and p, *size = its length */
+int apk_sim_block_he_profile(apk_sim *sim, int lb, double *r, double *p, int n, int *size);
+/* the problem generator's conserved state of local block lb, interior cells only: out[nvar][nx3][nx2][nx1] of the
+ * block (every generator that fills block by block; not turbulence) */
+int apk_sim_pgen_block(apk_sim *sim, int lb, double *out);
+/* apk_gravity_src once on the current state with the given beta_dt (conserved state and stored primitives of the
+ * current buffers).  For tests. */
+int apk_sim_gravity_src(apk_sim *sim, double beta_dt);
+
 /* ---- tracer particles (<tracers>, src/tracers/tracers.cpp; csrc/host/tracers.cpp) ---------------------------------
  * Keys (tracers.cpp:43-93, 102-118): enabled (default false), initial_seed_method = none | random_per_block | user,
  * initial_num_tracers_per_cell, initial_rng_seed; and apk_amd/tracer_step = fused (default) | passes.  Refused at
