@@ -204,7 +204,7 @@ int launch_copy_regions(const apk_copy_plan &plan, hipStream_t s, int c2p_fluid 
                         unsigned *d_flags = nullptr, int64_t prim_delta = 0, bool prim_only = false);
 // fused stage path (fused_dispatch.hip)
 int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
-                       const apk_stage_args &a, double dedner_coeff, hipStream_t s);
+                       const apk_stage_args &a, double dedner_coeff, hipStream_t s, const char *&why);
 
 // +max into the stage's time-step word (word 4) before a kernel reduces into it -- unless the stream already holds it
 int prepare_dt_word(apk_ctx *ctx, hipStream_t s);

@@ -7,7 +7,8 @@
 #include <new>
 
 #include "apk_internal.hpp"
-#include "fused_kernel.hpp"
+#include "hydro_math.hpp"
+#include "stage_form.hpp"
 
 using namespace apk;
 
@@ -16,6 +17,18 @@ namespace {
 hipStream_t as_stream(apk_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 bool valid_eos(const apk_eos *e) { return e && e->gamma > 1.0; }
+
+// what is wrong with the shape of a pack, or NULL
+const char *bad_pack_geometry(const apk_pack_desc &d) {
+  if (d.nblocks <= 0) return "empty pack";
+  if (d.nhydro != 5 && d.nhydro != 9) return "nhydro must be 5 or 9";
+  if (d.nscalars < 0 || d.ng < 1 || d.nx[0] < 1 || d.nx[1] < 1 || d.nx[2] < 1) return "bad pack geometry";
+  if (d.nx[1] == 1 && d.nx[2] > 1) return "nx2 == 1 requires nx3 == 1";
+  const PackView t = make_view(d, nullptr);  // (explicit strides: no array may overlap the next one)
+  if (d.stride[0] < 0 || d.stride[1] < 0 || d.stride[2] < 0 || t.sj < t.ni || t.sk < t.sj * t.nj || t.sn < t.sk * t.nk)
+    return "pack strides smaller than the extents they step over";
+  return nullptr;
+}
 
 // registry of compiled-in flux functions: src/hydro/hydro.cpp:386-416
 bool in_registry(const apk_flux_cfg &c) {
@@ -36,13 +49,48 @@ int need_nghost(int recon) {  // src/hydro/hydro.cpp:316-339
   }
 }
 
-int check_cfg(apk_ctx *ctx, const apk_pack *md, const apk_flux_cfg &cfg) {
-  if (!in_registry(cfg)) return set_err(ctx, APK_ERR_UNSUPPORTED, "flux function not in registry");
+int cfg_status(const PackView &v, const apk_flux_cfg &cfg, const char *&why) {
   const int nh = (cfg.fluid == APK_FLUID_EULER) ? 5 : 9;
-  if (md->view.nhydro != nh) return set_err(ctx, APK_ERR_INVALID, "pack nhydro does not match fluid");
-  if (md->view.ng < need_nghost(cfg.recon))
-    return set_err(ctx, APK_ERR_NGHOST, "need more ghost zones for chosen reconstruction");
+  if (!in_registry(cfg)) return why = "flux function not in registry", APK_ERR_UNSUPPORTED;
+  if (v.nhydro != nh) return why = "pack nhydro does not match fluid", APK_ERR_INVALID;
+  if (v.ng < need_nghost(cfg.recon)) return why = "need more ghost zones for chosen reconstruction", APK_ERR_NGHOST;
   return APK_OK;
+}
+int check_cfg(apk_ctx *ctx, const apk_pack *md, const apk_flux_cfg &cfg) {
+  const char *why = "";
+  const int rc = cfg_status(md->view, cfg, why);
+  return rc == APK_OK ? rc : set_err(ctx, rc, why);
+}
+
+// apk_stage_fused's checks of its arguments against the shape of the pack (what needs the blocks' pointers stays there)
+int stage_args_status(const PackView &v, const apk_stage_args &a, const char *&why) {
+  if (!valid_eos(&a.eos)) return why = "apk_stage_fused: bad argument", APK_ERR_INVALID;
+  const int rc = cfg_status(v, a.cfg, why);
+  if (rc != APK_OK) return rc;
+  if (a.cfg.riemann == APK_RS_NONE || a.cfg.riemann == APK_RS_LLF)
+    return why = "fused stage: none/llf solvers use the flux-array path", APK_ERR_UNSUPPORTED;
+  if (a.dedner != 0 && (a.cfg.fluid != APK_FLUID_GLMMHD || !(a.mindx > 0.0)))
+    return why = "fused stage: Dedner source needs glmmhd and mindx > 0", APK_ERR_INVALID;
+  if (a.phase < 0 || a.phase > 2 || (a.phase == 1) != (a.window != nullptr) ||
+      (a.phase == 1 && (a.window_rl < 3 || a.window_rl > v.ni || a.window_rows < 1 || a.window_rows > v.nx2)))
+    return why = "fused stage: phase / window mismatch", APK_ERR_INVALID;
+  if (a.phase == 1 && a.estimate_dt && a.cfg.recon == APK_RC_DC && v.ndim == 3)
+    return why = "fused stage: estimate_dt is not available in a split 3-D donor-cell stage", APK_ERR_UNSUPPORTED;
+  if (a.fill_derived < 0 || a.fill_derived > 3) return why = "fused stage: fill_derived must be 0, 1, 2 or 3", APK_ERR_INVALID;
+  if (a.fill_derived == 3 && !a.estimate_dt)
+    return why = "fused stage: fill_derived = 3 (primitives for the time-step estimate only) needs estimate_dt", APK_ERR_INVALID;
+  if (a.prim_from_cons < 0 || a.prim_from_cons > 2) return why = "fused stage: prim_from_cons must be 0, 1 or 2", APK_ERR_INVALID;
+  if (a.prim_from_cons == 2 && a.cons_out_delta == 0)
+    return why = "fused stage: prim_from_cons = 2 (input = u0.cons) needs an out-of-place result (cons_out_delta)", APK_ERR_INVALID;
+  return APK_OK;
+}
+
+// the pack of a hypothetical stage for the legacy queries, and what of a request they fix
+StagePlan plan_hypothetical(const apk_pack *u0, const apk_flux_cfg *cfg, int fill_derived, StageRequest r) {
+  r.extra = fill_derived ? (fill_derived == 3 ? EXTRA_C2P_DT : EXTRA_C2P) : EXTRA_NONE;
+  r.prim_to_u1 = (fill_derived >= 2) ? 1 : 0;
+  r.no_prim_store = (fill_derived == 3) ? 1 : 0;
+  return plan_stage(cfg->fluid, cfg->recon, u0->view, r);
 }
 
 bool same_shape(const apk_pack *a, const apk_pack *b) {
@@ -193,16 +241,8 @@ const char *apk_last_error(const apk_ctx *ctx) { return ctx ? ctx->err : "null c
 int apk_pack_create(apk_ctx *ctx, const apk_pack_desc *desc, apk_pack **out) {
   if (!ctx || !desc || !out) return APK_ERR_INVALID;
   *out = nullptr;
-  if (desc->nblocks <= 0 || !desc->blocks) return set_err(ctx, APK_ERR_INVALID, "empty pack");
-  if (desc->nhydro != 5 && desc->nhydro != 9) return set_err(ctx, APK_ERR_INVALID, "nhydro must be 5 or 9");
-  if (desc->nscalars < 0 || desc->ng < 1 || desc->nx[0] < 1 || desc->nx[1] < 1 || desc->nx[2] < 1)
-    return set_err(ctx, APK_ERR_INVALID, "bad pack geometry");
-  if (desc->nx[1] == 1 && desc->nx[2] > 1) return set_err(ctx, APK_ERR_INVALID, "nx2 == 1 requires nx3 == 1");
-  {
-    const PackView t = make_view(*desc, nullptr);  // (explicit strides: no array may overlap the next one)
-    if (desc->stride[0] < 0 || desc->stride[1] < 0 || desc->stride[2] < 0 || t.sj < t.ni || t.sk < t.sj * t.nj || t.sn < t.sk * t.nk)
-      return set_err(ctx, APK_ERR_INVALID, "pack strides smaller than the extents they step over");
-  }
+  if (!desc->blocks) return set_err(ctx, APK_ERR_INVALID, "empty pack");
+  if (const char *why = bad_pack_geometry(*desc)) return set_err(ctx, APK_ERR_INVALID, why);
   apk_pack *p = new (std::nothrow) apk_pack();
   if (!p) return APK_ERR_INVALID;
   p->h_blocks.assign(desc->blocks, desc->blocks + desc->nblocks);
@@ -330,26 +370,11 @@ int apk_dedner_source(apk_ctx *ctx, const apk_pack *md, int extended, double alp
 
 int apk_stage_fused(apk_ctx *ctx, const apk_pack *u0, const apk_pack *u1,
                     const apk_stage_args *a, apk_stream_t stream) {
-  if (!ctx || !u0 || !u1 || !a || !same_shape(u0, u1) || !valid_eos(&a->eos))
+  if (!ctx || !u0 || !u1 || !a || !same_shape(u0, u1))
     return set_err(ctx, APK_ERR_INVALID, "apk_stage_fused: bad argument");
-  int rc = check_cfg(ctx, u0, a->cfg);
-  if (rc != APK_OK) return rc;
-  if (a->cfg.riemann == APK_RS_NONE || a->cfg.riemann == APK_RS_LLF)
-    return set_err(ctx, APK_ERR_UNSUPPORTED, "fused stage: none/llf solvers use the flux-array path");
-  if (a->dedner != 0 && (a->cfg.fluid != APK_FLUID_GLMMHD || !(a->mindx > 0.0)))
-    return set_err(ctx, APK_ERR_INVALID, "fused stage: Dedner source needs glmmhd and mindx > 0");
-  if (a->phase < 0 || a->phase > 2 || (a->phase == 1) != (a->window != nullptr) ||
-      (a->phase == 1 && (a->window_rl < 3 || a->window_rl > u0->view.ni || a->window_rows < 1 ||
-                         a->window_rows > u0->view.nx2)))
-    return set_err(ctx, APK_ERR_INVALID, "fused stage: phase / window mismatch");
-  if (a->phase == 1 && a->estimate_dt && a->cfg.recon == APK_RC_DC && u0->view.ndim == 3)
-    return set_err(ctx, APK_ERR_UNSUPPORTED, "fused stage: estimate_dt is not available in a split 3-D donor-cell stage");
-  if (a->fill_derived < 0 || a->fill_derived > 3) return set_err(ctx, APK_ERR_INVALID, "fused stage: fill_derived must be 0, 1, 2 or 3");
-  if (a->fill_derived == 3 && !a->estimate_dt)
-    return set_err(ctx, APK_ERR_INVALID, "fused stage: fill_derived = 3 (primitives for the time-step estimate only) needs estimate_dt");
-  if (a->prim_from_cons < 0 || a->prim_from_cons > 2) return set_err(ctx, APK_ERR_INVALID, "fused stage: prim_from_cons must be 0, 1 or 2");
-  if (a->prim_from_cons == 2 && a->cons_out_delta == 0)
-    return set_err(ctx, APK_ERR_INVALID, "fused stage: prim_from_cons = 2 (input = u0.cons) needs an out-of-place result (cons_out_delta)");
+  const char *why = "fused stage: not supported";
+  int rc = stage_args_status(u0->view, *a, why);
+  if (rc != APK_OK) return set_err(ctx, rc, why);
   if (a->prim_from_cons) {
     for (const apk_block_desc &b : u1->h_blocks)
       if (!b.cons) return set_err(ctx, APK_ERR_INVALID, "fused stage: prim_from_cons needs u1.cons");
@@ -363,10 +388,22 @@ int apk_stage_fused(apk_ctx *ctx, const apk_pack *u0, const apk_pack *u1,
   }
   double coeff = 1.0;
   if (a->dedner != 0) coeff = std::exp(-a->glmmhd_alpha * a->c_h * a->beta_dt / a->mindx);
-  rc = launch_stage_fused(ctx, u0->view, u1->view, *a, coeff, as_stream(stream));
-  if (rc == APK_ERR_UNSUPPORTED) return set_err(ctx, rc, "fused stage: option combination not supported (scalars, 1-D/extended-Dedner fill_derived, split 1-D or 3-D donor-cell stage, fill_derived = 3 / prim_from_cons outside the lean two-kernel / donor-cell stage)");
-  if (rc != APK_OK) return set_err(ctx, rc, "fused stage kernel launch failed", hipGetLastError());
-  return APK_OK;
+  rc = launch_stage_fused(ctx, u0->view, u1->view, *a, coeff, as_stream(stream), why);
+  if (rc == APK_ERR_DEVICE) return set_err(ctx, rc, "fused stage kernel launch failed", hipGetLastError());
+  return rc == APK_OK ? rc : set_err(ctx, rc, why);
+}
+
+int apk_stage_form(const apk_pack_desc *shape, const apk_stage_args *args, apk_stage_form_info *out) {
+  if (!shape || !args || !out) return APK_ERR_INVALID;
+  *out = apk_stage_form_info{APK_FORM_NONE, 0, 0, 0, 0, ""};
+  if ((out->reason = bad_pack_geometry(*shape))) return APK_ERR_INVALID;
+  out->reason = "";
+  const PackView v = make_view(*shape, nullptr);
+  const int rc = stage_args_status(v, *args, out->reason);
+  if (rc != APK_OK) return rc;
+  const StagePlan p = plan_stage_args(v, *args);
+  *out = apk_stage_form_info{p.form, p.lean, p.dc_rows, p.from_cons, p.x1_halo ? 1 : 0, p.reason};
+  return p.status;
 }
 
 int apk_stage_unphysical_read(apk_ctx *ctx, long long *count, apk_stream_t stream) {
@@ -379,41 +416,39 @@ int apk_stage_unphysical_read(apk_ctx *ctx, long long *count, apk_stream_t strea
   return APK_OK;
 }
 
+// The three older queries: each describes a hypothetical whole stage on this pack, asks the plan and reads the form.
 int apk_stage_split_axis(const apk_pack *u0, const apk_flux_cfg *cfg, int fill_derived) {
   if (!u0 || !cfg) return 0;
-  apk::StageParams sp{};
-  sp.prim_to_u1 = (fill_derived >= 2) ? 1 : 0;
-  const int extra = fill_derived ? apk::EXTRA_C2P : apk::EXTRA_NONE;
-  if (u0->view.ndim == 3 && cfg->recon == APK_RC_DC) return 0;  // single-kernel stage: 3-D index windows
-  return apk::two_kernel_stage_applies(u0->view, cfg->recon, extra, sp) ? 3 : 1;
+  // (of fill_derived only "in place, out of place or none": the layout of the windows does not depend on the rest)
+  switch (plan_hypothetical(u0, cfg, fill_derived > 2 ? 2 : fill_derived, StageRequest{}).form) {
+  case APK_FORM_DC_MARCH:
+  case APK_FORM_MARCH12_X3: return 0;  // single-kernel stage: 3-D index windows
+  case APK_FORM_TWO_KERNEL: return 3;
+  default: return 1;
+  }
 }
 
 int apk_stage_x1_halo(const apk_pack *u0, const apk_flux_cfg *cfg, const apk_eos *eos, int fill_derived, int dedner, int prim_from_cons) {
   if (!u0 || !cfg || !eos) return 0;
-  if (cfg->riemann == APK_RS_NONE || cfg->riemann == APK_RS_LLF || u0->view.nvar != u0->view.nhydro) return 0;
-  apk::StageParams sp{};
-  sp.eos = *eos;
-  sp.dedner = dedner;
-  sp.prim_to_u1 = (fill_derived >= 2) ? 1 : 0;
-  sp.no_prim_store = (fill_derived == 3) ? 1 : 0;
-  sp.prim_from_cons = prim_from_cons;
-  sp.out_delta = (prim_from_cons == 2) ? 1 : 0;  // (such a stage writes its result elsewhere: the caller's business)
-  const int extra = fill_derived ? (fill_derived == 3 ? apk::EXTRA_C2P_DT : apk::EXTRA_C2P) : apk::EXTRA_NONE;
-  if (!apk::x1_halo_stage_ok(u0->view, cfg->recon, extra, sp)) return 0;
+  if (cfg->riemann == APK_RS_NONE || cfg->riemann == APK_RS_LLF) return 0;
+  // (asked of the scheme's plain prim-free stage whatever fill_derived is: on the safe side for the stages with FillDerived,
+  // which keep the two kernels)
   if (cfg->recon != APK_RC_DC && prim_from_cons && apk_stage_single_march(u0, cfg)) return 0;
-  return 1;
+  StageRequest r;
+  r.scalars = u0->view.nvar != u0->view.nhydro;
+  r.eos = *eos;
+  r.dedner = dedner;
+  r.prim_from_cons = prim_from_cons;
+  r.out_of_place = prim_from_cons == 2;  // (such a stage writes its result elsewhere: the caller's business)
+  r.x1_halo = true;
+  return plan_hypothetical(u0, cfg, fill_derived, r).status == APK_OK ? 1 : 0;
 }
 
 int apk_stage_single_march(const apk_pack *u0, const apk_flux_cfg *cfg) {
   if (!u0 || !cfg) return 0;
-  apk::StageParams sp{};  // a whole-block lean stage whose input is a conserved state
-  sp.prim_from_cons = 1;
-  sp.eos.vceil = sp.eos.eceil = __builtin_inf();
-  sp.eos.pfloor = sp.eos.dfloor = sp.eos.efloor = -1.0;
-  if (!apk::two_kernel_stage_applies(u0->view, cfg->recon, apk::EXTRA_NONE, sp)) return 0;
-  if (cfg->fluid == APK_FLUID_EULER && cfg->recon == APK_RC_PLM)
-    return apk::single_march_stage_applies<APK_FLUID_EULER, APK_RC_PLM>(u0->view, apk::EXTRA_NONE, sp) ? 1 : 0;
-  return 0;
+  StageRequest r;  // a whole-block lean stage whose input is a conserved state
+  r.prim_from_cons = 1;
+  return plan_hypothetical(u0, cfg, 0, r).form == APK_FORM_SINGLE_MARCH ? 1 : 0;
 }
 
 int apk_cons_to_prim(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos,

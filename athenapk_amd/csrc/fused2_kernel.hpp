@@ -624,37 +624,8 @@ inline int resident_march_waves() {
   return n;
 }
 
-// can / should a stage take the two-kernel form?  3-D, a reconstruction with a stencil (ghost
-// layers), FillDerived out of place or absent (K2's lanes read their x1 neighbours' primitives from
-// memory), and rows long enough that the flattened (k, i) run keeps most lanes on interior cells
-// (nx1 / (nx1 + 2 ng): 128 -> 96 %, 32 -> 84 %, 16 with nghost 4 -> 67 %).  Measured on the refined mesh of
-// BASELINE config 5 (232 blocks of 16^3, MHD PPM+HLLD, nghost 4): 8.52e8 against 8.36e8 zone-cycles/s for the
-// three-sweep schedule with several rows per wave, so 16-cell blocks take it too; narrower ones do not.
-inline bool two_kernel_stage_applies(const PackView &u0, int recon, int extra, const StageParams &sp) {
-  constexpr int min_nx1 = 16;
-  // (blocks narrower than 32 cells only if they are deep enough along x3 for the plane windows of a split stage --
-  // 4 nghost planes: the driver's overlap rule -- so that taking this form never costs an overlapped exchange)
-  const bool wide_enough = u0.nx1 >= 32 || (u0.nx1 >= min_nx1 && u0.nx3 >= 4 * u0.ng);
-  // (the marches address a block's cells as scalar row pointer + 32-bit byte offset of the lane: RowCellAt)
-  const bool offsets_fit = (uint64_t)u0.sn * sizeof(double) < (1ull << 32);
-  return u0.ndim == 3 && recon != APK_RC_DC && wide_enough && offsets_fit && (extra == EXTRA_NONE || sp.prim_to_u1);
-}
-
-// does a stage of this form follow apk_stage_args.x1_halo?  (apk_stage_x1_halo; launch_fused_stage refuses the others)
-inline bool x1_halo_stage_ok(const PackView &u0, int recon, int extra, const StageParams &sp) {
-  if (u0.ndim != 3 || sp.mflux || !stage_is_lean(sp) || sp.window) return false;
-  const int deepest = sp.x1_send_depth > sp.x1_recv_depth ? sp.x1_send_depth : sp.x1_recv_depth;
-  if (u0.nx1 < 2 * deepest || sp.x1_send_depth < 0 || sp.x1_recv_depth < 0 || sp.x1_recv_depth > u0.ng) return false;
-  if (sp.x1_send_field == 1 && extra == EXTRA_NONE) return false;  // (primitives to send: a stage that computes them)
-  if (recon == APK_RC_DC)  // the two-row march, which has no form with the time-step estimate for it
-    return sp.phase == 0 && (extra == EXTRA_NONE || (sp.prim_to_u1 && extra == EXTRA_C2P)) && u0.nx2 % 2 == 0 && u0.nx2 >= 4;
-  // (from stored primitives or from a conserved state -- but not the stages that take the single march, fused3_kernel.hpp:
-  // launch_fused_stage asks single_march_stage_applies for those and refuses)
-  return two_kernel_stage_applies(u0, recon, extra, sp);
-}
-
 template <int FLUID, int RECON, int RS>
-inline void launch_m12f(const PackView &u0, const PackView &u1, const StageParams &sp, int extra, hipStream_t s) {
+inline bool launch_m12f(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
   if constexpr (RECON != APK_RC_DC) {
     constexpr int lds = march_lds_bytes<FLUID, RECON>();
     constexpr int cpw = m12_last_lane(RECON) - m12_first_lane(RECON) + 1;
@@ -671,46 +642,12 @@ inline void launch_m12f(const PackView &u0, const PackView &u1, const StageParam
     const int nwaves = (int)nw;
     const int per_xcd = (nwaves + 7) / 8;
     const dim3 g((unsigned)(per_xcd * 8), 1, 1);
-    const int lean_level = stage_lean_level(sp);
-    const bool lean = lean_level == 1;
-    const bool lean2 = lean_level == LEAN_PFLOOR && extra != EXTRA_NONE && !sp.prim_from_cons && !sp.x1_blocks;
-#define APK_LAUNCH_M12F(EXTRA_, LEAN_) \
-  hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EXTRA_, LEAN_>), g, dim3(64), lds, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows)
     constexpr int lds_fc = m12f_keeps_raw_rows<FLUID, RECON>() ? 2 * lds : lds;  // (the rows as loaded, too)
-#define APK_LAUNCH_M12F_FC(EXTRA_) \
-  hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EXTRA_, 1, true>), g, dim3(64), lds_fc, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows)
-#define APK_LAUNCH_M12F_X1H(EXTRA_) \
-  hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EXTRA_, 1, false, true>), g, dim3(64), lds, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows)
-#define APK_LAUNCH_M12F_FC_X1H(EXTRA_) \
-  hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EXTRA_, 1, true, true>), g, dim3(64), lds_fc, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows)
-    if (sp.x1_blocks && sp.prim_from_cons) {  // (the lean forms: launch_fused_stage has checked)
-      if (extra == EXTRA_C2P_DT) APK_LAUNCH_M12F_FC_X1H(EXTRA_C2P_DT);
-      else if (extra == EXTRA_C2P) APK_LAUNCH_M12F_FC_X1H(EXTRA_C2P);
-      else APK_LAUNCH_M12F_FC_X1H(EXTRA_NONE);
-    } else if (sp.x1_blocks) {
-      if (extra == EXTRA_C2P_DT) APK_LAUNCH_M12F_X1H(EXTRA_C2P_DT);
-      else if (extra == EXTRA_C2P) APK_LAUNCH_M12F_X1H(EXTRA_C2P);
-      else APK_LAUNCH_M12F_X1H(EXTRA_NONE);
-    } else if (sp.prim_from_cons) {  // (lean forms only: launch_fused_stage has checked)
-      if (extra == EXTRA_C2P_DT) APK_LAUNCH_M12F_FC(EXTRA_C2P_DT);
-      else if (extra == EXTRA_C2P) APK_LAUNCH_M12F_FC(EXTRA_C2P);
-      else APK_LAUNCH_M12F_FC(EXTRA_NONE);
-    } else if (extra == EXTRA_C2P_DT) {
-      if (lean) APK_LAUNCH_M12F(EXTRA_C2P_DT, 1);
-      else if (lean2) APK_LAUNCH_M12F(EXTRA_C2P_DT, LEAN_PFLOOR);
-      else APK_LAUNCH_M12F(EXTRA_C2P_DT, 0);
-    } else if (extra == EXTRA_C2P) {
-      if (lean) APK_LAUNCH_M12F(EXTRA_C2P, 1);
-      else if (lean2) APK_LAUNCH_M12F(EXTRA_C2P, LEAN_PFLOOR);
-      else APK_LAUNCH_M12F(EXTRA_C2P, 0);
-    } else {
-      if (lean) APK_LAUNCH_M12F(EXTRA_NONE, 1);
-      else APK_LAUNCH_M12F(EXTRA_NONE, 0);
-    }
-#undef APK_LAUNCH_M12F
-#undef APK_LAUNCH_M12F_FC
-#undef APK_LAUNCH_M12F_X1H
-#undef APK_LAUNCH_M12F_FC_X1H
+    const bool ok = as_constants([&](auto X1H, auto FC, auto EX, auto LN) {
+      if constexpr (m12f_compiled(RECON, EX, LN, FC, X1H))
+        hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EX, LN, (FC != 0), (X1H != 0)>), g, dim3(64), FC ? lds_fc : lds, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows);
+      return m12f_compiled(RECON, EX, LN, FC, X1H);
+    }, among<0, 1>{plan.x1_halo}, among<0, 1>{plan.from_cons != 0}, extra_among{plan.extra}, among<0, LEAN_PFLOOR, 1>{plan.lean});
 #if APK_M12F_TIMING
     {
       static int calls = 0;
@@ -723,13 +660,15 @@ inline void launch_m12f(const PackView &u0, const PackView &u1, const StageParam
         static const char *name[8] = {"other", "x1_recon", "x1_riemann", "x2_recon", "x2_riemann", "load_wait", "finish", "-"};
         double tot = 0;
         for (int p = 0; p < 7; ++p) tot += (double)h[p];
-        std::fprintf(stderr, "[m12f phases, shader clocks per wave over 8 launches, recon %d extra %d]", RECON, extra);
+        std::fprintf(stderr, "[m12f phases, shader clocks per wave over 8 launches, recon %d extra %d]", RECON, plan.extra);
         for (int p = 0; p < 7; ++p) std::fprintf(stderr, " %s %.1f%% (%.3e)", name[p], 100.0 * h[p] / tot, (double)h[p] / nwaves / 8.0);
         std::fprintf(stderr, "\n");
       }
     }
 #endif
+    return ok;
   }
+  return false;
 }
 
 }  // namespace apk

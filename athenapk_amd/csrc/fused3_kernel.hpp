@@ -316,27 +316,9 @@ fused_s3_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, int
   }
 }
 
-// does a stage take the single-march form?  3-D, a three-point reconstruction, the lean form with its input derived from
-// a conserved state (what a prim-free RK cycle asks of every stage), whole blocks (a split stage keeps the two kernels:
-// its x3 sweep runs on plane windows while the halo messages fly), an even number of x2 rows, no primitives stored.
-// Hydro with PLM for now: 256 VGPRs, no scratch (WENO3 / LimO3 spill 44 - 98 registers in this form, GLM-MHD would hold
-// 2 x 9 x 7 doubles across a Riemann solve): the others keep the two-kernel stage.
-template <int FLUID, int RECON>
-constexpr bool single_march_compiled() { return FLUID == APK_FLUID_EULER && RECON == APK_RC_PLM; }
-template <int FLUID, int RECON>
-inline bool single_march_stage_applies(const PackView &u0, int extra, const StageParams &sp) {
-  if constexpr (!single_march_compiled<FLUID, RECON>()) return false;
-  // (rows of 32 cells and more: on the 16^3 blocks of a refined mesh the march's x1 halo lanes outnumber its cells and the
-  // two-kernel form is faster -- refined hydro blast of BASELINE config 5, zone-cycles/s, same box: 16^3 blocks 2.02e9 with
-  // this march against 2.32e9 with the two-kernel stage; 32^3: 4.55e9 against 4.17e9; 48^3: 5.85e9 against 5.23e9)
-  return u0.ndim == 3 && u0.nx1 >= 32 && (uint64_t)u0.sn * sizeof(double) < (1ull << 32) && sp.prim_from_cons != 0 && sp.phase == 0 && sp.window == nullptr && stage_is_lean(sp) &&
-         u0.nx2 % 2 == 0 && u0.nx2 >= 4 && u0.ng >= 2 && (extra == EXTRA_NONE || (extra == EXTRA_C2P_DT && sp.no_prim_store)) &&
-         (sp.prim_from_cons == 1 || sp.out_delta != 0);
-}
-
 template <int FLUID, int RECON, int RS>
-inline void launch_s3(const PackView &u0, const PackView &u1, const StageParams &sp, int extra, hipStream_t s) {
-  if constexpr (single_march_compiled<FLUID, RECON>()) {
+inline bool launch_s3(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  if constexpr (s3_compiled(FLUID, RECON, EXTRA_NONE, 1)) {
     const int64_t run = (int64_t)(u0.nx2 / 2) * (u0.nx1 + 2 * kS3Halo);
     const int wpb = (int)((run + kS3Cells - 1) / kS3Cells);
     // a segment costs its planes plus two for the prologue (12.5 % at 16).  Measured on 8 x 128^3 (round 6, same box, ms per
@@ -349,17 +331,13 @@ inline void launch_s3(const PackView &u0, const PackView &u1, const StageParams 
     const int per_xcd = (int)((total + 7) / 8);
     const dim3 g((unsigned)(per_xcd * 8), 1, 1);
     constexpr int lds = 8 * nvars<FLUID>() * 64 * (int)sizeof(double);  // f3 + du + two planes as loaded, two cells each
-#define APK_LAUNCH_S3(EXTRA_, SRC_) \
-  hipLaunchKernelGGL((fused_s3_kernel<FLUID, RECON, RS, EXTRA_, SRC_>), g, dim3(64), lds, s, u0, u1, sp, kseg, wpb, nseg, per_xcd)
-    if (extra == EXTRA_C2P_DT) {
-      if (sp.prim_from_cons == 2) APK_LAUNCH_S3(EXTRA_C2P_DT, 2);
-      else APK_LAUNCH_S3(EXTRA_C2P_DT, 1);
-    } else {
-      if (sp.prim_from_cons == 2) APK_LAUNCH_S3(EXTRA_NONE, 2);
-      else APK_LAUNCH_S3(EXTRA_NONE, 1);
-    }
-#undef APK_LAUNCH_S3
+    return as_constants([&](auto EX, auto SRC) {
+      if constexpr (s3_compiled(FLUID, RECON, EX, SRC))
+        hipLaunchKernelGGL((fused_s3_kernel<FLUID, RECON, RS, EX, SRC>), g, dim3(64), lds, s, u0, u1, sp, kseg, wpb, nseg, per_xcd);
+      return s3_compiled(FLUID, RECON, EX, SRC);
+    }, extra_among{plan.extra}, among<1, 2>{plan.from_cons});
   }
+  return false;
 }
 
 }  // namespace apk

@@ -3,7 +3,7 @@
 
 namespace apk {
 int launch_fused_euler_hlle(const PackView &u0, const PackView &u1, int recon,
-                         const StageParams &sp, int extra, hipStream_t s) {
-  return launch_fused_family<APK_FLUID_EULER, APK_RS_HLLE>(u0, u1, recon, sp, extra, s);
+                         const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  return launch_fused_family<APK_FLUID_EULER, APK_RS_HLLE>(u0, u1, recon, sp, plan, s);
 }
 }  // namespace apk

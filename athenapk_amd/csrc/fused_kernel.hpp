@@ -23,6 +23,7 @@
 
 #include "apk_internal.hpp"
 #include "hydro_math.hpp"
+#include "stage_form.hpp"
 
 namespace apk {
 
@@ -148,9 +149,6 @@ APK_DEV void face_states_any(const double *c, int64_t st, double dx, int var, do
   }
 }
 
-// what the finishing sweep does besides the RK update + Dedner source
-enum { EXTRA_NONE = 0, EXTRA_C2P = 1, EXTRA_C2P_DT = 2 };
-
 // x1 sweep (lanes along the flattened rows): first lane of a wave that retires a cell and the
 // number of cells a wave retires.  Lane l needs the L state of lane l-1 and the flux of lane l+1;
 // with PPM lane l-1's state in turn needs the interface value of lane l-2 (face sharing).
@@ -185,7 +183,7 @@ APK_DEV double wave_shl1(double x) {  // lane l receives lane l+1 (lane 63: 0.0)
 // constraint -- otherwise array + n * sn is hoisted out of the march as nine loop-invariant register pairs per array, which
 // is what filled the scalar register file and spilled ~100 of them to vector lanes), and the lane offset is "fresh" in the
 // basic block that uses it (the zero extension has to be visible to instruction selection there).  Needs a block's
-// variable stride to fit 32 bits in bytes (two_kernel_stage_applies checks).
+// variable stride to fit 32 bits in bytes (stage_form.hpp: two_kernel_stage_applies checks).
 struct CellAt {
   int64_t cell;
 };
@@ -251,22 +249,11 @@ APK_DEV void store_vars(double *arr, int64_t sn, const RowCellAt &a, const doubl
 // ---- end-of-stage update of one cell (FINAL sweep) -------------------------------------------
 // UpdateWithFluxDivergence (hydro_driver.cpp:534-537) then DednerSource
 // (dedner_source.cpp:42-74), in that order, exactly as the task list runs them.
-// A stage is LEAN when none of the finishing sweep's optional work is asked for: no mass-flux workspace (passive
-// scalars), no trial count (first-order flux correction), no extended Dedner source, and an equation of state whose
-// velocity ceiling, pressure floor and energy ceiling are off (eos_is_lean).  The uniform-mesh cycles of the decks and
-// of the benchmark are all of this kind.  finish_cell<.., LEAN = true> compiles none of that work: no scalar
+// A stage is LEAN when none of the finishing sweep's optional work is asked for (stage_form.hpp: stage_lean_level).
+// finish_cell<.., LEAN = true> compiles none of that work: no scalar
 // registers for its parameters (the finishing march spills ~100 of them to vector lanes, one v_readlane per use), one
 // wave-uniform branch around the nine loads of the old state instead of nine, and -- product build -- the update as
 // one fused multiply-add per variable on the wave-uniform coefficient `upd` = -beta_dt / V.
-inline bool stage_is_lean(const StageParams &sp) {
-  return sp.mflux == nullptr && sp.bad_count == nullptr && sp.dedner != 2 && eos_is_lean(sp.eos);
-}
-// 1: lean; LEAN_PFLOOR (2): lean but for a pressure floor and / or the trial count of first-order flux correction -- the
-// Orszag-Tang deck has both -- whose few instructions the forms <.., LEAN = 2> compile in; 0: the general form
-inline int stage_lean_level(const StageParams &sp) {
-  if (stage_is_lean(sp)) return 1;
-  return (sp.mflux == nullptr && sp.dedner != 2 && eos_is_lean_but_pfloor(sp.eos)) ? LEAN_PFLOOR : 0;
-}
 // -beta_dt / V of a block (product build; the parity build divides by V per cell as the reference does)
 APK_DEV double update_coefficient(const StageParams &sp, double vol) { return to_sgpr(-sp.beta_dt / vol); }
 
@@ -1606,8 +1593,11 @@ inline int march_segments(int64_t waves, int n_along) {
   return nseg < 1 ? 1 : nseg;
 }
 
+// timing slots: donor-cell stages (VL2 predictor) are accounted separately
+constexpr int stage_timing_slot(int recon) { return (recon == APK_RC_DC) ? (int)APK_T_FUSED_DC_X1 : (int)APK_T_FUSED_X1; }
+
 template <int FLUID, int RECON, int RS, int DIR>
-inline void launch_final_march(const PackView &u0, const PackView &u1, const StageParams &sp, int extra,
+inline bool launch_final_march(const PackView &u0, const PackView &u1, const StageParams &sp, int extra,
                                dim3 grid, int lds, hipStream_t s) {
   // (a finishing march that replaces prim in place must own its columns from end to end: the
   // next segment's stencil rows would be overwritten under it)
@@ -1618,267 +1608,250 @@ inline void launch_final_march(const PackView &u0, const PackView &u1, const Sta
   grid.y = (ntrans + rpw - 1) / rpw;
   const int nseg = in_place ? 1 : march_segments((int64_t)grid.x * grid.y * grid.z, DIR == 2 ? u0.nx2 : u0.nx3);
   grid.z *= nseg;
-  if (extra == EXTRA_C2P_DT)
-    hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, DIR, true, EXTRA_C2P_DT>), grid, dim3(64), lds, s, u0, u1, sp, nseg, rpw);
-  else if (extra == EXTRA_C2P)
-    hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, DIR, true, EXTRA_C2P>), grid, dim3(64), lds, s, u0, u1, sp, nseg, rpw);
-  else
-    hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, DIR, true, EXTRA_NONE>), grid, dim3(64), lds, s, u0, u1, sp, nseg, rpw);
+  return as_constants([&](auto EX) {
+    hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, DIR, true, EX>), grid, dim3(64), lds, s, u0, u1, sp, nseg, rpw);
+    return true;
+  }, extra_among{extra});
 }
 
-template <int FLUID, int RECON, int RS>
-inline int launch_fused_stage(const PackView &u0, const PackView &u1, const StageParams &sp,
-                              int extra, hipStream_t s) {
+// the x1 sweep as a kernel of its own, finishing (1-D) or not
+template <int FLUID, int RECON, int RS, bool FINAL>
+inline void launch_x1_sweep(const PackView &u0, const PackView &u1, const StageParams &sp, hipStream_t s) {
   // a windowed x1 sweep (phase 1) flattens at most window_rl columns per row
   const int64_t run1 = (int64_t)u0.nx2 * (sp.window ? sp.window_rl : u0.nx1 + x1_first_lane(RECON) + 1);
   constexpr int cpw1 = x1_cells_per_wave(RECON);
   const int wpp = (int)((run1 + cpw1 - 1) / cpw1);
   const dim3 g1((wpp + 3) / 4, u0.nx3 * u0.nblocks, 1);
-  if (sp.phase != 0) {
-    // split stage: where the x1 sweep is its own, non-finishing kernel, or the single-kernel
-    // 3-D donor-cell stage with out-of-place (or no) FillDerived
-    if (u0.ndim == 1) return APK_ERR_UNSUPPORTED;
-    if (RECON == APK_RC_DC && u0.ndim == 3) {
-      if (!(extra == EXTRA_NONE || (sp.prim_to_u1 && extra == EXTRA_C2P))) return APK_ERR_UNSUPPORTED;
-      if (sp.phase == 2) {  // the cells were all retired in phase 1; only the scalars are left
-        if (sp.mflux) launch_scalar_update<RECON>(u0, u1, sp, extra, s);
-        return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
-      }
-    }
-  }
-  if (sp.face_nbr) {
-    // only the kernels that follow the table: the single-march donor-cell stage and the two-kernel
-    // stage; nothing that reads neighbouring cells from memory by plain index arithmetic
-    const bool form_ok = (RECON == APK_RC_DC) ? (extra == EXTRA_NONE || sp.prim_to_u1 != 0)
-                                              : two_kernel_stage_applies(u0, RECON, extra, sp);
-    if (u0.ndim != 3 || sp.mflux || sp.dedner == 2 || !form_ok) return APK_ERR_UNSUPPORTED;
-  }
-  // apk_stage_args.x1_halo: the lean two-row donor-cell march and the lean two-kernel stage's finishing march (phase 1 of
-  // a split two-kernel stage is the x3 sweep, which reads no x1 ghost column and retires nothing: it ignores the table)
-  if (sp.x1_blocks && !(RECON != APK_RC_DC && sp.phase == 1) &&
-      (!x1_halo_stage_ok(u0, RECON, extra, sp) || (RECON != APK_RC_DC && single_march_stage_applies<FLUID, RECON>(u0, extra, sp))))
-    return APK_ERR_UNSUPPORTED;
-  if (sp.no_prim_store && !(u0.ndim == 3 && RECON != APK_RC_DC && stage_is_lean(sp) && two_kernel_stage_applies(u0, RECON, extra, sp)))
-    return APK_ERR_UNSUPPORTED;
-  if (sp.prim_from_cons) {
-    const bool dc_ok = RECON == APK_RC_DC && sp.prim_from_cons == 1 && (extra == EXTRA_NONE || sp.prim_to_u1);
-    // the two-kernel stage, whole or split (a stage that reads u0's conserved state writes its result elsewhere)
-    const bool two_ok = RECON != APK_RC_DC && two_kernel_stage_applies(u0, RECON, extra, sp) && !sp.mflux &&
-                        (sp.prim_from_cons == 1 || sp.out_delta != 0);
-    if (!(u0.ndim == 3 && stage_is_lean(sp) && (dc_ok || two_ok))) return APK_ERR_UNSUPPORTED;
-  }
-  const bool do_x1 = sp.phase != 2, do_rest = sp.phase != 1;
-  // timing slots: donor-cell stages (VL2 predictor) are accounted separately
-  constexpr int TS = (RECON == APK_RC_DC) ? (int)APK_T_FUSED_DC_X1 : (int)APK_T_FUSED_X1;
-  if (u0.ndim == 1) {
-    ScopedTiming t(sp.ctx, TS + 0, s);
-    hipLaunchKernelGGL((fused_x1_kernel<FLUID, RECON, RS, true>), g1, dim3(256), 0, s, u0, u1, sp, wpp);
-  } else if (u0.ndim == 3) {
+  ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 0, s);
+  hipLaunchKernelGGL((fused_x1_kernel<FLUID, RECON, RS, FINAL>), g1, dim3(256), 0, s, u0, u1, sp, wpp);
+}
+
+// ---- one launcher per form (stage_form.hpp: plan_stage) ----------------------------------------
+template <int FLUID, int RECON, int RS>
+inline bool launch_x1(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  launch_x1_sweep<FLUID, RECON, RS, true>(u0, u1, sp, s);
+  if (sp.mflux && sp.phase != 1) launch_scalar_update<RECON>(u0, u1, sp, plan.extra, s);
+  return true;
+}
+
+template <int FLUID, int RECON, int RS>
+inline bool launch_x1_x2(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  if (sp.phase != 2) launch_x1_sweep<FLUID, RECON, RS, false>(u0, u1, sp, s);
+  // 2-D: the (j,i)-flattened x1 sweep keeps far more waves in flight than a march over a
+  // single k-plane would; the x2 march finishes the stage
+  bool ok = true;
+  if (sp.phase != 1) {
     constexpr int lds = march_lds_bytes<FLUID, RECON>();
-    if constexpr (RECON == APK_RC_DC) {
-      if (extra == EXTRA_NONE || sp.prim_to_u1) {
-        // whole donor-cell stage in one march (see fused_dc3_kernel); its FillDerived is out of place
-        const int64_t run3 = sp.window ? (int64_t)sp.window_rows * sp.window_rl : (int64_t)u0.nx2 * (u0.nx1 + 2);
-        const int wpb = (int)((run3 + 61) / 62);
-        const int lean_level = stage_lean_level(sp);
-        const bool lean = lean_level == 1;
-        // (the lean form with a pressure floor / the trial count: the two-row march with FillDerived from stored primitives)
-        const bool lean2 = lean_level == LEAN_PFLOOR && extra != EXTRA_NONE && !sp.prim_from_cons && !sp.x1_blocks;
-        // two rows per lane (fused_dc3r2_kernel): whole blocks only -- a split stage's windows keep the one-row kernel
-        const bool two_rows = (lean || lean2) && !sp.window && u0.nx2 % 2 == 0 && u0.nx2 >= 4;
-        const int wpb2 = (int)(((int64_t)(u0.nx2 / 2) * (u0.nx1 + 2) + 61) / 62);
-        const int wpb_run = two_rows ? wpb2 : wpb;  // wave columns per block of the kernel that will run
-        // measured on 8 x 128^3 (round 5, two-row march from the conserved state, ms per cycle of the headline, same box):
-        // 6 planes 3.67 - 3.70, 8: 3.64 - 3.66, 12: 3.65, 16: 3.61 - 3.63, 32: 3.61 - 3.66 -- the predictor itself is
-        // fastest at 8 (1.07 against 1.08 / 1.16 ms at 16 / 32), but what it leaves of the power budget is clock for the
-        // two kernels after it (finishing march 1.85 -> 1.82 -> 1.76 ms): 16 is the cycle's optimum
-        int kseg = (u0.nx3 >= 32) ? 16 : ((u0.nx3 >= 16) ? 8 : u0.nx3);
-        if (u0.nx3 >= 16 && (int64_t)wpb_run * ((u0.nx3 + 7) / 8) * u0.nblocks < 4 * 2048) {
-          // small packs (refined meshes of 16^3 blocks): a few waves per SIMD in all, so pick the segment length with
-          // the fewest plane-steps on the busiest SIMD -- a segment costs its planes plus about 1.5 for the prologue, a
-          // SIMD (1024 of them) works through ceil(waves / 1024) segments at the rate two resident waves share, and a
-          // wave that has its SIMD to itself runs 1.4 times as fast as one of a pair, not twice.  (Round 5: counted with
-          // the wave columns of the kernel that RUNS -- the two-row march has 3 per 16^3 block where the one-row march has
-          // 5 -- and per SIMD instead of per round of 2048 waves.  232 blocks of 16^3, two-row march, us per launch:
-          // segments of 4 planes 124, 8: 134, 6: 141, 16: 167 -- the order this estimate gives.)
-          double best = 1.0e300;
-          for (const int cand : {4, 6, 8, 16}) {
-            if (cand > u0.nx3) continue;
-            const int64_t waves = (int64_t)wpb_run * ((u0.nx3 + cand - 1) / cand) * u0.nblocks;
-            const double per_simd = waves <= 1024 ? 2.0 / 1.4 : (double)((waves + 1023) / 1024);
-            const double cost = per_simd * (cand + 1.5);
-            if (cost < best) best = cost, kseg = cand;
-          }
-        }
-        const int nseg = (u0.nx3 + kseg - 1) / kseg;
-        const int64_t total = (int64_t)wpb * nseg * u0.nblocks;
-        const int per_xcd = (int)((total + 7) / 8);
-        const dim3 g((unsigned)(per_xcd * 8), 1, 1);
-        constexpr int lds3 = 2 * nvars<FLUID>() * 64 * (int)sizeof(double);
-        ScopedTiming t(sp.ctx, TS + 0, s);
-        if (two_rows) {
-          const int64_t total2 = (int64_t)wpb2 * nseg * u0.nblocks;
-          const int per_xcd2 = (int)((total2 + 7) / 8);
-          const dim3 g2((unsigned)(per_xcd2 * 8), 1, 1);
-          constexpr int lds4 = 4 * nvars<FLUID>() * 64 * (int)sizeof(double);
-#define APK_LAUNCH_DC3R2(EXTRA_, FC_) \
-  hipLaunchKernelGGL((fused_dc3r2_kernel<FLUID, RS, EXTRA_, FC_>), g2, dim3(64), lds4, s, u0, u1, sp, kseg, wpb2, nseg, per_xcd2)
-#define APK_LAUNCH_DC3R2_X1H(EXTRA_, FC_) \
-  hipLaunchKernelGGL((fused_dc3r2_kernel<FLUID, RS, EXTRA_, FC_, true>), g2, dim3(64), lds4, s, u0, u1, sp, kseg, wpb2, nseg, per_xcd2)
-          if (lean2) {
-            if (extra == EXTRA_C2P_DT) hipLaunchKernelGGL((fused_dc3r2_kernel<FLUID, RS, EXTRA_C2P_DT, false, false, LEAN_PFLOOR>), g2, dim3(64), lds4, s, u0, u1, sp, kseg, wpb2, nseg, per_xcd2);
-            else hipLaunchKernelGGL((fused_dc3r2_kernel<FLUID, RS, EXTRA_C2P, false, false, LEAN_PFLOOR>), g2, dim3(64), lds4, s, u0, u1, sp, kseg, wpb2, nseg, per_xcd2);
-          } else if (sp.x1_blocks) {  // (apk_stage_args.x1_halo: stages without the dt estimate -- the predictor's place in a cycle)
-            if (extra == EXTRA_C2P_DT) return APK_ERR_UNSUPPORTED;
-            if (extra == EXTRA_C2P) {
-              if (sp.prim_from_cons) APK_LAUNCH_DC3R2_X1H(EXTRA_C2P, true);
-              else APK_LAUNCH_DC3R2_X1H(EXTRA_C2P, false);
-            } else {
-              if (sp.prim_from_cons) APK_LAUNCH_DC3R2_X1H(EXTRA_NONE, true);
-              else APK_LAUNCH_DC3R2_X1H(EXTRA_NONE, false);
-            }
-          } else if (extra == EXTRA_C2P_DT) {
-            if (sp.prim_from_cons) APK_LAUNCH_DC3R2(EXTRA_C2P_DT, true);
-            else APK_LAUNCH_DC3R2(EXTRA_C2P_DT, false);
-          } else if (extra == EXTRA_C2P) {
-            if (sp.prim_from_cons) APK_LAUNCH_DC3R2(EXTRA_C2P, true);
-            else APK_LAUNCH_DC3R2(EXTRA_C2P, false);
-          } else {
-            if (sp.prim_from_cons) APK_LAUNCH_DC3R2(EXTRA_NONE, true);
-            else APK_LAUNCH_DC3R2(EXTRA_NONE, false);
-          }
-#undef APK_LAUNCH_DC3R2
-#undef APK_LAUNCH_DC3R2_X1H
-          return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
-        }
-        if (sp.x1_blocks) return APK_ERR_UNSUPPORTED;  // (x1_halo: the two-row march only)
-        if (sp.prim_from_cons) {  // (one row per lane: odd row counts, the windows of a split stage)
-#define APK_LAUNCH_DC3FC(EXTRA_) \
-  hipLaunchKernelGGL((fused_dc3_kernel<FLUID, RS, EXTRA_, 1, true>), g, dim3(64), lds3, s, u0, u1, sp, kseg, wpb, nseg, per_xcd)
-          if (extra == EXTRA_C2P_DT) APK_LAUNCH_DC3FC(EXTRA_C2P_DT);
-          else if (extra == EXTRA_C2P) APK_LAUNCH_DC3FC(EXTRA_C2P);
-          else APK_LAUNCH_DC3FC(EXTRA_NONE);
-#undef APK_LAUNCH_DC3FC
-          return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
-        }
-#define APK_LAUNCH_DC3(EXTRA_, LEAN_) \
-  hipLaunchKernelGGL((fused_dc3_kernel<FLUID, RS, EXTRA_, LEAN_>), g, dim3(64), lds3, s, u0, u1, sp, kseg, wpb, nseg, per_xcd)
-        // (the windows of a split stage and odd row counts take the one-row march in the SAME lean form the whole stage
-        // takes as the two-row march: the product build's update expression is the form's, and a split stage must
-        // reproduce the whole one bit for bit)
-        if (extra == EXTRA_C2P_DT) {
-          if (lean) APK_LAUNCH_DC3(EXTRA_C2P_DT, 1);
-          else if (lean2) APK_LAUNCH_DC3(EXTRA_C2P_DT, LEAN_PFLOOR);
-          else APK_LAUNCH_DC3(EXTRA_C2P_DT, 0);
-        } else if (extra == EXTRA_C2P) {
-          if (lean) APK_LAUNCH_DC3(EXTRA_C2P, 1);
-          else if (lean2) APK_LAUNCH_DC3(EXTRA_C2P, LEAN_PFLOOR);
-          else APK_LAUNCH_DC3(EXTRA_C2P, 0);
-        } else {
-          if (lean) APK_LAUNCH_DC3(EXTRA_NONE, 1);
-          else APK_LAUNCH_DC3(EXTRA_NONE, 0);
-        }
-#undef APK_LAUNCH_DC3
-        if (sp.mflux && sp.phase == 0) launch_scalar_update<RECON>(u0, u1, sp, extra, s);
-        return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
-      }
-      // (with FillDerived fused into the stage) donor cell: the sweeps are HBM-bound, so x1 and x2 share ONE march over (k,i)-flattened
-      // lanes (one du round trip and one prim read less).  With a high-order reconstruction
-      // the sweeps are ALU-bound and the 62/64 x 128/134 lane efficiency of the flattened march
-      // (and its 2216-wave grid on a 2048-wave machine) costs more than the traffic it saves
-      // (measured: PPM+HLLD 3.3 ms fused vs 1.39 + 1.02 ms separate on 8 x 128^3).
-      const int64_t run12 = (int64_t)u0.nx3 * u0.ni;
-      const int wpb = (int)((run12 + 61) / 62);
-      ScopedTiming t(sp.ctx, TS + 0, s);
-      hipLaunchKernelGGL((fused_march12_kernel<FLUID, RECON, RS>), dim3(wpb, 1, u0.nblocks), dim3(64), lds, s,
-                         u0, u1, sp, wpb);
-    } else if (two_kernel_stage_applies(u0, RECON, extra, sp) && single_march_stage_applies<FLUID, RECON>(u0, extra, sp)) {
-      // the whole stage in one march (fused3_kernel.hpp: three-point reconstructions, input from a conserved state)
-      ScopedTiming t(sp.ctx, TS + 0, s);
-      launch_s3<FLUID, RECON, RS>(u0, u1, sp, extra, s);
-      return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
-    } else if (two_kernel_stage_applies(u0, RECON, extra, sp)) {
-      // two-kernel stage (fused2_kernel.hpp): the x3 sweep writes its flux difference, then one
-      // march does x1 + x2 and finishes.  A split stage runs the x3 sweep on plane windows in
-      // phase 1 (it reads x3 ghost zones only) and the finishing march in phase 2.
-      const int du_pitch = ((u0.nx1 + 15) / 16) * 16;
-      if (do_x1) {
-        StageParams sp1 = sp;
-        sp1.du_first = 1;
-        sp1.du_pitch = du_pitch;
-        const int rpw = march_rows_per_wave(u0.nx1, u0.nx2);
-        dim3 g3((u0.nx1 + 64 / rpw - 1) / (64 / rpw), (u0.nx2 + rpw - 1) / rpw, u0.nblocks);
-        const int nseg = march_segments((int64_t)g3.x * g3.y * g3.z, u0.nx3);
-        g3.z *= nseg;
-        ScopedTiming t(sp.ctx, TS + 2, s);
-        if (sp.prim_from_cons)
-          hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, 3, false, EXTRA_NONE, true>), g3, dim3(64), lds, s, u0, u1, sp1, nseg, rpw);
-        else
-          hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, 3, false>), g3, dim3(64), lds, s, u0, u1, sp1, nseg, rpw);
-      }
-      if (do_rest) {
-        StageParams sp2 = sp;
-        sp2.window = nullptr;
-        sp2.du_pitch = du_pitch;
-        ScopedTiming t(sp.ctx, TS + 0, s);
-        launch_m12f<FLUID, RECON, RS>(u0, u1, sp2, extra, s);
-      }
-      if (sp.mflux && do_rest) launch_scalar_update<RECON>(u0, u1, sp, extra, s);
-      return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
-    } else {
-      if (do_x1) {
-        ScopedTiming t(sp.ctx, TS + 0, s);
-        hipLaunchKernelGGL((fused_x1_kernel<FLUID, RECON, RS, false>), g1, dim3(256), 0, s, u0, u1, sp, wpp);
-      }
-      if (do_rest) {
+    const dim3 g2((u0.nx1 + 63) / 64, u0.nx3, u0.nblocks);
+    {
+      ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 1, s);
+      ok = launch_final_march<FLUID, RECON, RS, 2>(u0, u1, sp, plan.extra, g2, lds, s);
+    }
+    if (sp.mflux) launch_scalar_update<RECON>(u0, u1, sp, plan.extra, s);
+  }
+  return ok;
+}
+
+// the finishing x3 march of the three sweeps and of march12 + x3, then the scalars
+template <int FLUID, int RECON, int RS>
+inline bool launch_final_x3(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  bool ok;
+  {
+    const dim3 g3((u0.nx1 + 63) / 64, u0.nx2, u0.nblocks);
+    ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 2, s);
+    ok = launch_final_march<FLUID, RECON, RS, 3>(u0, u1, sp, plan.extra, g3, march_lds_bytes<FLUID, RECON>(), s);
+  }
+  if (sp.mflux) launch_scalar_update<RECON>(u0, u1, sp, plan.extra, s);
+  return ok;
+}
+
+template <int FLUID, int RECON, int RS>
+inline bool launch_three_sweep(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  if constexpr (RECON != APK_RC_DC) {
+    if (sp.phase != 2) launch_x1_sweep<FLUID, RECON, RS, false>(u0, u1, sp, s);
+    if (sp.phase != 1) {
+      {
+        constexpr int lds = march_lds_bytes<FLUID, RECON>();
         const int rpw = march_rows_per_wave(u0.nx1, u0.nx3);
         dim3 g2((u0.nx1 + 64 / rpw - 1) / (64 / rpw), (u0.nx3 + rpw - 1) / rpw, u0.nblocks);
         const int nseg = march_segments((int64_t)g2.x * g2.y * g2.z, u0.nx2);
         g2.z *= nseg;
-        ScopedTiming t(sp.ctx, TS + 1, s);
+        ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 1, s);
         hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, 2, false>), g2, dim3(64), lds, s, u0, u1, sp, nseg, rpw);
       }
+      return launch_final_x3<FLUID, RECON, RS>(u0, u1, sp, plan, s);
     }
-    if (do_rest) {
-      const dim3 g3((u0.nx1 + 63) / 64, u0.nx2, u0.nblocks);
-      ScopedTiming t(sp.ctx, TS + 2, s);
-      launch_final_march<FLUID, RECON, RS, 3>(u0, u1, sp, extra, g3, lds, s);
-    }
-  } else {
-    if (do_x1) {
-      ScopedTiming t(sp.ctx, TS + 0, s);
-      hipLaunchKernelGGL((fused_x1_kernel<FLUID, RECON, RS, false>), g1, dim3(256), 0, s, u0, u1, sp, wpp);
-    }
-    // 2-D: the (j,i)-flattened x1 sweep keeps far more waves in flight than a march over a
-    // single k-plane would; the x2 march finishes the stage
-    if (do_rest) {
-      constexpr int lds = march_lds_bytes<FLUID, RECON>();
-      const dim3 g2((u0.nx1 + 63) / 64, u0.nx3, u0.nblocks);
-      ScopedTiming t(sp.ctx, TS + 1, s);
-      launch_final_march<FLUID, RECON, RS, 2>(u0, u1, sp, extra, g2, lds, s);
-    }
+    return true;
   }
-  if (sp.mflux && do_rest) launch_scalar_update<RECON>(u0, u1, sp, extra, s);
+  return false;  // (no such form for this reconstruction)
+}
+
+// (with FillDerived fused into the stage) donor cell: the sweeps are HBM-bound, so x1 and x2 share ONE march over (k,i)-flattened
+// lanes (one du round trip and one prim read less).  With a high-order reconstruction
+// the sweeps are ALU-bound and the 62/64 x 128/134 lane efficiency of the flattened march
+// (and its 2216-wave grid on a 2048-wave machine) costs more than the traffic it saves
+// (measured: PPM+HLLD 3.3 ms fused vs 1.39 + 1.02 ms separate on 8 x 128^3).
+template <int FLUID, int RECON, int RS>
+inline bool launch_march12_x3(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  if constexpr (RECON == APK_RC_DC) {
+    {
+      constexpr int lds = march_lds_bytes<FLUID, RECON>();
+      const int64_t run12 = (int64_t)u0.nx3 * u0.ni;
+      const int wpb = (int)((run12 + 61) / 62);
+      ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 0, s);
+      hipLaunchKernelGGL((fused_march12_kernel<FLUID, RECON, RS>), dim3(wpb, 1, u0.nblocks), dim3(64), lds, s,
+                         u0, u1, sp, wpb);
+    }
+    return launch_final_x3<FLUID, RECON, RS>(u0, u1, sp, plan, s);  // (a whole stage: plan_stage sends split donor-cell stages to the single march)
+  }
+  return false;
+}
+
+// whole donor-cell stage in one march (see fused_dc3_kernel); its FillDerived is out of place
+template <int FLUID, int RECON, int RS>
+inline bool launch_dc_march(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  if constexpr (RECON == APK_RC_DC) {
+    if (sp.phase == 2) {  // the cells were all retired in phase 1; only the scalars are left
+      if (sp.mflux) launch_scalar_update<RECON>(u0, u1, sp, plan.extra, s);
+      return true;
+    }
+    const int64_t run3 = sp.window ? (int64_t)sp.window_rows * sp.window_rl : (int64_t)u0.nx2 * (u0.nx1 + 2);
+    const int wpb = (int)((run3 + 61) / 62);
+    // two rows per lane (fused_dc3r2_kernel): whole blocks only -- a split stage's windows keep the one-row kernel
+    const bool two_rows = plan.dc_rows == 2;
+    const int wpb2 = (int)(((int64_t)(u0.nx2 / 2) * (u0.nx1 + 2) + 61) / 62);
+    const int wpb_run = two_rows ? wpb2 : wpb;  // wave columns per block of the kernel that will run
+    // measured on 8 x 128^3 (round 5, two-row march from the conserved state, ms per cycle of the headline, same box):
+    // 6 planes 3.67 - 3.70, 8: 3.64 - 3.66, 12: 3.65, 16: 3.61 - 3.63, 32: 3.61 - 3.66 -- the predictor itself is
+    // fastest at 8 (1.07 against 1.08 / 1.16 ms at 16 / 32), but what it leaves of the power budget is clock for the
+    // two kernels after it (finishing march 1.85 -> 1.82 -> 1.76 ms): 16 is the cycle's optimum
+    int kseg = (u0.nx3 >= 32) ? 16 : ((u0.nx3 >= 16) ? 8 : u0.nx3);
+    if (u0.nx3 >= 16 && (int64_t)wpb_run * ((u0.nx3 + 7) / 8) * u0.nblocks < 4 * 2048) {
+      // small packs (refined meshes of 16^3 blocks): a few waves per SIMD in all, so pick the segment length with
+      // the fewest plane-steps on the busiest SIMD -- a segment costs its planes plus about 1.5 for the prologue, a
+      // SIMD (1024 of them) works through ceil(waves / 1024) segments at the rate two resident waves share, and a
+      // wave that has its SIMD to itself runs 1.4 times as fast as one of a pair, not twice.  (Round 5: counted with
+      // the wave columns of the kernel that RUNS -- the two-row march has 3 per 16^3 block where the one-row march has
+      // 5 -- and per SIMD instead of per round of 2048 waves.  232 blocks of 16^3, two-row march, us per launch:
+      // segments of 4 planes 124, 8: 134, 6: 141, 16: 167 -- the order this estimate gives.)
+      double best = 1.0e300;
+      for (const int cand : {4, 6, 8, 16}) {
+        if (cand > u0.nx3) continue;
+        const int64_t waves = (int64_t)wpb_run * ((u0.nx3 + cand - 1) / cand) * u0.nblocks;
+        const double per_simd = waves <= 1024 ? 2.0 / 1.4 : (double)((waves + 1023) / 1024);
+        const double cost = per_simd * (cand + 1.5);
+        if (cost < best) best = cost, kseg = cand;
+      }
+    }
+    const int nseg = (u0.nx3 + kseg - 1) / kseg;
+    ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 0, s);
+    if (two_rows) {
+      const int64_t total2 = (int64_t)wpb2 * nseg * u0.nblocks;
+      const int per_xcd2 = (int)((total2 + 7) / 8);
+      const dim3 g2((unsigned)(per_xcd2 * 8), 1, 1);
+      constexpr int lds4 = 4 * nvars<FLUID>() * 64 * (int)sizeof(double);
+      return as_constants([&](auto LN, auto X1H, auto EX, auto FC) {
+        if constexpr (dc3r2_compiled(EX, FC, X1H, LN))
+          hipLaunchKernelGGL((fused_dc3r2_kernel<FLUID, RS, EX, (FC != 0), (X1H != 0), LN>), g2, dim3(64), lds4, s, u0, u1, sp, kseg, wpb2, nseg, per_xcd2);
+        return dc3r2_compiled(EX, FC, X1H, LN);
+      }, among<1, LEAN_PFLOOR>{plan.lean}, among<0, 1>{plan.x1_halo}, extra_among{plan.extra}, among<0, 1>{plan.from_cons != 0});
+    }
+    // (one row per lane: odd row counts, the windows of a split stage)
+    const int64_t total = (int64_t)wpb * nseg * u0.nblocks;
+    const int per_xcd = (int)((total + 7) / 8);
+    const dim3 g((unsigned)(per_xcd * 8), 1, 1);
+    constexpr int lds3 = 2 * nvars<FLUID>() * 64 * (int)sizeof(double);
+    const bool ok = as_constants([&](auto FC, auto EX, auto LN) {
+      if constexpr (dc3_compiled(EX, LN, FC, false))
+        hipLaunchKernelGGL((fused_dc3_kernel<FLUID, RS, EX, LN, (FC != 0)>), g, dim3(64), lds3, s, u0, u1, sp, kseg, wpb, nseg, per_xcd);
+      return dc3_compiled(EX, LN, FC, false);
+    }, among<0, 1>{plan.from_cons != 0}, extra_among{plan.extra}, among<0, LEAN_PFLOOR, 1>{plan.lean});
+    if (sp.mflux && sp.phase == 0) launch_scalar_update<RECON>(u0, u1, sp, plan.extra, s);
+    return ok && !plan.x1_halo;
+  }
+  return false;
+}
+
+// two-kernel stage (fused2_kernel.hpp): the x3 sweep writes its flux difference, then one
+// march does x1 + x2 and finishes.  A split stage runs the x3 sweep on plane windows in
+// phase 1 (it reads x3 ghost zones only) and the finishing march in phase 2.
+template <int FLUID, int RECON, int RS>
+inline bool launch_two_kernel(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  if constexpr (RECON != APK_RC_DC) {
+    constexpr int lds = march_lds_bytes<FLUID, RECON>();
+    const int du_pitch = ((u0.nx1 + 15) / 16) * 16;
+    bool ok = true;
+    if (sp.phase != 2) {
+      StageParams sp1 = sp;
+      sp1.du_first = 1;
+      sp1.du_pitch = du_pitch;
+      const int rpw = march_rows_per_wave(u0.nx1, u0.nx2);
+      dim3 g3((u0.nx1 + 64 / rpw - 1) / (64 / rpw), (u0.nx2 + rpw - 1) / rpw, u0.nblocks);
+      const int nseg = march_segments((int64_t)g3.x * g3.y * g3.z, u0.nx3);
+      g3.z *= nseg;
+      ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 2, s);
+      ok = as_constants([&](auto FC) {
+        if constexpr (x3_sweep_compiled(RECON, FC))
+          hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, 3, false, EXTRA_NONE, (FC != 0)>), g3, dim3(64), lds, s, u0, u1, sp1, nseg, rpw);
+        return x3_sweep_compiled(RECON, FC);
+      }, among<0, 1>{plan.from_cons != 0});
+    }
+    if (sp.phase != 1) {
+      StageParams sp2 = sp;
+      sp2.window = nullptr;
+      sp2.du_pitch = du_pitch;
+      {
+        ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 0, s);
+        ok = launch_m12f<FLUID, RECON, RS>(u0, u1, sp2, plan, s) && ok;
+      }
+      if (sp.mflux) launch_scalar_update<RECON>(u0, u1, sp, plan.extra, s);
+    }
+    return ok;
+  }
+  return false;
+}
+
+// the whole stage in one march (fused3_kernel.hpp: three-point reconstructions, input from a conserved state)
+template <int FLUID, int RECON, int RS>
+inline bool launch_single_march(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
+  ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 0, s);
+  return launch_s3<FLUID, RECON, RS>(u0, u1, sp, plan, s);
+}
+
+template <int FLUID, int RECON, int RS>
+inline int launch_fused_stage(const PackView &u0, const PackView &u1, const StageParams &sp,
+                              const StagePlan &plan, hipStream_t s) {
+  bool launched = false;  // (a plan no launcher has a kernel for is an error, never a stage skipped in silence)
+  switch (plan.form) {  // (in the order the forms' kernels lie in the code object)
+  case APK_FORM_X1: launched = launch_x1<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  case APK_FORM_DC_MARCH: launched = launch_dc_march<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  case APK_FORM_MARCH12_X3: launched = launch_march12_x3<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  case APK_FORM_SINGLE_MARCH: launched = launch_single_march<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  case APK_FORM_TWO_KERNEL: launched = launch_two_kernel<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  case APK_FORM_THREE_SWEEP: launched = launch_three_sweep<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  case APK_FORM_X1_X2: launched = launch_x1_x2<FLUID, RECON, RS>(u0, u1, sp, plan, s); break;
+  }
+  if (!launched) return APK_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
 }
 
 template <int FLUID, int RS>
 inline int launch_fused_family(const PackView &u0, const PackView &u1, int recon,
-                               const StageParams &sp, int extra, hipStream_t s) {
+                               const StageParams &sp, const StagePlan &plan, hipStream_t s) {
   switch (recon) {
-  case APK_RC_DC: return launch_fused_stage<FLUID, APK_RC_DC, RS>(u0, u1, sp, extra, s);
-  case APK_RC_PLM: return launch_fused_stage<FLUID, APK_RC_PLM, RS>(u0, u1, sp, extra, s);
-  case APK_RC_PPM: return launch_fused_stage<FLUID, APK_RC_PPM, RS>(u0, u1, sp, extra, s);
-  case APK_RC_WENOZ: return launch_fused_stage<FLUID, APK_RC_WENOZ, RS>(u0, u1, sp, extra, s);
-  case APK_RC_WENO3: return launch_fused_stage<FLUID, APK_RC_WENO3, RS>(u0, u1, sp, extra, s);
-  case APK_RC_LIMO3: return launch_fused_stage<FLUID, APK_RC_LIMO3, RS>(u0, u1, sp, extra, s);
+  case APK_RC_DC: return launch_fused_stage<FLUID, APK_RC_DC, RS>(u0, u1, sp, plan, s);
+  case APK_RC_PLM: return launch_fused_stage<FLUID, APK_RC_PLM, RS>(u0, u1, sp, plan, s);
+  case APK_RC_PPM: return launch_fused_stage<FLUID, APK_RC_PPM, RS>(u0, u1, sp, plan, s);
+  case APK_RC_WENOZ: return launch_fused_stage<FLUID, APK_RC_WENOZ, RS>(u0, u1, sp, plan, s);
+  case APK_RC_WENO3: return launch_fused_stage<FLUID, APK_RC_WENO3, RS>(u0, u1, sp, plan, s);
+  case APK_RC_LIMO3: return launch_fused_stage<FLUID, APK_RC_LIMO3, RS>(u0, u1, sp, plan, s);
   default: return APK_ERR_UNSUPPORTED;
   }
 }
 
-int launch_fused_euler_hlle(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, int extra, hipStream_t s);
-int launch_fused_euler_hllc(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, int extra, hipStream_t s);
-int launch_fused_mhd_hlle(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, int extra, hipStream_t s);
-int launch_fused_mhd_hlld(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, int extra, hipStream_t s);
+int launch_fused_euler_hlle(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, const StagePlan &plan, hipStream_t s);
+int launch_fused_euler_hllc(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, const StagePlan &plan, hipStream_t s);
+int launch_fused_mhd_hlle(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, const StagePlan &plan, hipStream_t s);
+int launch_fused_mhd_hlld(const PackView &u0, const PackView &u1, int recon, const StageParams &sp, const StagePlan &plan, hipStream_t s);
 
 }  // namespace apk

@@ -159,7 +159,7 @@ bool direct_neighbors(const apk_sim *s) {
 // Refined meshes: may the stages read a same-rank neighbour of the SAME level through the face table (built in
 // amr_rebuild) instead of the ghost zone behind that face?  Then the faces-only exchange of the stage loop skips
 // those copies and their ConsToPrim (AMR_XCHG_DIRECT).  The stage forms that follow the table: the single-march
-// donor-cell stage and the two-kernel stage (launch_fused_stage); refined-mesh stages run without FillDerived.
+// donor-cell stage and the two-kernel stage (stage_form.hpp: plan_stage); refined-mesh stages run without FillDerived.
 bool amr_direct(const apk_sim *s) {
   if (!s->direct_on || !s->amr || !s->d_face_nbr || s->mesh.ndim != 3 || !stage_can_fuse(s) || !amr_faces_only(s)) return false;
   return !scalars_or_extended_dedner(s) && high_order_stages_are_two_kernel(s, 0);

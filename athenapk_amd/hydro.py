@@ -141,6 +141,7 @@ class MeshData:
         h = C.c_void_p()
         _check(ctx.lib.apk_pack_create(ctx.h, C.byref(desc), C.byref(h)), ctx.lib, ctx.h)
         self.h = h
+        self.desc, self._blocks = desc, blocks  # (the shape, for StageForm)
 
     def __del__(self):
         try:
@@ -303,6 +304,17 @@ def StageFollowsX1Halo(u0, fluid, recon, riemann, eos, fill_derived=2, dedner=0,
     """apk_stage_x1_halo: does a whole-block stage of this scheme follow apk_stage_args.x1_halo?"""
     return bool(u0.ctx.lib.apk_stage_x1_halo(u0.h, C.byref(_cfg(fluid, recon, riemann)), C.byref(eos), int(fill_derived), int(dedner),
                                              int(prim_from_cons)))
+
+
+def StageForm(lib, desc, args):
+    """apk_stage_form: which kernel form apk_stage_fused takes for `args` (lib.StageArgs) on packs of the shape `desc`
+    (lib.PackDesc; its blocks are not read) -- host only, no context.  Returns (status, dict): the status apk_stage_fused
+    would return as far as shape and arguments decide it, and form (a name of lib.STAGE_FORMS), lean, dc_rows, from_cons,
+    x1_halo and the reason of a refusal."""
+    info = L.StageFormInfo()
+    rc = lib.apk_stage_form(C.byref(desc), C.byref(args), C.byref(info))
+    return rc, dict(form=L.STAGE_FORMS[info.form], lean=info.lean, dc_rows=info.dc_rows, from_cons=info.from_cons,
+                    x1_halo=bool(info.x1_halo), reason=(info.reason or b"").decode())
 
 
 def ConservedToPrimitive(md, fluid, eos):

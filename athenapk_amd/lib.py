@@ -151,6 +151,16 @@ class StageArgs(C.Structure):
                 ("face_neighbor", C.c_void_p), ("cons_store", C.c_int), ("prim_from_cons", C.c_int), ("x1_halo", C.c_void_p)]
 
 
+# apk_stage_form_kind, and what apk_stage_form fills in
+STAGE_FORMS = ("NONE", "X1", "X1_X2", "THREE_SWEEP", "MARCH12_X3", "DC_MARCH", "TWO_KERNEL", "SINGLE_MARCH")
+LEAN_PFLOOR = 2
+
+
+class StageFormInfo(C.Structure):
+    _fields_ = [("form", C.c_int), ("lean", C.c_int), ("dc_rows", C.c_int), ("from_cons", C.c_int), ("x1_halo", C.c_int),
+                ("reason", C.c_char_p)]
+
+
 class X1HaloBlock(C.Structure):
     _fields_ = [("recv", C.c_void_p * 2), ("send", C.c_void_p * 2)]
 
@@ -344,6 +354,7 @@ def _signatures():
         "apk_trial_flags": (i, [vp, i, vp]),
         "apk_stage_split_axis": (i, [vp, vp, i]),
         "apk_stage_single_march": (i, [vp, vp]),
+        "apk_stage_form": (i, [C.POINTER(PackDesc), C.POINTER(StageArgs), C.POINTER(StageFormInfo)]),
         "apk_bench_scheme_floor": (i, [i, i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
         "apk_stage_x1_halo": (i, [vp, vp, E, i, i, i]),
         "apk_stage_unphysical_read": (i, [vp, C.POINTER(C.c_longlong), vp]),
@@ -499,9 +510,9 @@ def load(strict=False):
                 "%s not found: run athenapk_amd.lib.build() / __graft_entry__.build() "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % path)
         lib = C.CDLL(path)
-        # (APK_LIB_PATH: a profiling variant, possibly built from an older commit for a same-box comparison -- entry
-        # points it lacks are left unbound; the product library must export every declared symbol)
-        variant = bool(os.environ.get("APK_LIB_PATH")) and not strict
+        # (APK_LIB_PATH, or a library from another directory: a profiling variant or a build of an older commit for a
+        # same-box comparison -- entry points it lacks are left unbound; the product library must export every declared symbol)
+        variant = (bool(os.environ.get("APK_LIB_PATH")) and not strict) or os.path.dirname(path) != _HERE
         skipped = []
         for name, (res, args) in _signatures().items():
             if variant and not hasattr(lib, name):
@@ -512,7 +523,7 @@ def load(strict=False):
             fn.argtypes = args
         if skipped:  # (said aloud: a call through an unbound entry point would go out with default int argtypes)
             import warnings
-            warnings.warn("APK_LIB_PATH=%s lacks %d declared entry point(s), left unbound: %s"
+            warnings.warn("%s lacks %d declared entry point(s), left unbound: %s"
                           % (path, len(skipped), ", ".join(skipped)))
         _LIBS[key] = lib
     return _LIBS[key]

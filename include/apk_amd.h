@@ -326,13 +326,40 @@ int apk_stage_split_axis(const apk_pack *u0, const apk_flux_cfg *cfg, int fill_d
 /* 1 if a whole-block stage of this scheme with these options follows apk_stage_args.x1_halo: the lean two-row donor-cell
  * march (3-D, fill_derived 0 / 2, nx2 even) and the lean two-kernel stage's finishing march -- from stored primitives or
  * (prim_from_cons != 0) from a conserved state, but not the stages that take the single march (apk_stage_single_march) --
- * without passive scalars.  A caller checks BEFORE it leaves x1 strips out of its pack / unpack plans. */
+ * without passive scalars (donor cell with prim_from_cons = 2, which apk_stage_fused refuses, answers 0).  A caller checks
+ * BEFORE it leaves x1 strips out of its pack / unpack plans. */
 int apk_stage_x1_halo(const apk_pack *u0, const apk_flux_cfg *cfg, const apk_eos *eos, int fill_derived, int dedner, int prim_from_cons);
 /* 1 if a whole-block stage of this scheme in its lean form with prim_from_cons != 0 runs as ONE march (hydro with PLM:
  * x1 by wave shifts, two x2 rows per lane, x3 carried along the march -- no flux-difference array; the three tasks
  * hydro.cpp:1025-1208 + hydro_driver.cpp:534-544 in a single pass over the conserved state), 0 if it takes the two-kernel
  * form.  A split stage (phase != 0) always takes the two kernels: a caller that can choose leaves such a stage whole. */
 int apk_stage_single_march(const apk_pack *u0, const apk_flux_cfg *cfg);
+/* Which kernel form a stage takes, decided on the host from the pack's shape and the arguments alone: no context, no
+ * device.  Returns what apk_stage_fused() would return for `args` on packs of this shape, as far as shape and arguments
+ * decide it (APK_OK, or the code of the refusal), and fills `out`: the form, the lean level of its kernels (0 general,
+ * 1 lean, 2 lean with the pressure floor / trial count), the x2 rows per lane of the donor-cell march (1 or 2, else 0),
+ * the input its kernels convert (0, or prim_from_cons), whether they follow x1_halo, and -- of a refusal -- a short
+ * sentence naming the rule that refused (a static string; "" otherwise).  shape->blocks is not read; of args->window,
+ * face_neighbor and x1_halo->blocks only whether they are NULL. */
+enum apk_stage_form_kind {
+  APK_FORM_NONE = 0,         /* refused */
+  APK_FORM_X1 = 1,           /* 1-D: the finishing x1 sweep */
+  APK_FORM_X1_X2 = 2,        /* 2-D: x1 sweep, finishing x2 march */
+  APK_FORM_THREE_SWEEP = 3,  /* 3-D: x1 sweep, x2 march, finishing x3 march */
+  APK_FORM_MARCH12_X3 = 4,   /* 3-D donor cell with FillDerived in place: x1 + x2 in one march, finishing x3 march */
+  APK_FORM_DC_MARCH = 5,     /* 3-D donor cell: the whole stage in one march, one or two x2 rows per lane */
+  APK_FORM_TWO_KERNEL = 6,   /* 3-D: x3 sweep, then one finishing x1 + x2 march (apk_stage_split_axis() == 3) */
+  APK_FORM_SINGLE_MARCH = 7  /* 3-D hydro PLM from a conserved state: the whole stage in one march (apk_stage_single_march) */
+};
+typedef struct apk_stage_form_info {
+  int form; /* apk_stage_form_kind */
+  int lean;
+  int dc_rows;
+  int from_cons;
+  int x1_halo;
+  const char *reason;
+} apk_stage_form_info;
+int apk_stage_form(const apk_pack_desc *shape, const apk_stage_args *args, apk_stage_form_info *out);
 
 /* Replaces EquationOfState::ConservedToPrimitive(MeshData<Real>*) over the ENTIRE block
  * src/eos/adiabatic_hydro.cpp:33-55, adiabatic_glmmhd.cpp:33-56 (pkg->FillDerivedMesh,

@@ -2,7 +2,7 @@
 
 The other parity tests use packs of 1-3 small blocks of one dx.  Several launch choices depend on the pack: the segment
 count of a march (march_segments), the rows per wave (march_rows_per_wave), the donor-cell predictor's segment length
-(its cost model in launch_fused_stage), the two-row donor-cell march (even nx2 >= 4), the XCD-dealt grids and du_pitch.
+(its cost model in launch_dc_march), the two-row donor-cell march (even nx2 >= 4), the XCD-dealt grids and du_pitch.
 And many launches put nx3 * nblocks (3-D) or nblocks (1-D, 2-D) into grid y or z.  Every pack here gives its blocks
 their own data (own phases, every third block a shock instead of a wave) and their own dx (levels 0-2 mixed), so a
 mixed-up block index or dx changes the answer.
@@ -138,14 +138,14 @@ def march_segments(waves, n_along):
 
 
 def x3_sweep_segments(nx):
-    """segments of the two-kernel stage's x3 sweep (launch_fused_stage, two_kernel_stage_applies branch)"""
+    """segments of the two-kernel stage's x3 sweep (launch_two_kernel)"""
     rpw = march_rows_per_wave(nx[0], nx[1])
     waves = -(-nx[0] // (64 // rpw)) * -(-nx[1] // rpw)
     return rpw, lambda nb: march_segments(waves * nb, nx[2])
 
 
 def dc_kseg(nx, nblocks):
-    """the donor-cell predictor's segment length (launch_fused_stage, RECON == APK_RC_DC, two-row march if nx2 even)"""
+    """the donor-cell predictor's segment length (launch_dc_march, two-row march if nx2 even)"""
     two_rows = nx[1] % 2 == 0 and nx[1] >= 4
     wpb = ((nx[1] // 2) * (nx[0] + 2) + 61) // 62 if two_rows else (nx[1] * (nx[0] + 2) + 61) // 62
     kseg = 16 if nx[2] >= 32 else (8 if nx[2] >= 16 else nx[2])
@@ -172,7 +172,7 @@ def _dc(nx, nb):
 
 
 def _s3(nx, nb):
-    if nx[0] >= 32 and nx[1] % 2 == 0:   # single_march_stage_applies (fused3_kernel.hpp)
+    if nx[0] >= 32 and nx[1] % 2 == 0:   # single_march_stage_applies (stage_form.hpp)
         kseg = min(15, nx[2])
         return "single_march", "kseg%d_nseg%d" % (kseg, -(-nx[2] // kseg))
     return "two_kernel_rk", "nx1_below_32_takes_two_kernel"
