@@ -133,6 +133,17 @@ inline int set_err(apk_ctx *ctx, int code, const char *what, hipError_t e = hipS
   return code;
 }
 
+// at least n doubles in ctx->d_partial (contents are not kept)
+inline int ensure_partial_doubles(apk_ctx *ctx, size_t n) {
+  if (ctx->partial_cap >= n) return APK_OK;
+  if (ctx->d_partial) (void)hipFree(ctx->d_partial);
+  ctx->d_partial = nullptr;
+  ctx->partial_cap = 0;
+  if (hipMalloc(&ctx->d_partial, n * sizeof(double)) != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "partial buffer");
+  ctx->partial_cap = n;
+  return APK_OK;
+}
+
 #define APK_HIP_TRY(ctx, expr)                                              \
   do {                                                                      \
     hipError_t e__ = (expr);                                                \

@@ -1,10 +1,13 @@
 // cluster.cpp -- problem_id = cluster in the standalone host driver: the options of ProblemInitPackageData
 // (src/pgen/cluster.cpp:114-250) for the slice built here, what is refused of the rest, the problem generator
-// (cluster.cpp:469-550, 630-653), the per-block origins of the gravity source and the C entries of include/apk_host.h.
-// The model itself (ClusterGravity, ACCEPTEntropyProfile, HydrostaticEquilibriumSphere) is host/cluster_model.cpp.
+// (cluster.cpp:469-653), the per-block origins of the gravity and feedback sources, the feedback sources of a stage
+// (cluster.cpp:76-80) and the C entries of include/apk_host.h.  The model itself is host/cluster_model.cpp (ClusterGravity,
+// ACCEPTEntropyProfile, HydrostaticEquilibriumSphere) and host/feedback_model.cpp (the jet frame, AGNFeedback's derived
+// numbers, the magnetic tower's scaling and initial field).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
+#include <algorithm>
 #include <limits>
 
 #include "cluster.hpp"
@@ -32,6 +35,7 @@ double UnitsState::mpc() const { return cgs::mpc / code_length_cgs; }
 double UnitsState::km_s() const { return cgs::km_s / (code_length_cgs / code_time_cgs); }
 double UnitsState::kev() const { return cgs::kev / code_energy_cgs(); }
 double UnitsState::g() const { return 1.0 / code_mass_cgs; }
+double UnitsState::speed_of_light() const { return 2.99792458e10 / (code_length_cgs / code_time_cgs); }
 
 namespace host {
 
@@ -39,6 +43,9 @@ namespace {
 
 const char *kGrav = "problem/cluster/gravity";
 const char *kHse = "problem/cluster/hydrostatic_equilibrium";
+const char *kAgn = "problem/cluster/agn_feedback";
+const char *kTower = "problem/cluster/magnetic_tower";
+const char *kJet = "problem/cluster/precessing_jet";
 
 [[noreturn]] void refuse(const std::string &key, const std::string &why) {
   throw std::runtime_error("problem_id = cluster: " + key + " " + why);
@@ -52,13 +59,11 @@ void refuse_unbuilt(apk_sim *s) {
     refuse("parthenon/mesh/refinement", "must be none: the cluster problem runs on uniform meshes only (static refinement included)");
   if (s->mesh.nx[2] == 1) refuse("parthenon/mesh/nx3", "= 1: the cluster problem is three-dimensional");
   if (s->mesh.nx[1] == 1) refuse("parthenon/mesh/nx2", "= 1: the cluster problem is three-dimensional");
-  if (pin.GetOrAddReal("problem/cluster/agn_feedback", "fixed_power", 0.0) != 0.0)
-    refuse("problem/cluster/agn_feedback/fixed_power", "must be 0: AGN feedback is not implemented");
+  if (pin.GetOrAddBoolean(kAgn, "enable_tracer", false))
+    refuse("problem/cluster/agn_feedback/enable_tracer", "must be false: the AGN passive-scalar tag is not implemented");
   if (pin.DoesBlockExist("problem/cluster/agn_triggering") &&
       pin.GetOrAddString("problem/cluster/agn_triggering", "triggering_mode", "NONE") != "NONE")
     refuse("problem/cluster/agn_triggering/triggering_mode", "must be NONE: AGN triggering is not implemented");
-  if (pin.DoesBlockExist("problem/cluster/magnetic_tower"))
-    refuse("problem/cluster/magnetic_tower", "is not implemented: remove the block");
   if (pin.DoesBlockExist("problem/cluster/stellar_feedback"))
     refuse("problem/cluster/stellar_feedback", "is not implemented: remove the block");
   // (the reference's default is ENABLED: the deck has to say that it runs without)
@@ -106,6 +111,115 @@ HeProfile block_profile(apk_sim *s, int lb) {
 
 bool sphere_available(const apk_sim *s) { return s->cluster.enabled && s->pkg.units.has_composition; }
 
+// AGNFeedback, MagneticTower and JetCoordsFactory as the reference's constructors read them (agn_feedback.cpp:34-185,
+// magnetic_tower.hpp:178-219, jet_coords.hpp:100-107), and what this path refuses of them
+void feedback_initialize(apk_sim *s, bool agn_block, bool tower_block) {
+  ParameterInput &pin = s->pin;
+  const UnitsState &u = s->pkg.units;
+  const double inf = std::numeric_limits<double>::infinity();
+  apk_agn_feedback_options &o = s->agn_opt;
+  o = apk_agn_feedback_options{};
+  const bool mhd = s->pkg.fluid == APK_FLUID_GLMMHD;
+
+  o.jet_theta = pin.GetOrAddReal(kJet, "jet_theta", 0.0);
+  o.jet_phi_dot = pin.GetOrAddReal(kJet, "jet_phi_dot", 0.0);
+  o.jet_phi0 = pin.GetOrAddReal(kJet, "jet_phi0", 0.0);
+
+  // the tower first: AGN feedback's refusals look at it
+  apk_magnetic_tower_cfg &t = s->tower;
+  t = apk_magnetic_tower_cfg{};
+  t.li_alpha = pin.GetOrAddReal(kTower, "li_alpha", 0.0);
+  t.l_scale = pin.GetOrAddReal(kTower, "l_scale", 0.0);
+  t.donut_offset = pin.GetOrAddReal(kTower, "donut_offset", 0.0);
+  t.donut_thickness = pin.GetOrAddReal(kTower, "donut_thickness", 0.0);
+  o.initial_field = pin.GetOrAddReal(kTower, "initial_field", 0.0);
+  o.fixed_field_rate = pin.GetOrAddReal(kTower, "fixed_field_rate", 0.0);
+  o.fixed_mass_rate = pin.GetOrAddReal(kTower, "fixed_mass_rate", 0.0);
+  t.l_mass_scale = pin.GetOrAddReal(kTower, "l_mass_scale", 0.0);
+  const std::string potential_str = pin.GetOrAddString(kTower, "potential_type", "undefined");
+  t.potential = potential_str == "donut" ? APK_TOWER_DONUT : (potential_str == "li" ? APK_TOWER_LI : APK_TOWER_UNDEFINED);
+  // (stricter than the reference, which meets an undefined potential inside a kernel)
+  if (tower_block && t.potential == APK_TOWER_UNDEFINED)
+    refuse("problem/cluster/magnetic_tower/potential_type", "= " + potential_str + ": must be donut or li (Unknown magnetic tower potential.)");
+  tower_check_combination(t);
+  o.li_alpha = t.li_alpha, o.l_scale = t.l_scale, o.donut_offset = t.donut_offset, o.donut_thickness = t.donut_thickness;
+  o.l_mass_scale = t.l_mass_scale, o.tower_potential = t.potential;
+  const struct {
+    const char *key;
+    double v;
+  } tower_rates[] = {{"initial_field", o.initial_field}, {"fixed_field_rate", o.fixed_field_rate}, {"fixed_mass_rate", o.fixed_mass_rate}};
+  for (const auto &r : tower_rates)
+    if (r.v != 0.0 && !mhd) refuse(std::string(kTower) + "/" + r.key, "!= 0 needs hydro/fluid = glmmhd");
+
+  // AGN feedback
+  AgnFeedbackInput in;
+  in.fixed_power = pin.GetOrAddReal(kAgn, "fixed_power", 0.0);
+  in.vceil = pin.GetOrAddReal(kAgn, "vceil", inf);
+  in.efficiency = pin.GetOrAddReal(kAgn, "efficiency", 1e-3);
+  in.thermal_fraction = pin.GetOrAddReal(kAgn, "thermal_fraction", 0.0);
+  in.kinetic_fraction = pin.GetOrAddReal(kAgn, "kinetic_fraction", 0.0);
+  in.magnetic_fraction = pin.GetOrAddReal(kAgn, "magnetic_fraction", 0.0);
+  in.thermal_radius = pin.GetOrAddReal(kAgn, "thermal_radius", 0.01);
+  in.kinetic_jet_radius = pin.GetOrAddReal(kAgn, "kinetic_jet_radius", 0.01);
+  in.kinetic_jet_thickness = pin.GetOrAddReal(kAgn, "kinetic_jet_thickness", 0.02);
+  in.kinetic_jet_offset = pin.GetOrAddReal(kAgn, "kinetic_jet_offset", 0.02);
+  o.disabled = pin.GetOrAddBoolean(kAgn, "disabled", false) ? 1 : 0;
+  in.enable_magnetic_tower_mass_injection = pin.GetOrAddBoolean(kAgn, "enable_magnetic_tower_mass_injection", true);
+  in.has_velocity = pin.DoesParameterExist(kAgn, "kinetic_jet_velocity");
+  if (in.has_velocity) in.kinetic_jet_velocity = pin.GetReal(kAgn, "kinetic_jet_velocity");
+  in.has_temperature = pin.DoesParameterExist(kAgn, "kinetic_jet_temperature");
+  if (in.has_temperature) in.kinetic_jet_temperature = pin.GetReal(kAgn, "kinetic_jet_temperature");
+  in.Tceil = pin.GetOrAddReal(kAgn, "Tceil", inf);
+  o.fixed_power = in.fixed_power, o.efficiency = in.efficiency, o.vceil = in.vceil, o.Tceil = in.Tceil;
+  o.enable_magnetic_tower_mass_injection = in.enable_magnetic_tower_mass_injection ? 1 : 0;
+  o.thermal_radius = in.thermal_radius, o.kinetic_jet_radius = in.kinetic_jet_radius;
+  o.kinetic_jet_thickness = in.kinetic_jet_thickness, o.kinetic_jet_offset = in.kinetic_jet_offset;
+  o.thermal_fraction = in.thermal_fraction, o.kinetic_fraction = in.kinetic_fraction, o.magnetic_fraction = in.magnetic_fraction;
+
+  if (in.fixed_power != 0.0 && !u.has_composition)
+    refuse("problem/cluster/agn_feedback/fixed_power", "!= 0 requires units and gas composition. Set a 'units' block and "
+           "'hydro/He_mass_fraction' in the input file.");
+  // (the reference meets this in the first stage: "AGNFeedback::FeedbackSrcTerm Magnetic, Thermal, and Kinetic fractions
+  // are all zero")
+  if (in.fixed_power != 0.0 && in.thermal_fraction == 0.0 && in.kinetic_fraction == 0.0 && in.magnetic_fraction == 0.0)
+    refuse("problem/cluster/agn_feedback/fixed_power", "!= 0 with thermal_fraction, kinetic_fraction and magnetic_fraction all zero "
+           "(AGNFeedback::FeedbackSrcTerm Magnetic, Thermal, and Kinetic fractions are all zero)");
+  if (in.magnetic_fraction != 0.0 && !mhd) refuse("problem/cluster/agn_feedback/magnetic_fraction", "!= 0 needs hydro/fluid = glmmhd");
+
+  // the derived jet numbers need the units: with them the constructor's requirements hold for every deck, as in the
+  // reference; without them (no feedback possible, see above) the keys are kept as read
+  if (u.has_composition && agn_block) {
+    in.speed_of_light = u.speed_of_light();
+    in.mbar_gm1_over_kb = u.mbar_over_kb * (s->pkg.eos.gamma - 1.0);
+    s->agn = agn_feedback_model(in);
+    const AgnFeedbackModel &m = s->agn;
+    o.configured = 1;
+    o.assumed_cold_jet = m.assumed_cold_jet ? 1 : 0;
+    o.thermal_fraction = m.thermal_fraction, o.kinetic_fraction = m.kinetic_fraction, o.magnetic_fraction = m.magnetic_fraction;
+    o.thermal_mass_fraction = m.thermal_mass_fraction, o.kinetic_mass_fraction = m.kinetic_mass_fraction;
+    o.magnetic_mass_fraction = m.magnetic_mass_fraction;
+    o.kinetic_jet_velocity = m.kinetic_jet_velocity, o.kinetic_jet_temperature = m.kinetic_jet_temperature;
+    o.kinetic_jet_e = m.kinetic_jet_e, o.eceil = m.eceil;
+    o.speed_of_light = in.speed_of_light, o.mbar_gm1_over_kb = in.mbar_gm1_over_kb;
+    o.power = m.power(), o.mass_rate = m.mass_rate();
+  }
+  o.active = (o.configured && in.fixed_power != 0.0 && !o.disabled) ? 1 : 0;
+  o.tower_power_scaling = (o.active && o.magnetic_fraction != 0.0) ? 1 : 0;
+  // whatever evaluates the tower needs its potential and its length scales (MagneticTowerObj's constructor)
+  const bool tower_used = o.tower_power_scaling || o.initial_field != 0.0 || o.fixed_field_rate != 0.0;
+  if (tower_used && t.potential == APK_TOWER_UNDEFINED)
+    refuse("problem/cluster/magnetic_tower/potential_type", "must be donut or li (Unknown magnetic tower potential.)");
+  if (tower_used) tower_check_scales(t);
+  if ((o.active || o.fixed_field_rate != 0.0) && s->pkg.diffint == APK_DIFFINT_RKL2)
+    refuse(o.active ? "problem/cluster/agn_feedback/fixed_power" : "problem/cluster/magnetic_tower/fixed_field_rate",
+           "!= 0 is not supported with diffusion/integrator = rkl2");
+  s->pkg.feedback_srcterm = o.active || o.fixed_field_rate != 0.0;
+}
+
+apk_jet_coords jet_at(const apk_sim *s, double time) {
+  return jet_coords_at(s->agn_opt.jet_theta, s->agn_opt.jet_phi_dot, s->agn_opt.jet_phi0, time);
+}
+
 }  // namespace
 
 void cluster_initialize(apk_sim *s) {
@@ -118,6 +232,8 @@ void cluster_initialize(apk_sim *s) {
   if (pin.BlocksWithPrefix("problem/cluster").empty())
     throw std::runtime_error("unknown job/problem_id: cluster is known only together with its <problem/cluster/...> blocks, and "
                              "this deck has none (problem/cluster/gravity/gravity_srcterm is required)");
+  // (reading a key with its default enters it: which blocks the deck itself has is asked first)
+  const bool agn_block = pin.DoesBlockExist(kAgn), tower_block = pin.DoesBlockExist(kTower);
   refuse_unbuilt(s);
   o.enabled = 1;
   o.gravitational_constant = u.gravitational_constant();
@@ -173,6 +289,7 @@ void cluster_initialize(apk_sim *s) {
   if (o.gravity_srcterm && gi.which_bcg_g == APK_BCG_HERNQUIST && !(gi.r_bcg_s > 0.0))
     refuse("problem/cluster/gravity/r_bcg_s", "must be positive");
   s->pkg.gravity_srcterm = o.gravity_srcterm != 0;
+  feedback_initialize(s, agn_block, tower_block);
 
   // ACCEPTEntropyProfile (entropy_profiles.hpp:25-34)
   o.k_0 = pin.GetOrAddReal("problem/cluster/entropy_profile", "k_0", 20 * u.kev() * u.cm() * u.cm());
@@ -246,17 +363,102 @@ void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u) {
           at(4, k, j, i) = P_r / gm1;
         }
   }
-  if (mhd && o.init_uniform_b_field) {
-    const double bx = o.uniform_b_field_bx, by = o.uniform_b_field_by, bz = o.uniform_b_field_bz;
+  if (mhd && s->agn_opt.initial_field != 0.0) {
+    // the initial magnetic tower: the potential on the interior plus one cell, jet frame at time 0, B its
+    // central-difference curl and 0.5 B^2 added to the energy (cluster.cpp:556-625, magnetic_tower.cpp:206-235)
+    const int n1 = m.ie - m.is + 1, n2 = m.je - m.js + 1, n3 = m.ke - m.ks + 1;
+    std::vector<double> x1, x2, x3;
+    for (int i = m.is - 1; i <= m.ie + 1; ++i) x1.push_back(xc(s, x0, 0, i));
+    for (int j = m.js - 1; j <= m.je + 1; ++j) x2.push_back(xc(s, x0, 1, j));
+    for (int k = m.ks - 1; k <= m.ke + 1; ++k) x3.push_back(xc(s, x0, 2, k));
+    const size_t nb = (size_t)n1 * n2 * n3;
+    std::vector<double> b(3 * nb);
+    tower_initial_field_block(s->tower, jet_at(s, 0.0), s->agn_opt.initial_field, x1.data(), n1, x2.data(), n2, x3.data(), n3, s->dx,
+                              b.data());
     for (int k = m.ks; k <= m.ke; ++k)
       for (int j = m.js; j <= m.je; ++j)
         for (int i = m.is; i <= m.ie; ++i) {
+          const size_t q = ((size_t)(k - m.ks) * n2 + (j - m.js)) * n1 + (i - m.is);
+          const double bx = b[q], by = b[nb + q], bz = b[2 * nb + q];
           at(5, k, j, i) = bx;
           at(6, k, j, i) = by;
           at(7, k, j, i) = bz;
           at(4, k, j, i) += 0.5 * (bx * bx + by * by + bz * bz);
         }
   }
+  if (mhd && o.init_uniform_b_field) {
+    // (cluster.cpp:630-653: added to whatever the potential left)
+    const double bx = o.uniform_b_field_bx, by = o.uniform_b_field_by, bz = o.uniform_b_field_bz;
+    for (int k = m.ks; k <= m.ke; ++k)
+      for (int j = m.js; j <= m.je; ++j)
+        for (int i = m.is; i <= m.ie; ++i) {
+          const double bx_i = at(5, k, j, i), by_i = at(6, k, j, i), bz_i = at(7, k, j, i);
+          at(5, k, j, i) += bx;
+          at(6, k, j, i) += by;
+          at(7, k, j, i) += bz;
+          at(4, k, j, i) += bx_i * bx + by_i * by + bz_i * bz + 0.5 * (bx * bx + by * by + bz * bz);
+        }
+  }
+}
+
+bool cluster_needs_block_origins(const apk_sim *s) {
+  return s->pkg.gravity_srcterm || (s->cluster.enabled && (s->agn_opt.configured || s->tower.potential != APK_TOWER_UNDEFINED));
+}
+
+// MagneticTowerReducePowerContribs with its reduction over ranks (magnetic_tower.cpp:301-317, hydro_driver.cpp:409-449):
+// every local block's pair into its slot of a zeroed array over all blocks, one sum over ranks, the slots added in global
+// block order.  Adding zeros is exact: the two sums do not depend on the distribution of the blocks.
+int cluster_tower_contribs(apk_sim *s, double time, double out[2]) {
+  const Mesh &m = s->mesh;
+  const int nlb = (int)m.local_gids.size();
+  if (!s->d_block_xmin) return fail(s, APK_ERR_INVALID, "magnetic_tower_contribs needs problem_id = cluster with a magnetic tower");
+  SIM_TRY(s, sync_ghosts(s));  // (materialises the stored primitives when the cycle kept them out of memory)
+  if (!s->d_tower_contribs) SIM_TRY(s, dev_alloc(s, "tower_contribs", sizeof(double) * 2 * (size_t)std::max(nlb, 1), &s->d_tower_contribs));
+  const apk_jet_coords jet = jet_at(s, time);
+  SIM_TRY(s, apk_magnetic_tower_power_contribs(s->ctx, s->mu0(), &s->tower, &jet, s->d_block_xmin, s->d_tower_contribs, s->stream));
+  std::vector<double> local(2 * (size_t)nlb), all(2 * (size_t)m.nblocks_total, 0.0);
+  SIM_HIP(s, hipMemcpyAsync(local.data(), s->d_tower_contribs, sizeof(double) * local.size(), hipMemcpyDeviceToHost, hs(s)));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  for (int lb = 0; lb < nlb; ++lb)
+    for (int q = 0; q < 2; ++q) all[2 * (size_t)m.local_gids[lb] + q] = local[2 * (size_t)lb + q];
+  if (s->have_comm && s->nranks > 1 && s->comm.allreduce_sum(s->comm.user, all.data(), (int)all.size()) != 0)
+    return fail(s, APK_ERR_DEVICE, "allreduce_sum failed");
+  out[0] = out[1] = 0.0;
+  for (size_t g = 0; g < (size_t)m.nblocks_total; ++g) {
+    out[0] += all[2 * g];
+    out[1] += all[2 * g + 1];
+  }
+  return APK_OK;
+}
+
+// the feedback part of ClusterUnsplitSrcTerm (cluster.cpp:76-80): AGNFeedback::FeedbackSrcTerm -- the thermal and kinetic
+// channels, then MagneticTower::PowerSrcTerm with the power-scaled field (agn_feedback.cpp:411-416) -- and
+// MagneticTower::FixedFieldSrcTerm.  The jet frame is the one of the cycle's start time in every stage (tm.time).
+int cluster_feedback_sources(apk_sim *s, double beta_dt) {
+  const apk_agn_feedback_options &o = s->agn_opt;
+  const apk_jet_coords jet = jet_at(s, s->time);
+  try {
+    if (o.active) {
+      const apk_agn_feedback_cfg cfg = agn_feedback_stage_numbers(s->agn, beta_dt);
+      SIM_TRY(s, apk_agn_feedback_src(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, &cfg, &jet, s->d_block_xmin, s->stream));
+      const double magnetic_power = s->agn.power() * s->agn.magnetic_fraction;
+      const double magnetic_mass_rate = s->agn.mass_rate() * s->agn.magnetic_mass_fraction;
+      if (magnetic_power != 0) {
+        const double field_to_add = tower_field_to_add(s->tower_linear_contrib, s->tower_quadratic_contrib, beta_dt, magnetic_power);
+        (void)tower_density_to_add(magnetic_mass_rate * beta_dt, s->tower.l_mass_scale);  // (its requirement, as a step error)
+        SIM_TRY(s, apk_magnetic_tower_src(s->ctx, s->mu0(), &s->tower, &jet, s->d_block_xmin, field_to_add,
+                                          magnetic_mass_rate * beta_dt, s->stream));
+      }
+    }
+    if (o.fixed_field_rate != 0) {
+      (void)tower_density_to_add(o.fixed_mass_rate * beta_dt, s->tower.l_mass_scale);
+      SIM_TRY(s, apk_magnetic_tower_src(s->ctx, s->mu0(), &s->tower, &jet, s->d_block_xmin, o.fixed_field_rate * beta_dt,
+                                        o.fixed_mass_rate * beta_dt, s->stream));
+    }
+  } catch (const std::exception &e) {
+    return fail(s, APK_ERR_INVALID, e.what());
+  }
+  return APK_OK;
 }
 
 // the origins apk_gravity_src takes: every local block's lower interior corner, then the mesh's lower corner
@@ -271,7 +473,7 @@ int cluster_device_setup(apk_sim *s) {
     // the kernel rebuilds the block's first global index from the corner: the cell centres it then forms must be xc()'s
     for (int d = 0; d < 3; ++d)
       if (std::rint((h[3 * (size_t)lb + d] - s->xmin[d]) / s->dx[d]) != x0[d])
-        return fail(s, APK_ERR_INVALID, "cluster gravity: a block's corner does not give back its global cell index");
+        return fail(s, APK_ERR_INVALID, "cluster sources: a block's corner does not give back its global cell index");
   }
   for (int d = 0; d < 3; ++d) h[3 * (size_t)nlb + d] = s->xmin[d];
   SIM_TRY(s, dev_alloc(s, "block_xmin", h.size() * sizeof(double), &s->d_block_xmin));
@@ -369,6 +571,59 @@ int apk_sim_gravity_src(apk_sim *s, double beta_dt) {
   SIM_TRY(s, apk_gravity_src(s->ctx, s->mu0(), &s->cluster.gravity, s->d_block_xmin, beta_dt, s->stream));
   SIM_HIP(s, hipStreamSynchronize(hs(s)));
   return APK_OK;
+}
+
+int apk_sim_agn_feedback_options(const apk_sim *s, apk_agn_feedback_options *opt) {
+  if (!s || !opt) return APK_ERR_INVALID;
+  *opt = s->agn_opt;
+  return APK_OK;
+}
+
+int apk_sim_agn_feedback_stage_numbers(const apk_sim *s, double beta_dt, double time, apk_agn_feedback_cfg *cfg, apk_jet_coords *jet) {
+  if (!s || !cfg || !jet || !s->cluster.enabled || !s->agn_opt.configured) return APK_ERR_INVALID;
+  *cfg = agn_feedback_stage_numbers(s->agn, beta_dt);
+  *jet = jet_at(s, time);
+  return APK_OK;
+}
+
+int apk_sim_magnetic_tower_field_to_add(apk_sim *s, double lin, double quad, double beta_dt, double power, double *field) {
+  if (!s || !field) return APK_ERR_INVALID;
+  try {
+    *field = tower_field_to_add(lin, quad, beta_dt, power);
+  } catch (const std::exception &e) {
+    return fail(s, APK_ERR_INVALID, e.what());
+  }
+  return APK_OK;
+}
+
+int apk_sim_agn_feedback_src(apk_sim *s, double beta_dt, double time) {
+  if (!s || s->host_only) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || !s->agn_opt.configured || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "agn_feedback_src needs problem_id = cluster with a <problem/cluster/agn_feedback> block, units and gas composition");
+  SIM_TRY(s, sync_ghosts(s));  // (materialises the stored primitives when the cycle kept them out of memory)
+  const apk_agn_feedback_cfg cfg = agn_feedback_stage_numbers(s->agn, beta_dt);
+  const apk_jet_coords jet = jet_at(s, time);
+  SIM_TRY(s, apk_agn_feedback_src(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, &cfg, &jet, s->d_block_xmin, s->stream));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+int apk_sim_magnetic_tower_src(apk_sim *s, double field, double mass, double time) {
+  if (!s || s->host_only) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || s->tower.potential == APK_TOWER_UNDEFINED || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "magnetic_tower_src needs problem_id = cluster with a <problem/cluster/magnetic_tower> block");
+  SIM_TRY(s, sync_ghosts(s));
+  const apk_jet_coords jet = jet_at(s, time);
+  SIM_TRY(s, apk_magnetic_tower_src(s->ctx, s->mu0(), &s->tower, &jet, s->d_block_xmin, field, mass, s->stream));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+int apk_sim_magnetic_tower_contribs(apk_sim *s, double time, double out[2]) {
+  if (!s || s->host_only || !out) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || s->tower.potential == APK_TOWER_UNDEFINED)
+    return fail(s, APK_ERR_INVALID, "magnetic_tower_contribs needs problem_id = cluster with a <problem/cluster/magnetic_tower> block");
+  return cluster_tower_contribs(s, time, out);
 }
 
 }  // extern "C"

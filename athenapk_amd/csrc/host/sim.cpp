@@ -486,7 +486,9 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
   const bool cool = s->pkg.cooling;
   const double h = s->pkg.cool_table_hash;
   // With rkl2 one more, last: the diffusive limit itself, which sizes the next cycle's super-time-steps.
-  double mins[8] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0, (e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0,
+  // (the AGN feedback source's own pressure check shares the pressure slot: -2 below -1, so that every rank sees which)
+  double mins[8] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0,
+                    (e.flags & APK_FLAG_AGN_NEG_PRESSURE) ? -2.0 : ((e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0),
                     (e.flags & (APK_FLAG_COOL_MAX_ITER | APK_FLAG_COOL_TABLE)) ? -1.0 : 0.0, h, -h, e.dt_diff_local};
   if (s->have_comm && s->nranks > 1) {
     if (s->comm.allreduce_min(s->comm.user, mins, sts ? 8 : (cool ? 7 : 4)) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
@@ -498,6 +500,8 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
     if (e.flags & APK_FLAG_COOL_TABLE) return fail(s, APK_ERR_INVALID, "FATAL ERROR in [CoolingTable::DeDt]: Failed to find log_temp");
     return fail(s, APK_ERR_INVALID, "cooling failed on another rank");
   }
+  // agn_feedback.cpp:407-408: the reference aborts inside the source's loop, before any later ConsToPrim can complain
+  if (mins[3] <= -2.0) return fail(s, APK_ERR_INVALID, "Kinetic injection leads to negative pressure");
   if (mins[2] < 0.0)
     return fail(s, APK_ERR_INVALID, "Got negative density. Consider enabling first-order flux correction or setting a reasonble density floor.");
   if (mins[3] < 0.0)
@@ -882,7 +886,7 @@ int apk_sim_create(const char *deck, const char *const *overrides, int noverride
   if (s->mesh.ndim == 3 && (rc = build_face_table(s)) != APK_OK) return bail(rc);
   if (s->fmft && (rc = turbulence_device_setup(s)) != APK_OK) return bail(rc);
   if (s->tracers && (rc = tracers_device_setup(s)) != APK_OK) return bail(rc);
-  if (s->pkg.gravity_srcterm && (rc = cluster_device_setup(s)) != APK_OK) return bail(rc);
+  if (cluster_needs_block_origins(s) && (rc = cluster_device_setup(s)) != APK_OK) return bail(rc);
   return APK_OK;
 }
 
@@ -924,6 +928,7 @@ void apk_sim_destroy(apk_sim *s) {
     dev_free(s, s->d_acc);
     dev_free(s, s->d_phases);
     dev_free(s, s->d_block_xmin);
+    dev_free(s, s->d_tower_contribs);
     dev_free(s, s->d_cons2[0]);
     dev_free(s, s->d_prim2[0]);
     dev_free(s, s->d_prim2[1]);
@@ -1065,6 +1070,12 @@ int apk_sim_step(apk_sim *s) {
   // 581-583), both sized with the diffusive limit estimated at the end of the previous cycle
   const bool sts = s->pkg.diffusion_sts();
   if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
+  // the magnetic tower's power scaling: its two sums once per cycle, before stage 1 (hydro_driver.cpp:409-449)
+  if (s->agn_opt.tower_power_scaling) {
+    double contribs[2];
+    SIM_TRY(s, cluster_tower_contribs(s, s->time, contribs));
+    s->tower_linear_contrib = contribs[0], s->tower_quadratic_contrib = contribs[1];
+  }
   for (int stage = 1; stage <= s->nstages; ++stage) SIM_TRY(s, do_stage(s, stage));
   if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
   // the tracer step: after the last stage (and the turbulence kick inside it), with the cycle's dt

@@ -13,6 +13,7 @@
 #include "../../../include/apk_host.h"
 #include "../cooling_table.hpp"
 #include "amr.hpp"
+#include "feedback.hpp"
 #include "mesh.hpp"
 #include "params.hpp"
 #include "turbulence.hpp"
@@ -29,6 +30,7 @@ struct UnitsState {
   double k_boltzmann() const, mh() const, atomic_mass_unit() const, erg() const, cm() const, s() const;
   // (what the cluster problem converts its defaults with, host/cluster.cpp)
   double gravitational_constant() const, msun() const, kpc() const, mpc() const, km_s() const, kev() const, g() const;
+  double speed_of_light() const;
 };
 
 // "Hydro" StateDescriptor params (names as in hydro.cpp)
@@ -85,7 +87,10 @@ struct HydroPackage {
   // the unsplit sources that run through the flux-array stage path (no fused stage forms with them)
   // problem/cluster/gravity/gravity_srcterm: the static field acts as the problem's unsplit source (host/cluster.cpp)
   bool gravity_srcterm = false;
-  bool flux_path_sources() const { return diffusion_configured() || cooling || gravity_srcterm; }
+  // problem/cluster/agn_feedback/fixed_power != 0 (and not disabled) or problem/cluster/magnetic_tower/fixed_field_rate
+  // != 0: the feedback sources follow gravity in ProblemSourceUnsplit (cluster.cpp:63-84; host/cluster.cpp)
+  bool feedback_srcterm = false;
+  bool flux_path_sources() const { return diffusion_configured() || cooling || gravity_srcterm || feedback_srcterm; }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -172,7 +177,14 @@ struct apk_sim {
   apk::CpawState cpaw;
   apk::FieldLoopState floop;
   apk_cluster_options cluster{};     // problem_id = cluster as parsed (host/cluster.cpp)
-  double *d_block_xmin = nullptr;    // [nblocks + 1][3]: what apk_gravity_src takes (allocated with gravity_srcterm)
+  double *d_block_xmin = nullptr;    // [nblocks + 1][3]: what apk_gravity_src and the feedback sources take
+  // AGN feedback and the magnetic tower of the cluster problem as parsed and derived (host/cluster.cpp,
+  // host/feedback_model.cpp); the tower's power contributions of the cycle in flight (hydro_driver.cpp:409-449)
+  apk_agn_feedback_options agn_opt{};
+  apk::AgnFeedbackModel agn;
+  apk_magnetic_tower_cfg tower{};
+  double tower_linear_contrib = 0.0, tower_quadratic_contrib = 0.0;
+  double *d_tower_contribs = nullptr;  // [nblocks][2] (allocated on first use)
   bool host_only = false;
   bool fused = true;
   int rank = 0, nranks = 1;

@@ -53,7 +53,10 @@ void cooling_initialize(apk_sim *s);    // <cooling> (host/cooling.cpp), called 
 void mesh_initialize(apk_sim *s);
 void cluster_initialize(apk_sim *s);    // problem_id = cluster (host/cluster.cpp), called at creation after the mesh is known
 void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u);  // its generator, called by pgen_block
-int cluster_device_setup(apk_sim *s);   // the per-block origins of the gravity source
+int cluster_device_setup(apk_sim *s);   // the per-block origins of the gravity and feedback sources
+bool cluster_needs_block_origins(const apk_sim *s);
+int cluster_tower_contribs(apk_sim *s, double time, double out[2]);  // the tower's power contributions, all ranks
+int cluster_feedback_sources(apk_sim *s, double beta_dt);  // AGN feedback, tower power, tower fixed rate: one stage
 int cluster_write_test_profile(apk_sim *s, const std::string &path);  // test_he_sphere.dat
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);
 void dev_free(apk_sim *s, double *p);

@@ -806,6 +806,8 @@ static int run_flux_array_stage(apk_sim *s, const Stage &st) {
   // density and velocity of the stage's input -- the primitives this pack still holds
   if (pkg.gravity_srcterm)
     SIM_TRY(s, apk_gravity_src(s->ctx, s->mu0(), &s->cluster.gravity, s->d_block_xmin, st.beta_dt, s->stream));
+  // ... then AGN feedback with the tower's power-scaled field, then the tower's fixed field rate (cluster.cpp:76-80)
+  if (pkg.feedback_srcterm) SIM_TRY(s, cluster_feedback_sources(s, st.beta_dt));
   return APK_OK;
 }
 

@@ -16,12 +16,8 @@
 // 64^3 block (0.029 ns per cell), 0.308 ms on 8 x 128^3 (0.018 ns per cell, 5.2 TB/s of the 96 B: 83 % of the 6.29 TB/s
 // stream rate of DESIGN.md section 7.0).  Not measured: GLM-MHD packs (same bytes, a longer variable stride).
 //
-// Cell centres.  The centre must be the number the problem generator used on the host, xc() of host/sim_pgen.cpp:
-//   x_d = xmin_d + ((g_d + i_d) + 1/2) dx_d
-// with g_d the global index of the block's first interior cell and xmin_d the mesh's lower corner.  The kernel takes the
-// blocks' lower interior corners (and, in one more row, the mesh's) and rebuilds g_d = rint((corner_d - xmin_d) / dx_d),
-// exact for any mesh whose index fits a double's mantissa; product and sum are spelled __dmul_rn / __dadd_rn so that the
-// product build does not contract them into an FMA, which would be another number than the host's.
+// Cell centres.  The centre is the number the problem generator used on the host, xc() of host/sim_pgen.cpp, rebuilt
+// from the blocks' lower interior corners: cell_of / centre of cell_centre.hpp, shared with kernels_feedback.hip.
 //
 // Build forms.  The parity build (APK_FP_STRICT, -ffp-contract=off) keeps the reference's association order with IEEE
 // divides and roots: it agrees with a numpy restatement operation for operation, except for log, the one step that is
@@ -32,6 +28,7 @@
 #include <cstdint>
 
 #include "apk_internal.hpp"
+#include "cell_centre.hpp"
 #include "hydro_math.hpp"
 
 namespace apk {
@@ -47,27 +44,6 @@ APK_DEV double g_from_r(const apk_cluster_gravity &c, double r_in) {
   if (c.which_bcg == APK_BCG_HERNQUIST) g_r += c.g_const_bcg / ((1 + r / c.r_bcg_s) * (1 + r / c.r_bcg_s));
   if (c.include_smbh) g_r += c.g_const_smbh / r2;
   return g_r;
-}
-
-// (b, i, j, k) of interior cell `idx` of the pack, indices counted from the first interior cell, and its offset in the
-// block's arrays; false past the last one
-APK_DEV bool cell_of(const PackView &pv, int64_t idx, int &b, int &i, int &j, int &k, int64_t &off) {
-  const int64_t nrow = pv.nx1, nplane = nrow * pv.nx2, nblk = nplane * pv.nx3;
-  if (idx >= nblk * pv.nblocks) return false;
-  b = (int)(idx / nblk);
-  int64_t r = idx - (int64_t)b * nblk;
-  k = (int)(r / nplane);
-  r -= (int64_t)k * nplane;
-  j = (int)(r / nrow);
-  i = (int)(r - (int64_t)j * nrow);
-  off = (pv.ks + k) * pv.sk + (pv.js + j) * pv.sj + (pv.is + i);
-  return true;
-}
-
-// xc() of host/sim_pgen.cpp from the block's corner, the mesh's corner and the cell width (see the header comment)
-APK_DEV double centre(double corner, double xmin, double dx, int i) {
-  const double g = rint((corner - xmin) / dx);
-  return __dadd_rn(xmin, __dmul_rn((g + (double)i) + 0.5, dx));
 }
 
 // GravitationalFieldSrcTerm (gravitational_field.hpp:40-63), one interior cell per lane

@@ -137,6 +137,34 @@ class _ClusterHost:
                                                               p.ctypes.data_as(L.c_dp), size.value, C.byref(size)))
         return r, p
 
+    def agn_feedback_options(self):
+        """lib.AgnFeedbackOptions: <problem/cluster/agn_feedback>, <problem/cluster/magnetic_tower> and
+        <problem/cluster/precessing_jet> as parsed, the normalised fractions and the derived jet velocity, temperature,
+        e_jet and eceil (valid when `configured`)"""
+        o = L.AgnFeedbackOptions()
+        self._cluster_check(self.lib.apk_sim_agn_feedback_options(self.h, C.byref(o)))
+        return o
+
+    def agn_feedback_stage_numbers(self, beta_dt, time=0.0):
+        """(lib.AgnFeedbackCfg, lib.JetCoords): what a stage with this beta_dt at this cycle time passes to the kernels"""
+        cfg, jet = L.AgnFeedbackCfg(), L.JetCoords()
+        rc = self.lib.apk_sim_agn_feedback_stage_numbers(self.h, float(beta_dt), float(time), C.byref(cfg), C.byref(jet))
+        if rc != L.APK_OK:
+            raise L.ApkError(rc, "no AGN feedback configured in this sim")
+        return cfg, jet
+
+    def magnetic_tower_cfg(self):
+        """lib.MagneticTowerCfg of the parsed <problem/cluster/magnetic_tower> block"""
+        o = self.agn_feedback_options()
+        return L.MagneticTowerCfg(o.tower_potential, o.li_alpha, o.l_scale, o.donut_offset, o.donut_thickness, o.l_mass_scale)
+
+    def magnetic_tower_field_to_add(self, lin, quad, beta_dt, power):
+        """MagneticTower::PowerSrcTerm's field_to_add; raises with the reference's message where it fails"""
+        out = C.c_double(0.0)
+        self._cluster_check(self.lib.apk_sim_magnetic_tower_field_to_add(self.h, float(lin), float(quad), float(beta_dt),
+                                                                         float(power), C.byref(out)))
+        return out.value
+
     def pgen_block(self, lb):
         """the problem generator's conserved state of local block lb, interior cells: [nvar][nx3][nx2][nx1] of the block"""
         nf = self.info
@@ -664,6 +692,24 @@ class Simulation(_FmftHost, _ClusterHost, _MeshView):
         """lib.SpitzerCfg (the converted coefficient, mbar, k_boltzmann; code units) as the deck was parsed, or None
         unless diffusion/conduction_coeff = spitzer"""
         return _spitzer_options(self.lib, self.h)
+
+    def agn_feedback_src(self, beta_dt, time=None):
+        """the thermal and kinetic channels of AGN feedback (apk_agn_feedback_src) once on the current state, jet frame at
+        `time` (default: the sim's time): conserved state and stored primitives of the interior cells change"""
+        self._check(self.lib.apk_sim_agn_feedback_src(self.h, float(beta_dt), float(self.time if time is None else time)))
+
+    def magnetic_tower_src(self, field, mass, time=None):
+        """the magnetic tower's source (apk_magnetic_tower_src) once on the current state with (field_to_add,
+        mass_to_add): conserved B, E and rho of the interior cells change"""
+        self._check(self.lib.apk_sim_magnetic_tower_src(self.h, float(field), float(mass),
+                                                        float(self.time if time is None else time)))
+
+    def magnetic_tower_contribs(self, time=None):
+        """(sum(prim_B . b1 dV), sum(0.5 b1^2 dV)) over the whole mesh, b1 the tower's field at unit strength: what the
+        power scaling takes.  A collective."""
+        out = (C.c_double * 2)()
+        self._check(self.lib.apk_sim_magnetic_tower_contribs(self.h, float(self.time if time is None else time), out))
+        return out[0], out[1]
 
     def gravity_src(self, beta_dt):
         """the cluster problem's gravity source (apk_gravity_src) once on the current state: conserved momentum and

@@ -576,6 +576,43 @@ def GravitationalFieldSrcTerm(md, gravity, block_xmin, beta_dt):
     torch.cuda.current_stream().synchronize()  # (t is released on return)
 
 
+def _block_xmin_tensor(md, block_xmin):
+    bx = np.ascontiguousarray(block_xmin, dtype=np.float64)
+    assert bx.shape == (md.nblocks + 1, 3)
+    return torch.from_numpy(bx).to(torch.device("cuda"))
+
+
+def AgnFeedbackSrcTerm(md, fluid, eos, cfg, jet, block_xmin):
+    """the loop of AGNFeedback::FeedbackSrcTerm -- agn_feedback.cpp:314-409 on md.cons and md.prim (both written).
+    cfg: lib.AgnFeedbackCfg for the stage's beta_dt, jet: lib.JetCoords; block_xmin as for GravitationalFieldSrcTerm"""
+    ctx = md.ctx
+    t = _block_xmin_tensor(md, block_xmin)
+    _check(ctx.lib.apk_agn_feedback_src(ctx.h, md.h, L.FLUID[fluid], C.byref(eos), C.byref(cfg), C.byref(jet), t.data_ptr(),
+                                        _stream()), ctx.lib, ctx.h)
+    torch.cuda.current_stream().synchronize()  # (t is released on return)
+
+
+def MagneticTowerSrcTerm(md, tower, jet, block_xmin, field_to_add, mass_to_add):
+    """MagneticTower::AddSrcTerm(field_to_add, mass_to_add, md, tm) -- magnetic_tower.cpp:29-140 on md.cons with
+    md.prim's field; GLM-MHD packs"""
+    ctx = md.ctx
+    t = _block_xmin_tensor(md, block_xmin)
+    _check(ctx.lib.apk_magnetic_tower_src(ctx.h, md.h, C.byref(tower), C.byref(jet), t.data_ptr(), float(field_to_add),
+                                          float(mass_to_add), _stream()), ctx.lib, ctx.h)
+    torch.cuda.current_stream().synchronize()
+
+
+def MagneticTowerPowerContribs(md, tower, jet, block_xmin):
+    """MagneticTower::ReducePowerContribs per block -- magnetic_tower.cpp:146-202: [nblocks][2] =
+    sum(prim_B . b1 dV), sum(0.5 b1^2 dV), b1 the tower's field at unit strength"""
+    ctx = md.ctx
+    t = _block_xmin_tensor(md, block_xmin)
+    out = torch.zeros((md.nblocks, 2), dtype=torch.float64, device=torch.device("cuda"))
+    _check(ctx.lib.apk_magnetic_tower_power_contribs(ctx.h, md.h, C.byref(tower), C.byref(jet), t.data_ptr(),
+                                                     out.data_ptr(), _stream()), ctx.lib, ctx.h)
+    return out.cpu().numpy()
+
+
 def FirstOrderFluxCorrect(u0, u1, fluid, eos, c_h, gam0, gam1, beta_dt):
     """Hydro::FirstOrderFluxCorrect<fluid>(u0,u1,gam0,gam1,beta_dt) -- hydro.cpp:1223"""
     ctx = u0.ctx

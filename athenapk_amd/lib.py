@@ -25,9 +25,11 @@ DIFF_COEFF = {"none": 0, "fixed": 1, "spitzer": 2}
 COOL_INTEGRATOR = {"rk12": 1, "rk45": 2, "townsend": 3}
 APK_FLAG_COOL_MAX_ITER = 4
 APK_FLAG_COOL_TABLE = 8
+APK_FLAG_AGN_NEG_PRESSURE = 16
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
-                "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort", "gravity")
+                "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort", "gravity",
+                "agn_feedback", "tower", "tower_contribs")
 
 APK_OK = 0
 APK_RCCL_ID_BYTES = 128
@@ -122,6 +124,43 @@ class ClusterOptions(C.Structure):
                                            "uniform_b_field_by", "uniform_b_field_bz", "mh", "k_boltzmann", "mu", "mu_e",
                                            "gravitational_constant", "msun", "kpc", "mpc", "km_s", "kev")] +
                 [("gravity", ClusterGravity)])
+
+
+# potential_type of the magnetic tower (apk_tower_potential; cluster::MagneticTowerPotential)
+TOWER_POTENTIAL = {"undefined": 0, "li": 1, "donut": 2}
+
+
+class JetCoords(C.Structure):
+    """apk_jet_coords: cos and sin of the jet axis' angle off z and around z (jet_coords.hpp:25-37)"""
+    _fields_ = [(n, C.c_double) for n in ("cos_theta", "sin_theta", "cos_phi", "sin_phi")]
+
+
+class AgnFeedbackCfg(C.Structure):
+    """apk_agn_feedback_cfg: what AGNFeedback::FeedbackSrcTerm computes for one stage (agn_feedback.cpp:263-303)"""
+    _fields_ = [(n, C.c_double) for n in ("thermal_feedback", "thermal_density", "thermal_radius", "jet_density",
+                                          "jet_momentum", "jet_feedback", "kinetic_jet_radius", "kinetic_jet_thickness",
+                                          "kinetic_jet_offset", "vceil", "eceil")]
+
+
+class MagneticTowerCfg(C.Structure):
+    """apk_magnetic_tower_cfg: MagneticTowerObj's members (magnetic_tower.hpp:45-58)"""
+    _fields_ = [("potential", C.c_int)] + [(n, C.c_double) for n in ("li_alpha", "l_scale", "donut_offset",
+                                                                    "donut_thickness", "l_mass_scale")]
+
+
+class AgnFeedbackOptions(C.Structure):
+    """apk_agn_feedback_options: <problem/cluster/agn_feedback>, .../magnetic_tower and .../precessing_jet as parsed, and
+    the derived jet numbers (include/apk_host.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("configured", "active", "disabled", "enable_magnetic_tower_mass_injection",
+                                        "assumed_cold_jet", "tower_potential", "tower_power_scaling")] +
+                [(n, C.c_double) for n in ("fixed_power", "efficiency", "thermal_fraction", "kinetic_fraction",
+                                           "magnetic_fraction", "thermal_mass_fraction", "kinetic_mass_fraction",
+                                           "magnetic_mass_fraction", "thermal_radius", "kinetic_jet_radius",
+                                           "kinetic_jet_thickness", "kinetic_jet_offset", "kinetic_jet_velocity",
+                                           "kinetic_jet_temperature", "kinetic_jet_e", "vceil", "Tceil", "eceil",
+                                           "jet_theta", "jet_phi_dot", "jet_phi0", "li_alpha", "l_scale", "donut_offset",
+                                           "donut_thickness", "initial_field", "fixed_field_rate", "fixed_mass_rate",
+                                           "l_mass_scale", "speed_of_light", "mbar_gm1_over_kb", "power", "mass_rate")])
 
 
 class UnitsInfo(C.Structure):
@@ -329,6 +368,9 @@ def _signatures():
         "apk_estimate_cooling_timestep": (i, [vp, vp, vp, c_dp, vp]),
         "apk_gravity_src": (i, [vp, vp, C.POINTER(ClusterGravity), vp, d, vp]),
         "apk_gravity_g_from_r": (i, [vp, C.POINTER(ClusterGravity), vp, vp, C.c_int64, vp]),
+        "apk_agn_feedback_src": (i, [vp, vp, i, C.POINTER(Eos), C.POINTER(AgnFeedbackCfg), C.POINTER(JetCoords), vp, vp]),
+        "apk_magnetic_tower_src": (i, [vp, vp, C.POINTER(MagneticTowerCfg), C.POINTER(JetCoords), vp, d, d, vp]),
+        "apk_magnetic_tower_power_contribs": (i, [vp, vp, C.POINTER(MagneticTowerCfg), C.POINTER(JetCoords), vp, vp, vp]),
         "apk_first_order_flux_correct": (i, [vp, vp, vp, i, E, d, d, d, d, C.POINTER(ll), vp]),
         "apk_count_unphysical": (i, [vp, vp, i, C.POINTER(ll), vp]),
         "apk_history": (i, [vp, vp, i, c_dp, vp]),
@@ -416,6 +458,12 @@ def _signatures():
         "apk_sim_block_he_profile": (i, [vp, i, c_dp, c_dp, i, C.POINTER(C.c_int)]),
         "apk_sim_pgen_block": (i, [vp, i, c_dp]),
         "apk_sim_gravity_src": (i, [vp, d]),
+        "apk_sim_agn_feedback_options": (i, [vp, C.POINTER(AgnFeedbackOptions)]),
+        "apk_sim_agn_feedback_stage_numbers": (i, [vp, d, d, C.POINTER(AgnFeedbackCfg), C.POINTER(JetCoords)]),
+        "apk_sim_magnetic_tower_field_to_add": (i, [vp, d, d, d, d, c_dp]),
+        "apk_sim_agn_feedback_src": (i, [vp, d, d]),
+        "apk_sim_magnetic_tower_src": (i, [vp, d, d, d]),
+        "apk_sim_magnetic_tower_contribs": (i, [vp, d, c_dp]),
         "apk_sim_tracers_options": (i, [vp, C.POINTER(TracersOptions)]),
         "apk_sim_tracers_count": (i, [vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ll)]),
         "apk_sim_tracers_stats": (i, [vp, C.POINTER(ll), C.POINTER(ll)]),

@@ -57,6 +57,8 @@ enum apk_status {
 /* tabular cooling: the reference's device failures (PARTHENON_FAIL / REQUIRE), latched instead of trapping */
 #define APK_FLAG_COOL_MAX_ITER 4u /* "Sub cycles exceed max_iter", tabular_cooling.cpp:375-380 */
 #define APK_FLAG_COOL_TABLE 8u    /* "Failed to find log_temp", tabular_cooling.hpp:155-156 */
+/* AGN feedback: "Kinetic injection leads to negative pressure" (agn_feedback.cpp:407-408), latched instead of trapping */
+#define APK_FLAG_AGN_NEG_PRESSURE 16u
 
 typedef void *apk_stream_t; /* hipStream_t */
 
@@ -932,6 +934,53 @@ int apk_gravity_src(apk_ctx *ctx, const apk_pack *md, const apk_cluster_gravity 
 int apk_gravity_g_from_r(apk_ctx *ctx, const apk_cluster_gravity *gravity, const double *r, double *g, int64_t n,
                          apk_stream_t stream);
 
+/* ---- AGN feedback and the magnetic tower of the cluster problem (src/pgen/cluster/agn_feedback.{hpp,cpp},
+ * magnetic_tower.{hpp,cpp}, jet_coords.hpp, cluster_utils.hpp) --------------------------------------------------------
+ * The jet frame (JetCoords, jet_coords.hpp:25-37): cos and sin of the axis' angle off z and of its angle around z,
+ * phi0 + time * phi_dot, computed by the host (csrc/host/feedback_model.cpp) and passed by value. */
+typedef struct apk_jet_coords {
+  double cos_theta, sin_theta, cos_phi, sin_phi;
+} apk_jet_coords;
+/* The numbers AGNFeedback::FeedbackSrcTerm computes before its loop (agn_feedback.cpp:263-303), for one stage's beta_dt,
+ * in the reference's operation order (host: agn_feedback_stage_numbers).  vceil / eceil = +inf: no ceiling. */
+typedef struct apk_agn_feedback_cfg {
+  double thermal_feedback, thermal_density, thermal_radius;
+  double jet_density, jet_momentum, jet_feedback;
+  double kinetic_jet_radius, kinetic_jet_thickness, kinetic_jet_offset;
+  double vceil, eceil;
+} apk_agn_feedback_cfg;
+enum apk_tower_potential { APK_TOWER_UNDEFINED = 0, APK_TOWER_LI = 1, APK_TOWER_DONUT = 2 };
+/* MagneticTower's members that MagneticTowerObj takes (magnetic_tower.hpp:45-58, 167-176) */
+typedef struct apk_magnetic_tower_cfg {
+  int potential; /* apk_tower_potential, uniform over a launch */
+  double li_alpha, l_scale, donut_offset, donut_thickness, l_mass_scale;
+} apk_magnetic_tower_cfg;
+
+/* Replaces the loop of AGNFeedback::FeedbackSrcTerm (agn_feedback.cpp:314-409) on the interior cells of every block,
+ * operation for operation: the thermal sphere (r2 <= R^2; AddDensityToConsAtFixedVel, cluster_utils.hpp:22-34, on the
+ * stored primitives), the jet cylinders (r < radius, offset <= |h| <= offset + thickness; ConsToPrim before and after
+ * the deposit), the velocity and internal-energy ceilings on every cell while jet_density > 0 (outside the cylinders
+ * they see the stored primitives), and the closing ConsToPrim, which writes the stored primitives of every interior
+ * cell.  Where the reference aborts on the device ("Kinetic injection leads to negative pressure") the kernel latches
+ * APK_FLAG_AGN_NEG_PRESSURE in the flag word (apk_poll_device_flags) and goes on.  Squares are products (x * x) where
+ * the reference writes pow(x, 2).  block_xmin as for apk_gravity_src. */
+int apk_agn_feedback_src(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_agn_feedback_cfg *cfg,
+                         const apk_jet_coords *jet, const double *block_xmin, apk_stream_t stream);
+/* Replaces MagneticTower::AddSrcTerm (magnetic_tower.cpp:29-140), GLM-MHD only, in ONE kernel and without the
+ * reference's potential array: a cell evaluates PotentialInSimCart (magnetic_tower.hpp:60-102) at its six neighbours'
+ * centres -- the same centre function of the same index a stored array would have been filled with -- forms the
+ * central-difference curl in the reference's association (/ dx / 2.0), adds b to cons B, prim_B . b + 0.5 b^2 to E (the
+ * stored primitive field) and, with mass_to_add > 0, the Gaussian density (DensityFromSimCart) scaled by
+ * mass_to_add / (l_mass_scale^3 pi^(3/2)).  field_to_add = mass_to_add = 0 launches nothing. */
+int apk_magnetic_tower_src(apk_ctx *ctx, const apk_pack *md, const apk_magnetic_tower_cfg *tower, const apk_jet_coords *jet,
+                           const double *block_xmin, double field_to_add, double mass_to_add, apk_stream_t stream);
+/* Replaces MagneticTower::ReducePowerContribs (magnetic_tower.cpp:146-202): per block, sum(prim_B . b1 dV) and
+ * sum(0.5 b1^2 dV) over its interior cells, b1 = FieldInSimCart at unit field, into contribs[nblocks][2] (device).  A
+ * fixed reduction tree per block, no atomics: a block's pair is a function of the block alone, bit for bit. */
+int apk_magnetic_tower_power_contribs(apk_ctx *ctx, const apk_pack *md, const apk_magnetic_tower_cfg *tower,
+                                      const apk_jet_coords *jet, const double *block_xmin, double *contribs,
+                                      apk_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
  * they are launched on.  When enabled, every kernel launch of the listed groups is
@@ -953,7 +1002,10 @@ enum apk_timing_slot {
   APK_T_TRACERS = 12,     /* tracer particles: advect, re-own, fill (or the fused step), lookbacks */
   APK_T_TRACER_SORT = 13, /* ... and their counting sort (memset, histogram, scan, scatter) */
   APK_T_GRAVITY = 14,     /* the static gravity source (apk_gravity_src) */
-  APK_T_COUNT = 15
+  APK_T_AGN_FEEDBACK = 15,   /* apk_agn_feedback_src */
+  APK_T_TOWER = 16,          /* apk_magnetic_tower_src */
+  APK_T_TOWER_CONTRIBS = 17, /* apk_magnetic_tower_power_contribs */
+  APK_T_COUNT = 18
 };
 int apk_kernel_timing_enable(apk_ctx *ctx, int on);
 /* total_ms / launches may be NULL */

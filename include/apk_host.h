@@ -212,8 +212,8 @@ int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int
  * The slice built here: static gravity (NFW + Hernquist BCG + SMBH) as an unsplit source, the ACCEPT-like entropy
  * profile and the hydrostatic-equilibrium sphere, or uniform gas; a uniform field with GLM-MHD.  Keys and defaults are
  * the reference's (<problem/cluster>, .../gravity, .../entropy_profile, .../hydrostatic_equilibrium, .../uniform_gas,
- * .../uniform_b_field).  Refused at creation, each with a message naming the key: refined meshes, nx2 = 1 or nx3 = 1,
- * agn_feedback/fixed_power != 0, agn_triggering other than NONE, magnetic_tower, stellar_feedback, snia_feedback unless
+ * .../uniform_b_field; AGN feedback and the magnetic tower: below).  Refused at creation, each with a message naming the
+ * key: refined meshes, nx2 = 1 or nx3 = 1, agn_triggering other than NONE, stellar_feedback, snia_feedback unless
  * disabled = true, any clips key off its default, init_perturb/sigma_v or sigma_b != 0, dipole_b_field, reductions, the
  * sphere without <units> and hydro/He_mass_fraction, uniform_b_field without GLM-MHD, gravity_srcterm with
  * diffusion/integrator = rkl2.  All entries below work on a host-only sim. */
@@ -245,6 +245,55 @@ int apk_sim_pgen_block(apk_sim *sim, int lb, double *out);
 /* apk_gravity_src once on the current state with the given beta_dt (conserved state and stored primitives of the
  * current buffers).  For tests. */
 int apk_sim_gravity_src(apk_sim *sim, double beta_dt);
+
+/* ---- fixed-power AGN feedback and the magnetic tower of the cluster problem (src/pgen/cluster/agn_feedback.cpp,
+ * magnetic_tower.{hpp,cpp}, jet_coords.hpp; csrc/host/feedback_model.cpp, csrc/host/cluster.cpp) ---------------------
+ * Keys and defaults are the reference's: <problem/cluster/precessing_jet> jet_theta, jet_phi_dot, jet_phi0;
+ * <problem/cluster/agn_feedback> fixed_power, efficiency, thermal_fraction, kinetic_fraction, magnetic_fraction,
+ * enable_magnetic_tower_mass_injection, thermal_radius, kinetic_jet_radius, kinetic_jet_thickness, kinetic_jet_offset,
+ * kinetic_jet_velocity and / or kinetic_jet_temperature, vceil, Tceil, disabled; <problem/cluster/magnetic_tower>
+ * potential_type = donut | li, li_alpha, l_scale, donut_offset, donut_thickness, initial_field, fixed_field_rate,
+ * fixed_mass_rate, l_mass_scale.  A violated requirement of the reference is a deck error with its wording.  Refused at
+ * creation, naming the key: fixed_power != 0 without <units> and hydro/He_mass_fraction, or with all three fractions zero
+ * (the reference fails that at the first stage); magnetic_fraction != 0 or a non-zero tower field or rate without
+ * hydro/fluid = glmmhd; a magnetic_tower block whose potential_type is neither donut nor li (stricter than the
+ * reference, which fails inside a kernel); enable_tracer = true; agn_triggering other than NONE (the accretion rate is
+ * zero: power = fixed_power).  No agn_feedback_power history column.  All entries but the three sources work on a
+ * host-only sim. */
+typedef struct apk_agn_feedback_options {
+  int configured; /* a <problem/cluster/agn_feedback> block was read and its derived numbers are valid */
+  int active;     /* fixed_power != 0 and not disabled: the source runs in every stage */
+  int disabled, enable_magnetic_tower_mass_injection, assumed_cold_jet;
+  int tower_potential; /* apk_tower_potential */
+  int tower_power_scaling; /* magnetic_fraction != 0 && fixed_power != 0: the contributions are reduced every cycle */
+  double fixed_power, efficiency;
+  double thermal_fraction, kinetic_fraction, magnetic_fraction; /* normalised to sum 1 */
+  double thermal_mass_fraction, kinetic_mass_fraction, magnetic_mass_fraction;
+  double thermal_radius, kinetic_jet_radius, kinetic_jet_thickness, kinetic_jet_offset;
+  double kinetic_jet_velocity, kinetic_jet_temperature, kinetic_jet_e; /* as given or derived */
+  double vceil, Tceil, eceil;
+  double jet_theta, jet_phi_dot, jet_phi0;
+  double li_alpha, l_scale, donut_offset, donut_thickness, initial_field, fixed_field_rate, fixed_mass_rate, l_mass_scale;
+  double speed_of_light, mbar_gm1_over_kb; /* what the derivations take from Units and the composition */
+  double power, mass_rate;                 /* GetFeedbackPower / GetFeedbackMassRate with zero accretion */
+} apk_agn_feedback_options;
+int apk_sim_agn_feedback_options(const apk_sim *sim, apk_agn_feedback_options *opt);
+/* the numbers of agn_feedback.cpp:263-303 for beta_dt, and the jet frame at `time` (what the kernels are passed) */
+int apk_sim_agn_feedback_stage_numbers(const apk_sim *sim, double beta_dt, double time, apk_agn_feedback_cfg *cfg,
+                                       apk_jet_coords *jet);
+/* MagneticTower::PowerSrcTerm's field_to_add = (-lin + sqrt(lin^2 + 4 quad beta_dt P)) / (2 quad); fails with the
+ * reference's two messages (both contributions zero; negative discriminant or quad = 0) */
+int apk_sim_magnetic_tower_field_to_add(apk_sim *sim, double lin, double quad, double beta_dt, double power, double *field);
+/* apk_agn_feedback_src once on the current state (thermal and kinetic channels; conserved state and stored primitives of
+ * the current buffers), jet frame at `time`.  For tests. */
+int apk_sim_agn_feedback_src(apk_sim *sim, double beta_dt, double time);
+/* apk_magnetic_tower_src once on the current state with (field_to_add, mass_to_add), jet frame at `time`.  For tests. */
+int apk_sim_magnetic_tower_src(apk_sim *sim, double field, double mass, double time);
+/* apk_magnetic_tower_power_contribs on the current state, jet frame at `time`: out[0] = sum(prim_B . b1 dV), out[1] =
+ * sum(0.5 b1^2 dV) over the whole mesh.  Each local block's pair goes into its slot of a zeroed array of 2 *
+ * nblocks_global, allreduce_sum adds the arrays, and the host adds the slots in global block order: the result does not
+ * depend on how the blocks are distributed over ranks (the reference sums per-rank partial sums).  A collective. */
+int apk_sim_magnetic_tower_contribs(apk_sim *sim, double time, double out[2]);
 
 /* ---- tracer particles (<tracers>, src/tracers/tracers.cpp; csrc/host/tracers.cpp) ---------------------------------
  * Keys (tracers.cpp:43-93, 102-118): enabled (default false), initial_seed_method = none | random_per_block | user,
