@@ -1,7 +1,7 @@
 // cluster.cpp -- problem_id = cluster in the standalone host driver: the options of ProblemInitPackageData
 // (src/pgen/cluster.cpp:114-250) for the slice built here, what is refused of the rest, the problem generator
 // (cluster.cpp:469-653), the per-block origins of the gravity and feedback sources, the feedback sources of a stage
-// (cluster.cpp:76-80) and the C entries of include/apk_host.h.  The model itself is host/cluster_model.cpp (ClusterGravity,
+// (cluster.cpp:76-80), AGN triggering's options, active list and cycle (agn_triggering.cpp, hydro_driver.cpp:360-394) and the C entries of include/apk_host.h.  The model itself is host/cluster_model.cpp (ClusterGravity,
 // ACCEPTEntropyProfile, HydrostaticEquilibriumSphere) and host/feedback_model.cpp (the jet frame, AGNFeedback's derived
 // numbers, the magnetic tower's scaling and initial field).
 #include <cerrno>
@@ -46,6 +46,7 @@ const char *kHse = "problem/cluster/hydrostatic_equilibrium";
 const char *kAgn = "problem/cluster/agn_feedback";
 const char *kTower = "problem/cluster/magnetic_tower";
 const char *kJet = "problem/cluster/precessing_jet";
+const char *kTrig = "problem/cluster/agn_triggering";
 
 [[noreturn]] void refuse(const std::string &key, const std::string &why) {
   throw std::runtime_error("problem_id = cluster: " + key + " " + why);
@@ -61,9 +62,6 @@ void refuse_unbuilt(apk_sim *s) {
   if (s->mesh.nx[1] == 1) refuse("parthenon/mesh/nx2", "= 1: the cluster problem is three-dimensional");
   if (pin.GetOrAddBoolean(kAgn, "enable_tracer", false))
     refuse("problem/cluster/agn_feedback/enable_tracer", "must be false: the AGN passive-scalar tag is not implemented");
-  if (pin.DoesBlockExist("problem/cluster/agn_triggering") &&
-      pin.GetOrAddString("problem/cluster/agn_triggering", "triggering_mode", "NONE") != "NONE")
-    refuse("problem/cluster/agn_triggering/triggering_mode", "must be NONE: AGN triggering is not implemented");
   if (pin.DoesBlockExist("problem/cluster/stellar_feedback"))
     refuse("problem/cluster/stellar_feedback", "is not implemented: remove the block");
   // (the reference's default is ENABLED: the deck has to say that it runs without)
@@ -110,6 +108,72 @@ HeProfile block_profile(apk_sim *s, int lb) {
 }
 
 bool sphere_available(const apk_sim *s) { return s->cluster.enabled && s->pkg.units.has_composition; }
+
+// AGNTriggering as the reference's constructor reads it (agn_triggering.cpp:53-119), what this path refuses of it, and
+// the active list of this rank's blocks (include/apk_amd.h: apk_trig_box)
+void triggering_active_list(apk_sim *s) {
+  const Mesh &m = s->mesh;
+  s->trig_boxes.clear();
+  s->trig_box_cells = s->trig_max_box_cells = 0;
+  const int next[3] = {m.ni, m.nj, m.nk};
+  for (int lb = 0; lb < (int)m.local_gids.size(); ++lb) {
+    double x0[3];
+    block_origin(s, lb, x0);
+    apk_trig_box box{};
+    box.block = lb;
+    long long cells = 1;
+    for (int d = 0; d < 3; ++d) {
+      std::vector<double> x((size_t)next[d]);
+      for (int i = 0; i < next[d]; ++i) x[(size_t)i] = xc(s, x0, d, i);
+      triggering_index_range(x.data(), next[d], s->trig.accretion_radius, &box.lo[d], &box.hi[d]);
+      cells *= std::max(box.hi[d] - box.lo[d], 0);
+    }
+    if (cells == 0) continue;
+    s->trig_boxes.push_back(box);
+    s->trig_box_cells += cells;
+    s->trig_max_box_cells = std::max(s->trig_max_box_cells, cells);
+  }
+}
+
+void triggering_initialize(apk_sim *s) {
+  ParameterInput &pin = s->pin;
+  const UnitsState &u = s->pkg.units;
+  AgnTriggeringModel &t = s->trig;
+  t = AgnTriggeringModel{};
+  s->trig_q = AgnTriggeringModel::Reduced{};
+  s->trig_rate = s->trig_time = s->trig_dt = 0.0;
+  const std::string mode_key = std::string(kTrig) + "/triggering_mode";
+  t.mode = parse_agn_triggering_mode(pin.GetOrAddString(kTrig, "triggering_mode", "NONE"));
+  t.accretion_radius = pin.GetOrAddReal(kTrig, "accretion_radius", 0);
+  t.cold_temp_thresh = pin.GetOrAddReal(kTrig, "cold_temp_thresh", 0);
+  t.cold_t_acc = pin.GetOrAddReal(kTrig, "cold_t_acc", 0);
+  t.bondi_alpha = pin.GetOrAddReal(kTrig, "bondi_alpha", 0);
+  t.bondi_M_smbh = pin.GetOrAddReal(kGrav, "m_smbh", 0);
+  t.bondi_n0 = pin.GetOrAddReal(kTrig, "bondi_n0", 0);
+  t.bondi_beta = pin.GetOrAddReal(kTrig, "bondi_beta", 0);
+  t.accretion_cfl = pin.GetOrAddReal(kTrig, "accretion_cfl", 1e-1);
+  t.remove_accreted_mass = pin.GetOrAddBoolean(kTrig, "removed_accreted_mass", true);
+  s->trig_write_to_file = pin.GetOrAddBoolean(kTrig, "write_to_file", false);
+  s->trig_filename = pin.GetOrAddString(kTrig, "triggering_filename", "agn_triggering.dat");
+  t.gravitational_constant = u.gravitational_constant();
+  if (u.has_composition) {
+    t.mean_molecular_mass = u.mu * u.atomic_mass_unit();
+    t.mean_molecular_mass_by_kb = t.mean_molecular_mass / u.k_boltzmann();
+  }
+  if (!(t.accretion_cfl > 0.0)) refuse(std::string(kTrig) + "/accretion_cfl", "must be positive");
+  s->pkg.agn_triggering = t.mode != APK_TRIG_NONE;
+  if (t.mode == APK_TRIG_NONE) return;
+  // (stricter than the reference, where an empty sphere gives 0 / 0 and a zero accretion time a zero time step and an
+  // infinite rate)
+  if (!(t.accretion_radius > 0.0)) refuse(mode_key, "other than NONE needs " + std::string(kTrig) + "/accretion_radius > 0");
+  if (t.mode == APK_TRIG_COLD_GAS && !(t.cold_t_acc > 0.0)) refuse(mode_key, "= COLD_GAS needs " + std::string(kTrig) + "/cold_t_acc > 0");
+  if (t.mode == APK_TRIG_BOOTH_SCHAYE && !(t.bondi_n0 > 0.0)) refuse(std::string(kTrig) + "/bondi_n0", "must be positive with triggering_mode = BOOTH_SCHAYE");
+  if (!u.has_composition)
+    refuse(mode_key, "other than NONE requires units and gas composition. Set a 'units' block and 'hydro/He_mass_fraction' in the "
+           "input file.");
+  if (s->pkg.diffint == APK_DIFFINT_RKL2) refuse(mode_key, "other than NONE is not supported with diffusion/integrator = rkl2");
+  triggering_active_list(s);
+}
 
 // AGNFeedback, MagneticTower and JetCoordsFactory as the reference's constructors read them (agn_feedback.cpp:34-185,
 // magnetic_tower.hpp:178-219, jet_coords.hpp:100-107), and what this path refuses of them
@@ -184,11 +248,16 @@ void feedback_initialize(apk_sim *s, bool agn_block, bool tower_block) {
   if (in.fixed_power != 0.0 && in.thermal_fraction == 0.0 && in.kinetic_fraction == 0.0 && in.magnetic_fraction == 0.0)
     refuse("problem/cluster/agn_feedback/fixed_power", "!= 0 with thermal_fraction, kinetic_fraction and magnetic_fraction all zero "
            "(AGNFeedback::FeedbackSrcTerm Magnetic, Thermal, and Kinetic fractions are all zero)");
+  const bool triggered = s->trig.mode != APK_TRIG_NONE;
+  if (triggered && !o.disabled && in.thermal_fraction == 0.0 && in.kinetic_fraction == 0.0 && in.magnetic_fraction == 0.0)
+    refuse("problem/cluster/agn_triggering/triggering_mode", "other than NONE with problem/cluster/agn_feedback/disabled = false and "
+           "thermal_fraction, kinetic_fraction and magnetic_fraction all zero (AGNFeedback::FeedbackSrcTerm Magnetic, Thermal, and "
+           "Kinetic fractions are all zero)");
   if (in.magnetic_fraction != 0.0 && !mhd) refuse("problem/cluster/agn_feedback/magnetic_fraction", "!= 0 needs hydro/fluid = glmmhd");
 
   // the derived jet numbers need the units: with them the constructor's requirements hold for every deck, as in the
   // reference; without them (no feedback possible, see above) the keys are kept as read
-  if (u.has_composition && agn_block) {
+  if (u.has_composition && (agn_block || triggered)) {
     in.speed_of_light = u.speed_of_light();
     in.mbar_gm1_over_kb = u.mbar_over_kb * (s->pkg.eos.gamma - 1.0);
     s->agn = agn_feedback_model(in);
@@ -203,7 +272,8 @@ void feedback_initialize(apk_sim *s, bool agn_block, bool tower_block) {
     o.speed_of_light = in.speed_of_light, o.mbar_gm1_over_kb = in.mbar_gm1_over_kb;
     o.power = m.power(), o.mass_rate = m.mass_rate();
   }
-  o.active = (o.configured && in.fixed_power != 0.0 && !o.disabled) ? 1 : 0;
+  o.active = (o.configured && (in.fixed_power != 0.0 || triggered) && !o.disabled) ? 1 : 0;
+  // (cluster.cpp:225-231: magnetic_fraction != 0 && (fixed_power != 0 || triggering_mode != NONE))
   o.tower_power_scaling = (o.active && o.magnetic_fraction != 0.0) ? 1 : 0;
   // whatever evaluates the tower needs its potential and its length scales (MagneticTowerObj's constructor)
   const bool tower_used = o.tower_power_scaling || o.initial_field != 0.0 || o.fixed_field_rate != 0.0;
@@ -211,7 +281,7 @@ void feedback_initialize(apk_sim *s, bool agn_block, bool tower_block) {
     refuse("problem/cluster/magnetic_tower/potential_type", "must be donut or li (Unknown magnetic tower potential.)");
   if (tower_used) tower_check_scales(t);
   if ((o.active || o.fixed_field_rate != 0.0) && s->pkg.diffint == APK_DIFFINT_RKL2)
-    refuse(o.active ? "problem/cluster/agn_feedback/fixed_power" : "problem/cluster/magnetic_tower/fixed_field_rate",
+    refuse((o.active && in.fixed_power != 0.0) ? "problem/cluster/agn_feedback/fixed_power" : "problem/cluster/magnetic_tower/fixed_field_rate",
            "!= 0 is not supported with diffusion/integrator = rkl2");
   s->pkg.feedback_srcterm = o.active || o.fixed_field_rate != 0.0;
 }
@@ -289,6 +359,7 @@ void cluster_initialize(apk_sim *s) {
   if (o.gravity_srcterm && gi.which_bcg_g == APK_BCG_HERNQUIST && !(gi.r_bcg_s > 0.0))
     refuse("problem/cluster/gravity/r_bcg_s", "must be positive");
   s->pkg.gravity_srcterm = o.gravity_srcterm != 0;
+  triggering_initialize(s);
   feedback_initialize(s, agn_block, tower_block);
 
   // ACCEPTEntropyProfile (entropy_profiles.hpp:25-34)
@@ -402,7 +473,8 @@ void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u) {
 }
 
 bool cluster_needs_block_origins(const apk_sim *s) {
-  return s->pkg.gravity_srcterm || (s->cluster.enabled && (s->agn_opt.configured || s->tower.potential != APK_TOWER_UNDEFINED));
+  return s->pkg.gravity_srcterm || s->pkg.agn_triggering ||
+         (s->cluster.enabled && (s->agn_opt.configured || s->tower.potential != APK_TOWER_UNDEFINED));
 }
 
 // MagneticTowerReducePowerContribs with its reduction over ranks (magnetic_tower.cpp:301-317, hydro_driver.cpp:409-449):
@@ -438,7 +510,7 @@ int cluster_feedback_sources(apk_sim *s, double beta_dt) {
   const apk_agn_feedback_options &o = s->agn_opt;
   const apk_jet_coords jet = jet_at(s, s->time);
   try {
-    if (o.active) {
+    if (o.active && s->agn.power() != 0) {  // (agn_feedback.cpp:241: "No AGN feedback, return")
       const apk_agn_feedback_cfg cfg = agn_feedback_stage_numbers(s->agn, beta_dt);
       SIM_TRY(s, apk_agn_feedback_src(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, &cfg, &jet, s->d_block_xmin, s->stream));
       const double magnetic_power = s->agn.power() * s->agn.magnetic_fraction;
@@ -461,6 +533,88 @@ int cluster_feedback_sources(apk_sim *s, double beta_dt) {
   return APK_OK;
 }
 
+// AGN triggering of one cycle (hydro_driver.cpp:360-394): AGNTriggeringResetTriggering, ReduceTriggering over this rank's
+// active list (COLD_GAS removes in the same launch), the sum over ranks -- every local block's sums into its slot of a
+// zeroed array over all blocks, one allreduce_sum, the slots added in global block order, as cluster_tower_contribs: the
+// result does not depend on the distribution of the blocks -- and what follows from the sums.
+static int triggering_reduce(apk_sim *s, double dt) {
+  const Mesh &m = s->mesh;
+  const int nlb = (int)m.local_gids.size();
+  const AgnTriggeringModel &t = s->trig;
+  SIM_TRY(s, sync_ghosts(s));  // (ghost cells of the boxes are read and written; materialises the stored primitives)
+  std::vector<double> local(4 * (size_t)nlb, 0.0), all(4 * (size_t)m.nblocks_total, 0.0);
+  if (!s->trig_boxes.empty()) {  // (a rank with no block in the list launches nothing)
+    apk_agn_triggering_cfg cfg{};
+    cfg.mode = t.mode, cfg.remove_accreted_mass = t.remove_accreted_mass ? 1 : 0;
+    cfg.accretion_radius = t.accretion_radius, cfg.cold_temp_thresh = t.cold_temp_thresh, cfg.cold_t_acc = t.cold_t_acc;
+    cfg.mean_molecular_mass_by_kb = t.mean_molecular_mass_by_kb;
+    SIM_TRY(s, apk_agn_triggering_reduce(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, &cfg, s->d_trig_boxes, (int)s->trig_boxes.size(),
+                                         s->trig_max_box_cells, s->d_block_xmin, dt, s->d_trig_sums, s->stream));
+    SIM_HIP(s, hipMemcpyAsync(local.data(), s->d_trig_sums, sizeof(double) * local.size(), hipMemcpyDeviceToHost, hs(s)));
+    SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  }
+  for (int lb = 0; lb < nlb; ++lb)
+    for (int q = 0; q < 4; ++q) all[4 * (size_t)m.local_gids[lb] + q] = local[4 * (size_t)lb + q];
+  if (s->have_comm && s->nranks > 1 && s->comm.allreduce_sum(s->comm.user, all.data(), (int)all.size()) != 0)
+    return fail(s, APK_ERR_DEVICE, "allreduce_sum failed");
+  double sum[4] = {0.0, 0.0, 0.0, 0.0};
+  for (size_t g = 0; g < (size_t)m.nblocks_total; ++g)
+    for (int q = 0; q < 4; ++q) sum[q] += all[4 * g + q];
+  AgnTriggeringModel::Reduced &r = s->trig_q;
+  r = AgnTriggeringModel::Reduced{};
+  if (t.mode == APK_TRIG_COLD_GAS) r.cold_mass = sum[0];
+  else r.total_mass = sum[0], r.mass_weighted_density = sum[1], r.mass_weighted_velocity = sum[2], r.mass_weighted_cs = sum[3];
+  s->trig_time = s->time, s->trig_dt = dt;
+  if (t.mode != APK_TRIG_COLD_GAS && r.total_mass == 0) {
+    s->trig_rate = s->agn.accretion_rate = 0.0;
+    return fail(s, APK_ERR_INVALID, "AGN triggering: no gas inside problem/cluster/agn_triggering/accretion_radius (the reduced total_mass "
+                                    "is zero): the Bondi accretion rate is undefined");
+  }
+  s->trig_rate = t.accretion_rate(r);
+  s->agn.accretion_rate = s->trig_rate;
+  if (s->agn_opt.configured) s->agn_opt.power = s->agn.power(), s->agn_opt.mass_rate = s->agn.mass_rate();
+  return APK_OK;
+}
+
+static int triggering_remove_bondi(apk_sim *s, double dt) {
+  if (s->trig_boxes.empty()) return APK_OK;
+  return apk_agn_triggering_remove_bondi(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, s->trig.accretion_radius, s->d_trig_boxes,
+                                         (int)s->trig_boxes.size(), s->trig_max_box_cells, s->d_block_xmin, s->trig_q.total_mass,
+                                         s->trig_rate, dt, s->stream);
+}
+
+// AGNTriggeringFinalizeTriggering's row (agn_triggering.cpp:491-524), every number with %.17g (the reference prints six
+// digits): time dt accretion_rate, then cold_mass or total_mass avg_density avg_velocity avg_cs
+static int triggering_write_row(apk_sim *s) {
+  if (s->trig_path.empty() || s->rank != 0) return APK_OK;
+  FILE *f = std::fopen(s->trig_path.c_str(), "a");
+  if (!f) return fail(s, APK_ERR_INVALID, "cannot open " + s->trig_path);
+  const AgnTriggeringModel::Reduced &r = s->trig_q;
+  std::fprintf(f, "%.17g %.17g %.17g ", s->trig_time, s->trig_dt, s->trig_rate);
+  if (s->trig.mode == APK_TRIG_COLD_GAS)
+    std::fprintf(f, "%.17g", r.cold_mass);
+  else
+    std::fprintf(f, "%.17g %.17g %.17g %.17g", r.total_mass, r.mass_weighted_density / r.total_mass, r.mass_weighted_velocity / r.total_mass,
+                 r.mass_weighted_cs / r.total_mass);
+  std::fprintf(f, "\n");
+  std::fclose(f);
+  return APK_OK;
+}
+
+int cluster_agn_triggering(apk_sim *s, double dt) {
+  SIM_TRY(s, triggering_reduce(s, dt));
+  SIM_TRY(s, triggering_write_row(s));  // (AGNTriggeringFinalizeTriggering writes before it removes)
+  if (s->trig.mode != APK_TRIG_COLD_GAS && s->trig.remove_accreted_mass) SIM_TRY(s, triggering_remove_bondi(s, dt));
+  return APK_OK;
+}
+
+void cluster_triggering_reset(apk_sim *s) {
+  s->trig_q = AgnTriggeringModel::Reduced{};
+  s->trig_rate = s->trig_time = s->trig_dt = 0.0;
+  s->agn.accretion_rate = 0.0;
+  if (s->agn_opt.configured) s->agn_opt.power = s->agn.power(), s->agn_opt.mass_rate = s->agn.mass_rate();
+}
+
 // the origins apk_gravity_src takes: every local block's lower interior corner, then the mesh's lower corner
 int cluster_device_setup(apk_sim *s) {
   const Mesh &m = s->mesh;
@@ -478,6 +632,11 @@ int cluster_device_setup(apk_sim *s) {
   for (int d = 0; d < 3; ++d) h[3 * (size_t)nlb + d] = s->xmin[d];
   SIM_TRY(s, dev_alloc(s, "block_xmin", h.size() * sizeof(double), &s->d_block_xmin));
   SIM_HIP(s, hipMemcpy(s->d_block_xmin, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (s->pkg.agn_triggering && !s->trig_boxes.empty()) {
+    SIM_TRY(s, dev_alloc(s, "trig_boxes", s->trig_boxes.size() * sizeof(apk_trig_box), reinterpret_cast<double **>(&s->d_trig_boxes)));
+    SIM_HIP(s, hipMemcpy(s->d_trig_boxes, s->trig_boxes.data(), s->trig_boxes.size() * sizeof(apk_trig_box), hipMemcpyHostToDevice));
+    SIM_TRY(s, dev_alloc(s, "trig_sums", sizeof(double) * 4 * (size_t)std::max(nlb, 1), &s->d_trig_sums));
+  }
   return APK_OK;
 }
 
@@ -624,6 +783,91 @@ int apk_sim_magnetic_tower_contribs(apk_sim *s, double time, double out[2]) {
   if (!s->cluster.enabled || s->tower.potential == APK_TOWER_UNDEFINED)
     return fail(s, APK_ERR_INVALID, "magnetic_tower_contribs needs problem_id = cluster with a <problem/cluster/magnetic_tower> block");
   return cluster_tower_contribs(s, time, out);
+}
+
+int apk_sim_agn_triggering_options(const apk_sim *s, apk_agn_triggering_options *o) {
+  if (!s || !o || !s->cluster.enabled) return APK_ERR_INVALID;
+  const AgnTriggeringModel &t = s->trig;
+  *o = apk_agn_triggering_options{};
+  o->mode = t.mode, o->remove_accreted_mass = t.remove_accreted_mass ? 1 : 0, o->write_to_file = s->trig_write_to_file ? 1 : 0;
+  o->active_blocks = (int)s->trig_boxes.size(), o->active_box_cells = s->trig_box_cells;
+  o->accretion_radius = t.accretion_radius, o->cold_temp_thresh = t.cold_temp_thresh, o->cold_t_acc = t.cold_t_acc;
+  o->bondi_alpha = t.bondi_alpha, o->bondi_M_smbh = t.bondi_M_smbh, o->bondi_n0 = t.bondi_n0, o->bondi_beta = t.bondi_beta;
+  o->accretion_cfl = t.accretion_cfl;
+  o->mean_molecular_mass = t.mean_molecular_mass, o->mean_molecular_mass_by_kb = t.mean_molecular_mass_by_kb;
+  o->gravitational_constant = t.gravitational_constant;
+  std::snprintf(o->triggering_filename, sizeof(o->triggering_filename), "%s", s->trig_filename.c_str());
+  return APK_OK;
+}
+
+int apk_sim_agn_triggering_state(const apk_sim *s, apk_agn_triggering_state *st) {
+  if (!s || !st || !s->cluster.enabled) return APK_ERR_INVALID;
+  const AgnTriggeringModel::Reduced &r = s->trig_q;
+  *st = apk_agn_triggering_state{};
+  st->cold_mass = r.cold_mass, st->total_mass = r.total_mass, st->mass_weighted_density = r.mass_weighted_density;
+  st->mass_weighted_velocity = r.mass_weighted_velocity, st->mass_weighted_cs = r.mass_weighted_cs;
+  st->accretion_rate = s->trig_rate;
+  st->power = s->agn_opt.configured ? s->agn.power() : 0.0;
+  st->dt_limit = s->trig.estimate_timestep(r);
+  st->time = s->trig_time, st->dt = s->trig_dt;
+  return APK_OK;
+}
+
+static AgnTriggeringModel::Reduced reduced_of(const AgnTriggeringModel &t, const double *q) {
+  AgnTriggeringModel::Reduced r;
+  if (t.mode == APK_TRIG_COLD_GAS) r.cold_mass = q[0];
+  else r.total_mass = q[0], r.mass_weighted_density = q[1], r.mass_weighted_velocity = q[2], r.mass_weighted_cs = q[3];
+  return r;
+}
+
+int apk_sim_agn_triggering_accretion_rate(const apk_sim *s, const double *q, double *rate) {
+  if (!s || !q || !rate || !s->cluster.enabled) return APK_ERR_INVALID;
+  *rate = s->trig.accretion_rate(reduced_of(s->trig, q));
+  return APK_OK;
+}
+
+int apk_sim_agn_triggering_timestep(const apk_sim *s, const double *q, double *dt) {
+  if (!s || !q || !dt || !s->cluster.enabled) return APK_ERR_INVALID;
+  *dt = s->trig.estimate_timestep(reduced_of(s->trig, q));
+  return APK_OK;
+}
+
+int apk_sim_agn_feedback_power_of(const apk_sim *s, double accretion_rate, double *power, double *mass_rate) {
+  if (!s || !power || !mass_rate || !s->cluster.enabled || !s->agn_opt.configured) return APK_ERR_INVALID;
+  AgnFeedbackModel m = s->agn;
+  m.accretion_rate = accretion_rate;
+  *power = m.power(), *mass_rate = m.mass_rate();
+  return APK_OK;
+}
+
+int apk_sim_agn_triggering_active_list(const apk_sim *s, int *out, int n, int *size) {
+  if (!s || !size || !s->cluster.enabled) return APK_ERR_INVALID;
+  *size = (int)s->trig_boxes.size();
+  for (int e = 0; out && e < n && e < *size; ++e) {
+    const apk_trig_box &b = s->trig_boxes[(size_t)e];
+    out[7 * e] = b.block;
+    for (int d = 0; d < 3; ++d) out[7 * e + 1 + d] = b.lo[d], out[7 * e + 4 + d] = b.hi[d];
+  }
+  return APK_OK;
+}
+
+int apk_sim_agn_triggering_reduce(apk_sim *s, double dt) {
+  if (!s || s->host_only) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || !s->pkg.agn_triggering || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "agn_triggering_reduce needs problem_id = cluster with problem/cluster/agn_triggering/triggering_mode other than NONE");
+  SIM_TRY(s, triggering_reduce(s, dt));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+int apk_sim_agn_triggering_remove_bondi(apk_sim *s, double dt) {
+  if (!s || s->host_only) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || s->trig.mode == APK_TRIG_NONE || s->trig.mode == APK_TRIG_COLD_GAS || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "agn_triggering_remove_bondi needs problem_id = cluster with triggering_mode = BOOSTED_BONDI or BOOTH_SCHAYE");
+  SIM_TRY(s, sync_ghosts(s));
+  SIM_TRY(s, triggering_remove_bondi(s, dt));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 // restated in the reference's operation order.  Plain C++ (host/feedback_model.cpp): a stand-alone program can link it.
 #pragma once
 
+#include <string>
+
 #include "../../../include/apk_amd.h"
 
 namespace apk {
@@ -30,7 +32,9 @@ struct AgnFeedbackModel {
   double thermal_mass_fraction = 0, kinetic_mass_fraction = 0, magnetic_mass_fraction = 0;
   double kinetic_jet_velocity = 0, kinetic_jet_temperature = 0, kinetic_jet_e = 0, eceil = 0;
   bool assumed_cold_jet = false;  // neither velocity nor temperature given (the reference prints a warning)
-  // GetFeedbackPower / GetFeedbackMassRate without triggering (agn_feedback.cpp:187-212): accretion_rate = 0
+  // GetFeedbackPower / GetFeedbackMassRate (agn_feedback.cpp:187-212) with the accretion rate of AGN triggering (0
+  // without it): fixed_power + mdot * efficiency * c^2 and mdot * (1 - efficiency) + fixed_power / (efficiency * c^2)
+  double accretion_rate = 0;
   double power() const;
   double mass_rate() const;
 };
@@ -51,5 +55,31 @@ void tower_check_scales(const apk_magnetic_tower_cfg &t);
 // central-difference curl on the interior, b[3][n3][n2][n1]
 void tower_initial_field_block(const apk_magnetic_tower_cfg &t, const apk_jet_coords &jc, double field, const double *x1, int n1,
                                const double *x2, int n2, const double *x3, int n3, const double dx[3], double *b);
+
+// AGNTriggering (agn_triggering.{hpp,cpp}) on already reduced quantities, in the reference's operation order
+struct AgnTriggeringModel {
+  int mode = APK_TRIG_NONE;
+  double accretion_radius = 0, cold_temp_thresh = 0, cold_t_acc = 0, bondi_alpha = 0, bondi_M_smbh = 0, bondi_n0 = 0, bondi_beta = 0;
+  double accretion_cfl = 1e-1;
+  bool remove_accreted_mass = true;
+  double mean_molecular_mass = 0;        // mu * atomic_mass_unit (agn_triggering.cpp:75-78)
+  double mean_molecular_mass_by_kb = 0;  // mean_molecular_mass / k_boltzmann (agn_triggering.cpp:149)
+  double gravitational_constant = 0;     // Units::gravitational_constant()
+  // the reduced quantities (the "agn_triggering_*" params): COLD_GAS reads cold_mass, the Bondi-like modes the four sums
+  struct Reduced {
+    double cold_mass = 0, total_mass = 0, mass_weighted_density = 0, mass_weighted_velocity = 0, mass_weighted_cs = 0;
+  };
+  // GetAccretionRate (agn_triggering.cpp:319-365)
+  double accretion_rate(const Reduced &q) const;
+  // EstimateTimeStep (agn_triggering.cpp:556-584); numeric_limits<double>::max() where there is no limit
+  double estimate_timestep(const Reduced &q) const;
+};
+// ParseAGNTriggeringMode (agn_triggering.cpp:34-51); throws with the reference's wording
+int parse_agn_triggering_mode(const std::string &mode_str);
+
+// The active list of one block and one direction: the range [lo, hi) of extended indices (0 .. n_ext - 1; the first
+// interior cell is `first`) whose centres x[i] can satisfy |x| < radius, widened by one cell per side and clipped to the
+// block's arrays.  x[n_ext]: the centres of the extended cells.  lo >= hi: no cell.
+void triggering_index_range(const double *x, int n_ext, double radius, int *lo, int *hi);
 
 }  // namespace apk

@@ -1,6 +1,7 @@
 // feedback_model.cpp -- the host-side model of the cluster problem's fixed-power AGN feedback (host/feedback.hpp): the
 // jet frame, AGNFeedback's derived jet numbers with its five consistency requirements, the per-stage numbers, the
-// magnetic tower's power scaling and its initial field.  Plain C++, no driver, no GPU: tools/cluster/feedback_check.cpp
+// magnetic tower's power scaling and its initial field; AGN triggering's accretion rate, time-step rule and the index
+// range of its active list.  Plain C++, no driver, no GPU: tools/cluster/feedback_check.cpp
 // links it alone.  std::pow and M_PI stand where the reference has them; squares of positions are products
 // (feedback_math.hpp).
 #include <cmath>
@@ -23,8 +24,10 @@ apk_jet_coords jet_coords_at(double jet_theta, double jet_phi_dot, double jet_ph
   return apk_jet_coords{std::cos(jet_theta), std::sin(jet_theta), std::cos(phi), std::sin(phi)};
 }
 
-double AgnFeedbackModel::power() const { return in.fixed_power; }
-double AgnFeedbackModel::mass_rate() const { return in.fixed_power / (in.efficiency * std::pow(in.speed_of_light, 2)); }
+double AgnFeedbackModel::power() const { return in.fixed_power + accretion_rate * in.efficiency * std::pow(in.speed_of_light, 2); }
+double AgnFeedbackModel::mass_rate() const {
+  return accretion_rate * (1 - in.efficiency) + in.fixed_power / (in.efficiency * std::pow(in.speed_of_light, 2));
+}
 
 // AGNFeedback::AGNFeedback (agn_feedback.cpp:34-160)
 AgnFeedbackModel agn_feedback_model(const AgnFeedbackInput &in) {
@@ -157,6 +160,71 @@ void tower_initial_field_block(const apk_magnetic_tower_cfg &t, const apk_jet_co
         b[1 * nb + q] = (a(0, k + 1, j, i) - a(0, k - 1, j, i)) / dx[2] / 2.0 - (a(2, k, j, i + 1) - a(2, k, j, i - 1)) / dx[0] / 2.0;
         b[2 * nb + q] = (a(1, k, j, i + 1) - a(1, k, j, i - 1)) / dx[0] / 2.0 - (a(0, k, j + 1, i) - a(0, k, j - 1, i)) / dx[1] / 2.0;
       }
+}
+
+int parse_agn_triggering_mode(const std::string &mode_str) {
+  if (mode_str == "COLD_GAS") return APK_TRIG_COLD_GAS;
+  if (mode_str == "BOOSTED_BONDI") return APK_TRIG_BOOSTED_BONDI;
+  if (mode_str == "BOOTH_SCHAYE") return APK_TRIG_BOOTH_SCHAYE;
+  if (mode_str == "NONE") return APK_TRIG_NONE;
+  throw std::runtime_error("### FATAL ERROR in function [ParseAGNTriggeringMode]\nUnrecognized AGNTriggeringMode: \"" + mode_str + "\"");
+}
+
+// agn_triggering.cpp:319-365
+double AgnTriggeringModel::accretion_rate(const Reduced &q) const {
+  switch (mode) {
+  case APK_TRIG_COLD_GAS:
+    return q.cold_mass / cold_t_acc;
+  case APK_TRIG_BOOSTED_BONDI:
+  case APK_TRIG_BOOTH_SCHAYE: {
+    const double mean_mass_weighted_density = q.mass_weighted_density / q.total_mass;
+    const double mean_mass_weighted_velocity = q.mass_weighted_velocity / q.total_mass;
+    const double mean_mass_weighted_cs = q.mass_weighted_cs / q.total_mass;
+    double alpha = 0;
+    if (mode == APK_TRIG_BOOSTED_BONDI) {
+      alpha = bondi_alpha;
+    } else {
+      const double mean_mass_weighted_n = mean_mass_weighted_density / mean_molecular_mass;
+      alpha = (mean_mass_weighted_n <= bondi_n0) ? 1 : std::pow(mean_mass_weighted_n / bondi_n0, bondi_beta);
+    }
+    return alpha * 2 * M_PI * std::pow(gravitational_constant, 2) * std::pow(bondi_M_smbh, 2) * mean_mass_weighted_density /
+           (std::pow(std::pow(mean_mass_weighted_velocity, 2) + std::pow(mean_mass_weighted_cs, 2), 3. / 2.));
+  }
+  default:
+    return 0;
+  }
+}
+
+// agn_triggering.cpp:556-584
+double AgnTriggeringModel::estimate_timestep(const Reduced &q) const {
+  switch (mode) {
+  case APK_TRIG_COLD_GAS:
+    return accretion_cfl * cold_t_acc;
+  case APK_TRIG_BOOSTED_BONDI:
+  case APK_TRIG_BOOTH_SCHAYE: {
+    // (before the first reduction: the reference ignores the constraint during the first time step)
+    if (q.total_mass == 0) return std::numeric_limits<double>::max();
+    const double mdot = accretion_rate(q);
+    return accretion_cfl * q.total_mass / mdot;
+  }
+  default:
+    return std::numeric_limits<double>::max();
+  }
+}
+
+void triggering_index_range(const double *x, int n_ext, double radius, int *lo, int *hi) {
+  int first = n_ext, last = -1;
+  for (int i = 0; i < n_ext; ++i)
+    if (std::fabs(x[i]) < radius) {
+      if (first == n_ext) first = i;
+      last = i;
+    }
+  if (last < 0) {
+    *lo = *hi = 0;
+    return;
+  }
+  *lo = first - 1 < 0 ? 0 : first - 1;
+  *hi = last + 2 > n_ext ? n_ext : last + 2;
 }
 
 }  // namespace apk

@@ -476,6 +476,9 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
   const bool sts = s->pkg.diffusion_sts();
   // (rkl2: dt_diff does not join min_dt directly, hydro.cpp:950-956)
   double dt = std::min(std::min(e.dt_hyp_local, sts ? kHuge : e.dt_diff_local), e.dt_cool_local);
+  // the triggering limit (cluster.cpp:95-107 through ProblemEstimateTimestep): joins min_dt, not dt_hyp.  It follows from
+  // the globally reduced quantities: the same number on every rank
+  if (s->pkg.agn_triggering) dt = std::min(dt, s->trig.estimate_timestep(s->trig_q));
   if (s->pkg.max_dt > 0.0 && s->pkg.max_dt < dt) dt = s->pkg.max_dt;
   // one reduction for both minima: the time step, and the hyperbolic estimate that the next cycle's
   // c_h needs (hydro.cpp:102-143 reduces it in PreStepMeshUserWorkInLoop; same value, one message less).
@@ -929,6 +932,8 @@ void apk_sim_destroy(apk_sim *s) {
     dev_free(s, s->d_phases);
     dev_free(s, s->d_block_xmin);
     dev_free(s, s->d_tower_contribs);
+    dev_free(s, reinterpret_cast<double *>(s->d_trig_boxes));
+    dev_free(s, s->d_trig_sums);
     dev_free(s, s->d_cons2[0]);
     dev_free(s, s->d_prim2[0]);
     dev_free(s, s->d_prim2[1]);
@@ -1030,6 +1035,7 @@ int apk_sim_initialize(apk_sim *s) {
   s->zone_cycles = 0;
   s->pkg.mindx = kHuge;
   s->pkg.dt_hyp = kHuge;
+  if (s->cluster.enabled) cluster_triggering_reset(s);
   SIM_TRY(s, exchange_ghosts(s));
   SIM_TRY(s, fill_derived(s));
   // adaptive meshes: tag the initial condition, refine, and evaluate the problem generator again on
@@ -1070,6 +1076,9 @@ int apk_sim_step(apk_sim *s) {
   // 581-583), both sized with the diffusive limit estimated at the end of the previous cycle
   const bool sts = s->pkg.diffusion_sts();
   if (sts) SIM_TRY(s, sts_half_step(s, 0.5 * s->dt));
+  // AGN triggering: the accretion rate of the cycle and the removal of the accreted gas, with the cycle's dt, before
+  // the tower's contributions (hydro_driver.cpp:360-394)
+  if (s->pkg.agn_triggering) SIM_TRY(s, cluster_agn_triggering(s, s->dt));
   // the magnetic tower's power scaling: its two sums once per cycle, before stage 1 (hydro_driver.cpp:409-449)
   if (s->agn_opt.tower_power_scaling) {
     double contribs[2];
@@ -1443,6 +1452,9 @@ int apk_sim_history_labels(const apk_sim *s, char *buf, size_t len) {
   if (s->fmft) l += mhd ? " Ms Ma plasma_beta" : " Ms";
   if (s->problem_id == "field_loop") l += " UserRelDivB";
   if (s->problem_id == "linear_wave_mhd" && s->lwm.dump_max_v2) l += " MaxAbsV2";
+  // (agn_feedback.cpp:162-177 adds the column whenever feedback is enabled; here only runs with triggering have it, so
+  // that the others keep their columns)
+  if (s->pkg.agn_triggering) l += " agn_feedback_power";
   std::snprintf(buf, len, "%s", l.c_str());
   return APK_OK;
 }
@@ -1486,6 +1498,7 @@ int apk_sim_write_history(apk_sim *s, const char *path) {
   if (s->fmft) row.insert(row.end(), t3, t3 + (mhd ? 3 : 1));
   if (floop) row.push_back(urdb);
   if (maxv2) row.push_back(mv2);
+  if (s->pkg.agn_triggering) row.push_back(s->agn_opt.configured ? s->agn.power() : 0.0);
   FILE *f = std::fopen(path, "r");
   const bool fresh = (f == nullptr);
   if (f) std::fclose(f);
@@ -1586,6 +1599,19 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     }
   } csv_scope{s};
   if (s->tracers && s->tracers->lookback) s->tracers->csv_path = std::string(outdir) + "/correlations.csv";
+  // problem/cluster/agn_triggering/write_to_file: truncated here, a row per cycle while this call runs
+  struct TrigScope {
+    apk_sim *s;
+    ~TrigScope() { s->trig_path.clear(); }
+  } trig_scope{s};
+  if (s->pkg.agn_triggering && s->trig_write_to_file) {
+    s->trig_path = std::string(outdir) + "/" + s->trig_filename;
+    if (s->rank == 0) {
+      FILE *f = std::fopen(s->trig_path.c_str(), "w");
+      if (!f) return fail(s, APK_ERR_INVALID, "cannot open " + s->trig_path);
+      std::fclose(f);
+    }
+  }
   SIM_TRY(s, apk_sim_initialize(s));
   // problem/cluster/hydrostatic_equilibrium/test_he_sphere: the reference writes the file when it builds the package
   SIM_TRY(s, cluster_write_test_profile(s, std::string(outdir) + "/test_he_sphere.dat"));

@@ -90,7 +90,10 @@ struct HydroPackage {
   // problem/cluster/agn_feedback/fixed_power != 0 (and not disabled) or problem/cluster/magnetic_tower/fixed_field_rate
   // != 0: the feedback sources follow gravity in ProblemSourceUnsplit (cluster.cpp:63-84; host/cluster.cpp)
   bool feedback_srcterm = false;
-  bool flux_path_sources() const { return diffusion_configured() || cooling || gravity_srcterm || feedback_srcterm; }
+  // problem/cluster/agn_triggering/triggering_mode != NONE: the cycle's reduction and removal update cons and prim in
+  // place before stage 1 (hydro_driver.cpp:360-394)
+  bool agn_triggering = false;
+  bool flux_path_sources() const { return diffusion_configured() || cooling || gravity_srcterm || feedback_srcterm || agn_triggering; }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -185,6 +188,17 @@ struct apk_sim {
   apk_magnetic_tower_cfg tower{};
   double tower_linear_contrib = 0.0, tower_quadratic_contrib = 0.0;
   double *d_tower_contribs = nullptr;  // [nblocks][2] (allocated on first use)
+  // AGN triggering (host/feedback_model.cpp, host/cluster.cpp): the model, the reduced quantities of the last cycle with
+  // what follows from them, this rank's active list (built once at creation) and its device copy
+  apk::AgnTriggeringModel trig;
+  apk::AgnTriggeringModel::Reduced trig_q;
+  double trig_rate = 0.0, trig_time = 0.0, trig_dt = 0.0;
+  bool trig_write_to_file = false;
+  std::string trig_filename, trig_path;  // trig_path: the file apk_sim_execute appends to (empty: none)
+  std::vector<apk_trig_box> trig_boxes;
+  long long trig_box_cells = 0, trig_max_box_cells = 0;
+  apk_trig_box *d_trig_boxes = nullptr;
+  double *d_trig_sums = nullptr;  // [nblocks][4]
   bool host_only = false;
   bool fused = true;
   int rank = 0, nranks = 1;

@@ -56,6 +56,8 @@ void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u);  // its gen
 int cluster_device_setup(apk_sim *s);   // the per-block origins of the gravity and feedback sources
 bool cluster_needs_block_origins(const apk_sim *s);
 int cluster_tower_contribs(apk_sim *s, double time, double out[2]);  // the tower's power contributions, all ranks
+int cluster_agn_triggering(apk_sim *s, double dt);  // AGN triggering of one cycle: reduce, sum over ranks, remove
+void cluster_triggering_reset(apk_sim *s);          // the reduced quantities back to zero (initialisation)
 int cluster_feedback_sources(apk_sim *s, double beta_dt);  // AGN feedback, tower power, tower fixed rate: one stage
 int cluster_write_test_profile(apk_sim *s, const std::string &path);  // test_he_sphere.dat
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);

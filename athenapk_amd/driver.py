@@ -165,6 +165,52 @@ class _ClusterHost:
                                                                          float(power), C.byref(out)))
         return out.value
 
+    def agn_triggering_options(self):
+        """lib.AgnTriggeringOptions: <problem/cluster/agn_triggering> as parsed, mean_molecular_mass, the temperature
+        factor the cold-gas kernel is passed, and the number of active blocks and box cells on this rank"""
+        o = L.AgnTriggeringOptions()
+        self._cluster_check(self.lib.apk_sim_agn_triggering_options(self.h, C.byref(o)))
+        return o
+
+    def agn_triggering_state(self):
+        """lib.AgnTriggeringState: the last cycle's reduced quantities, accretion rate, power and time-step limit"""
+        st = L.AgnTriggeringState()
+        self._cluster_check(self.lib.apk_sim_agn_triggering_state(self.h, C.byref(st)))
+        return st
+
+    def _trig_q(self, q):
+        a = np.zeros(4)
+        q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        a[:len(q)] = q
+        return a
+
+    def agn_triggering_accretion_rate(self, q):
+        """GetAccretionRate of reduced quantities: q = cold_mass (COLD_GAS) or (total_mass, the three mass-weighted sums)"""
+        a, out = self._trig_q(q), C.c_double(0.0)
+        self._cluster_check(self.lib.apk_sim_agn_triggering_accretion_rate(self.h, a.ctypes.data_as(L.c_dp), C.byref(out)))
+        return out.value
+
+    def agn_triggering_timestep(self, q):
+        """EstimateTimeStep of reduced quantities (sys.float_info.max: no limit)"""
+        a, out = self._trig_q(q), C.c_double(0.0)
+        self._cluster_check(self.lib.apk_sim_agn_triggering_timestep(self.h, a.ctypes.data_as(L.c_dp), C.byref(out)))
+        return out.value
+
+    def agn_feedback_power_of(self, accretion_rate):
+        """(power, mass_rate) of AGN feedback for this accretion rate (GetFeedbackPower, GetFeedbackMassRate)"""
+        p, m = C.c_double(0.0), C.c_double(0.0)
+        self._cluster_check(self.lib.apk_sim_agn_feedback_power_of(self.h, float(accretion_rate), C.byref(p), C.byref(m)))
+        return p.value, m.value
+
+    def agn_triggering_active_list(self):
+        """this rank's active list: [(local block, (lo_i, lo_j, lo_k), (hi_i, hi_j, hi_k))], boxes in the extended index
+        space, hi exclusive"""
+        size = C.c_int(0)
+        self._cluster_check(self.lib.apk_sim_agn_triggering_active_list(self.h, None, 0, C.byref(size)))
+        out = (C.c_int * (7 * max(size.value, 1)))()
+        self._cluster_check(self.lib.apk_sim_agn_triggering_active_list(self.h, out, size.value, C.byref(size)))
+        return [(out[7 * e], tuple(out[7 * e + 1:7 * e + 4]), tuple(out[7 * e + 4:7 * e + 7])) for e in range(size.value)]
+
     def pgen_block(self, lb):
         """the problem generator's conserved state of local block lb, interior cells: [nvar][nx3][nx2][nx1] of the block"""
         nf = self.info
@@ -703,6 +749,16 @@ class Simulation(_FmftHost, _ClusterHost, _MeshView):
         mass_to_add): conserved B, E and rho of the interior cells change"""
         self._check(self.lib.apk_sim_magnetic_tower_src(self.h, float(field), float(mass),
                                                         float(self.time if time is None else time)))
+
+    def agn_triggering_reduce(self, dt):
+        """one reduction of AGN triggering (COLD_GAS: with its removal) on the current state with this dt, summed over
+        ranks; returns the updated agn_triggering_state().  A collective"""
+        self._check(self.lib.apk_sim_agn_triggering_reduce(self.h, float(dt)))
+        return self.agn_triggering_state()
+
+    def agn_triggering_remove_bondi(self, dt):
+        """RemoveBondiAccretedGas once on the current state with the stored total_mass and accretion rate"""
+        self._check(self.lib.apk_sim_agn_triggering_remove_bondi(self.h, float(dt)))
 
     def magnetic_tower_contribs(self, time=None):
         """(sum(prim_B . b1 dV), sum(0.5 b1^2 dV)) over the whole mesh, b1 the tower's field at unit strength: what the

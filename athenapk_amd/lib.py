@@ -29,7 +29,7 @@ APK_FLAG_AGN_NEG_PRESSURE = 16
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
                 "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort", "gravity",
-                "agn_feedback", "tower", "tower_contribs")
+                "agn_feedback", "tower", "tower_contribs", "triggering")
 
 APK_OK = 0
 APK_RCCL_ID_BYTES = 128
@@ -161,6 +161,39 @@ class AgnFeedbackOptions(C.Structure):
                                            "jet_theta", "jet_phi_dot", "jet_phi0", "li_alpha", "l_scale", "donut_offset",
                                            "donut_thickness", "initial_field", "fixed_field_rate", "fixed_mass_rate",
                                            "l_mass_scale", "speed_of_light", "mbar_gm1_over_kb", "power", "mass_rate")])
+
+
+# triggering_mode of AGN triggering (apk_agn_triggering_mode; cluster::AGNTriggeringMode)
+TRIGGERING_MODE = {"NONE": 0, "COLD_GAS": 1, "BOOSTED_BONDI": 2, "BOOTH_SCHAYE": 3}
+
+
+class TrigBox(C.Structure):
+    """apk_trig_box: an entry of the active list -- a block of the pack and its index box [lo, hi) in the block's
+    extended index space (i, j, k)"""
+    _fields_ = [("block", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3)]
+
+
+class AgnTriggeringCfg(C.Structure):
+    """apk_agn_triggering_cfg: what apk_agn_triggering_reduce takes by value"""
+    _fields_ = ([("mode", C.c_int), ("remove_accreted_mass", C.c_int)] +
+                [(n, C.c_double) for n in ("accretion_radius", "cold_temp_thresh", "cold_t_acc", "mean_molecular_mass_by_kb")])
+
+
+class AgnTriggeringOptions(C.Structure):
+    """apk_agn_triggering_options: <problem/cluster/agn_triggering> as parsed, the derived mean molecular mass and
+    temperature factor, and the size of this rank's active list (include/apk_host.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("mode", "remove_accreted_mass", "write_to_file", "active_blocks")] +
+                [("active_box_cells", C.c_longlong)] +
+                [(n, C.c_double) for n in ("accretion_radius", "cold_temp_thresh", "cold_t_acc", "bondi_alpha", "bondi_M_smbh",
+                                           "bondi_n0", "bondi_beta", "accretion_cfl", "mean_molecular_mass",
+                                           "mean_molecular_mass_by_kb", "gravitational_constant")] +
+                [("triggering_filename", C.c_char * 256)])
+
+
+class AgnTriggeringState(C.Structure):
+    """apk_agn_triggering_state: the last cycle's reduced quantities and what follows from them"""
+    _fields_ = [(n, C.c_double) for n in ("cold_mass", "total_mass", "mass_weighted_density", "mass_weighted_velocity",
+                                          "mass_weighted_cs", "accretion_rate", "power", "dt_limit", "time", "dt")]
 
 
 class UnitsInfo(C.Structure):
@@ -371,6 +404,8 @@ def _signatures():
         "apk_agn_feedback_src": (i, [vp, vp, i, C.POINTER(Eos), C.POINTER(AgnFeedbackCfg), C.POINTER(JetCoords), vp, vp]),
         "apk_magnetic_tower_src": (i, [vp, vp, C.POINTER(MagneticTowerCfg), C.POINTER(JetCoords), vp, d, d, vp]),
         "apk_magnetic_tower_power_contribs": (i, [vp, vp, C.POINTER(MagneticTowerCfg), C.POINTER(JetCoords), vp, vp, vp]),
+        "apk_agn_triggering_reduce": (i, [vp, vp, i, C.POINTER(Eos), C.POINTER(AgnTriggeringCfg), vp, i, C.c_int64, vp, d, vp, vp]),
+        "apk_agn_triggering_remove_bondi": (i, [vp, vp, i, C.POINTER(Eos), d, vp, i, C.c_int64, vp, d, d, d, vp]),
         "apk_first_order_flux_correct": (i, [vp, vp, vp, i, E, d, d, d, d, C.POINTER(ll), vp]),
         "apk_count_unphysical": (i, [vp, vp, i, C.POINTER(ll), vp]),
         "apk_history": (i, [vp, vp, i, c_dp, vp]),
@@ -464,6 +499,14 @@ def _signatures():
         "apk_sim_agn_feedback_src": (i, [vp, d, d]),
         "apk_sim_magnetic_tower_src": (i, [vp, d, d, d]),
         "apk_sim_magnetic_tower_contribs": (i, [vp, d, c_dp]),
+        "apk_sim_agn_triggering_options": (i, [vp, C.POINTER(AgnTriggeringOptions)]),
+        "apk_sim_agn_triggering_state": (i, [vp, C.POINTER(AgnTriggeringState)]),
+        "apk_sim_agn_triggering_accretion_rate": (i, [vp, c_dp, c_dp]),
+        "apk_sim_agn_triggering_timestep": (i, [vp, c_dp, c_dp]),
+        "apk_sim_agn_feedback_power_of": (i, [vp, d, c_dp, c_dp]),
+        "apk_sim_agn_triggering_active_list": (i, [vp, C.POINTER(C.c_int), i, C.POINTER(C.c_int)]),
+        "apk_sim_agn_triggering_reduce": (i, [vp, d]),
+        "apk_sim_agn_triggering_remove_bondi": (i, [vp, d]),
         "apk_sim_tracers_options": (i, [vp, C.POINTER(TracersOptions)]),
         "apk_sim_tracers_count": (i, [vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ll)]),
         "apk_sim_tracers_stats": (i, [vp, C.POINTER(ll), C.POINTER(ll)]),

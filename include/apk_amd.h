@@ -981,6 +981,46 @@ int apk_magnetic_tower_power_contribs(apk_ctx *ctx, const apk_pack *md, const ap
                                       const apk_jet_coords *jet, const double *block_xmin, double *contribs,
                                       apk_stream_t stream);
 
+/* ---- AGN triggering of the cluster problem (src/pgen/cluster/agn_triggering.{hpp,cpp}, cluster_utils.hpp:40-52) -------
+ * The accretion sphere is a few cells across at the centre of a large mesh, and neither the mesh nor the radius changes
+ * during a run: the host builds an ACTIVE LIST once (csrc/host/cluster.cpp: triggering_active_list) -- per local block
+ * the index box, in the block's extended index space (ghost cells included, 0 .. ni-1), of the cells whose centre can
+ * satisfy |x_d| < accretion_radius in all three directions, widened by one cell per side; blocks with an empty box are
+ * not listed -- and the kernels launch over the list only.  A kernel clips every box to the block's arrays. */
+enum apk_agn_triggering_mode { APK_TRIG_NONE = 0, APK_TRIG_COLD_GAS = 1, APK_TRIG_BOOSTED_BONDI = 2, APK_TRIG_BOOTH_SCHAYE = 3 };
+typedef struct apk_trig_box {
+  int block;        /* index into the pack */
+  int lo[3], hi[3]; /* i, j, k: lo inclusive, hi exclusive, in the extended index space */
+} apk_trig_box;
+typedef struct apk_agn_triggering_cfg {
+  int mode;                    /* apk_agn_triggering_mode, not NONE */
+  int remove_accreted_mass;    /* COLD_GAS: remove in the reduction's launch */
+  double accretion_radius;
+  double cold_temp_thresh, cold_t_acc;
+  double mean_molecular_mass_by_kb; /* mean_molecular_mass / k_boltzmann, the host's number */
+} apk_agn_triggering_cfg;
+/* Replaces AGNTriggering::ReduceBondiTriggeringQuantities (agn_triggering.cpp:202-264) and ReduceColdMass
+ * (agn_triggering.cpp:124-198).  sums: device, [nblocks][4]; blocks outside the list report zeros.
+ * Bondi-like modes: per block the sums over its interior cells with r2 < R^2 (strict) of m = rho dV, m rho, m |v| and
+ * m sqrt(gamma p / rho), from the stored primitives.  COLD_GAS: sums[b][0] = the interior mass of cells with r2 < R^2 and
+ * T = mean_molecular_mass_by_kb * p / rho <= cold_temp_thresh (inclusive), the other three 0; and with
+ * remove_accreted_mass every such cell of the box, ghost cells included, gets delta = -rho / cold_t_acc * dt through
+ * AddDensityToConsAtFixedVelTemp (cluster_utils.hpp:40-52) and its primitives from ConsToPrim, whose flags go into the
+ * flag word.  r2 = x * x + y * y + z * z (products where the reference writes pow(x, 2)).
+ * Grid (P, nboxes): each workgroup of 256 takes a fixed contiguous share of its box's cells, i fastest; a lane adds its
+ * cells in index order, the workgroup reduces through a fixed LDS tree, a second kernel adds a block's P partials in
+ * order.  No atomics: a block's sums depend on nothing but the block and its box.  boxes: device, nboxes entries, at
+ * most one per block; max_box_cells: the largest box.  block_xmin as for apk_gravity_src. */
+int apk_agn_triggering_reduce(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_agn_triggering_cfg *cfg,
+                              const apk_trig_box *boxes, int nboxes, int64_t max_box_cells, const double *block_xmin, double dt,
+                              double *sums, apk_stream_t stream);
+/* Replaces AGNTriggering::RemoveBondiAccretedGas (agn_triggering.cpp:269-315) over the same list: every cell of a box
+ * with r2 < R^2, ghost cells included, gets delta = -rho / total_mass * accretion_rate * dt (that association) through
+ * AddDensityToConsAtFixedVelTemp, then ConsToPrim. */
+int apk_agn_triggering_remove_bondi(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, double accretion_radius,
+                                    const apk_trig_box *boxes, int nboxes, int64_t max_box_cells, const double *block_xmin,
+                                    double total_mass, double accretion_rate, double dt, apk_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
  * they are launched on.  When enabled, every kernel launch of the listed groups is
@@ -1005,7 +1045,8 @@ enum apk_timing_slot {
   APK_T_AGN_FEEDBACK = 15,   /* apk_agn_feedback_src */
   APK_T_TOWER = 16,          /* apk_magnetic_tower_src */
   APK_T_TOWER_CONTRIBS = 17, /* apk_magnetic_tower_power_contribs */
-  APK_T_COUNT = 18
+  APK_T_TRIGGERING = 18,     /* apk_agn_triggering_reduce, apk_agn_triggering_remove_bondi */
+  APK_T_COUNT = 19
 };
 int apk_kernel_timing_enable(apk_ctx *ctx, int on);
 /* total_ms / launches may be NULL */

@@ -213,7 +213,7 @@ int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int
  * profile and the hydrostatic-equilibrium sphere, or uniform gas; a uniform field with GLM-MHD.  Keys and defaults are
  * the reference's (<problem/cluster>, .../gravity, .../entropy_profile, .../hydrostatic_equilibrium, .../uniform_gas,
  * .../uniform_b_field; AGN feedback and the magnetic tower: below).  Refused at creation, each with a message naming the
- * key: refined meshes, nx2 = 1 or nx3 = 1, agn_triggering other than NONE, stellar_feedback, snia_feedback unless
+ * key: refined meshes, nx2 = 1 or nx3 = 1, stellar_feedback, snia_feedback unless
  * disabled = true, any clips key off its default, init_perturb/sigma_v or sigma_b != 0, dipole_b_field, reductions, the
  * sphere without <units> and hydro/He_mass_fraction, uniform_b_field without GLM-MHD, gravity_srcterm with
  * diffusion/integrator = rkl2.  All entries below work on a host-only sim. */
@@ -257,15 +257,16 @@ int apk_sim_gravity_src(apk_sim *sim, double beta_dt);
  * creation, naming the key: fixed_power != 0 without <units> and hydro/He_mass_fraction, or with all three fractions zero
  * (the reference fails that at the first stage); magnetic_fraction != 0 or a non-zero tower field or rate without
  * hydro/fluid = glmmhd; a magnetic_tower block whose potential_type is neither donut nor li (stricter than the
- * reference, which fails inside a kernel); enable_tracer = true; agn_triggering other than NONE (the accretion rate is
- * zero: power = fixed_power).  No agn_feedback_power history column.  All entries but the three sources work on a
- * host-only sim. */
+ * reference, which fails inside a kernel); enable_tracer = true.  With AGN triggering (below) the power is fixed_power +
+ * accretion_rate * efficiency * c^2, the source runs whenever that is not zero, and the history has an
+ * agn_feedback_power column; without it the columns are the ones a run had before.  All entries but the three sources
+ * work on a host-only sim. */
 typedef struct apk_agn_feedback_options {
   int configured; /* a <problem/cluster/agn_feedback> block was read and its derived numbers are valid */
-  int active;     /* fixed_power != 0 and not disabled: the source runs in every stage */
+  int active;     /* not disabled and (fixed_power != 0 or a triggering mode): the source runs in every stage whose power != 0 */
   int disabled, enable_magnetic_tower_mass_injection, assumed_cold_jet;
   int tower_potential; /* apk_tower_potential */
-  int tower_power_scaling; /* magnetic_fraction != 0 && fixed_power != 0: the contributions are reduced every cycle */
+  int tower_power_scaling; /* magnetic_fraction != 0 && (fixed_power != 0 || a triggering mode): the contributions are reduced every cycle */
   double fixed_power, efficiency;
   double thermal_fraction, kinetic_fraction, magnetic_fraction; /* normalised to sum 1 */
   double thermal_mass_fraction, kinetic_mass_fraction, magnetic_mass_fraction;
@@ -275,7 +276,7 @@ typedef struct apk_agn_feedback_options {
   double jet_theta, jet_phi_dot, jet_phi0;
   double li_alpha, l_scale, donut_offset, donut_thickness, initial_field, fixed_field_rate, fixed_mass_rate, l_mass_scale;
   double speed_of_light, mbar_gm1_over_kb; /* what the derivations take from Units and the composition */
-  double power, mass_rate;                 /* GetFeedbackPower / GetFeedbackMassRate with zero accretion */
+  double power, mass_rate;                 /* GetFeedbackPower / GetFeedbackMassRate with the current accretion rate */
 } apk_agn_feedback_options;
 int apk_sim_agn_feedback_options(const apk_sim *sim, apk_agn_feedback_options *opt);
 /* the numbers of agn_feedback.cpp:263-303 for beta_dt, and the jet frame at `time` (what the kernels are passed) */
@@ -294,6 +295,61 @@ int apk_sim_magnetic_tower_src(apk_sim *sim, double field, double mass, double t
  * nblocks_global, allreduce_sum adds the arrays, and the host adds the slots in global block order: the result does not
  * depend on how the blocks are distributed over ranks (the reference sums per-rank partial sums).  A collective. */
 int apk_sim_magnetic_tower_contribs(apk_sim *sim, double time, double out[2]);
+
+/* ---- AGN triggering of the cluster problem (src/pgen/cluster/agn_triggering.{hpp,cpp}; csrc/host/feedback_model.cpp,
+ * csrc/host/cluster.cpp, csrc/kernels_triggering.hip) -----------------------------------------------------------------
+ * <problem/cluster/agn_triggering> with the reference's keys and defaults: triggering_mode = NONE | COLD_GAS |
+ * BOOSTED_BONDI | BOOTH_SCHAYE, accretion_radius, cold_temp_thresh (K), cold_t_acc, bondi_alpha, bondi_n0, bondi_beta,
+ * accretion_cfl (0.1), removed_accreted_mass (true), write_to_file, triggering_filename; bondi_M_smbh is
+ * problem/cluster/gravity/m_smbh.  An unknown mode is a deck error ("Unrecognized AGNTriggeringMode").  Refused at
+ * creation, naming the key: a mode with accretion_radius <= 0 or COLD_GAS with cold_t_acc <= 0 (both name
+ * .../triggering_mode; stricter than the reference, where they give 0/0 and an infinite rate), BOOTH_SCHAYE with
+ * bondi_n0 <= 0, accretion_cfl <= 0, a mode without <units> and hydro/He_mass_fraction, with diffusion/integrator = rkl2,
+ * or with feedback enabled and all three fractions zero.
+ * Once per cycle, before the tower's contributions (hydro_driver.cpp:360-394): reduce (COLD_GAS removes in the same
+ * launch, with the cycle's dt), one sum over ranks with every block's sums in its own slot, the slots added in global
+ * block order -- the result does not depend on the distribution of the blocks -- and, for the Bondi-like modes with
+ * removed_accreted_mass, the removal.  A Bondi-like cycle whose reduced total_mass is zero fails the step.  The
+ * triggering limit of the time step (agn_triggering.cpp:556-584) joins min_dt.  Not restarted; uniform meshes. */
+typedef struct apk_agn_triggering_options {
+  int mode; /* apk_agn_triggering_mode */
+  int remove_accreted_mass, write_to_file;
+  int active_blocks;          /* this rank's entries of the active list ... */
+  long long active_box_cells; /* ... and the cells of their boxes */
+  double accretion_radius, cold_temp_thresh, cold_t_acc, bondi_alpha, bondi_M_smbh, bondi_n0, bondi_beta, accretion_cfl;
+  double mean_molecular_mass;       /* mu * atomic_mass_unit */
+  double mean_molecular_mass_by_kb; /* mean_molecular_mass / k_boltzmann: what the kernel is passed */
+  double gravitational_constant;
+  char triggering_filename[256];
+} apk_agn_triggering_options;
+int apk_sim_agn_triggering_options(const apk_sim *sim, apk_agn_triggering_options *opt);
+/* the last cycle's (or the last apk_sim_agn_triggering_reduce's) reduced quantities, all zero before the first */
+typedef struct apk_agn_triggering_state {
+  double cold_mass;                                                                /* COLD_GAS */
+  double total_mass, mass_weighted_density, mass_weighted_velocity, mass_weighted_cs; /* Bondi-like: the four sums */
+  double accretion_rate; /* GetAccretionRate of them (0 before the first reduction) */
+  double power;          /* AGNFeedback::GetFeedbackPower with that rate (0 without an <agn_feedback> block) */
+  double dt_limit;       /* EstimateTimeStep: DBL_MAX where the reference gives no limit */
+  double time, dt;       /* of the cycle that reduced them */
+} apk_agn_triggering_state;
+int apk_sim_agn_triggering_state(const apk_sim *sim, apk_agn_triggering_state *st);
+/* GetAccretionRate (agn_triggering.cpp:319-365) of the given reduced quantities with this sim's parameters: q[0] =
+ * cold_mass (COLD_GAS), or q[0..3] = total_mass and the three mass-weighted sums.  Works on a host-only sim. */
+int apk_sim_agn_triggering_accretion_rate(const apk_sim *sim, const double *q, double *rate);
+/* EstimateTimeStep (agn_triggering.cpp:556-584) of the given reduced quantities */
+int apk_sim_agn_triggering_timestep(const apk_sim *sim, const double *q, double *dt);
+/* AGNFeedback::GetFeedbackPower and GetFeedbackMassRate (agn_feedback.cpp:187-212) for the given accretion rate:
+ * fixed_power + rate * efficiency * c^2 and rate * (1 - efficiency) + fixed_power / (efficiency * c^2).  Needs a configured
+ * feedback model (apk_agn_feedback_options.configured).  Works on a host-only sim. */
+int apk_sim_agn_feedback_power_of(const apk_sim *sim, double accretion_rate, double *power, double *mass_rate);
+/* this rank's active list: copies min(n, size) entries of 7 ints (local block, lo[3], hi[3]) into out, *size = the
+ * number of entries.  Works on a host-only sim. */
+int apk_sim_agn_triggering_active_list(const apk_sim *sim, int *out, int n, int *size);
+/* One reduction (for COLD_GAS with the removal) on the current state with this dt, the sum over ranks, and the state
+ * above updated: what a cycle does before the Bondi removal.  A collective.  For tests. */
+int apk_sim_agn_triggering_reduce(apk_sim *sim, double dt);
+/* RemoveBondiAccretedGas on the current state with the stored total_mass and accretion rate.  For tests. */
+int apk_sim_agn_triggering_remove_bondi(apk_sim *sim, double dt);
 
 /* ---- tracer particles (<tracers>, src/tracers/tracers.cpp; csrc/host/tracers.cpp) ---------------------------------
  * Keys (tracers.cpp:43-93, 102-118): enabled (default false), initial_seed_method = none | random_per_block | user,

@@ -1,0 +1,106 @@
+"""numpy restatement of the cluster problem's AGN triggering, in the operation order of the code under test: the
+accretion rate of the three modes and the time-step rule from reduced quantities, the mask of the accretion sphere, the
+Bondi sums and the cold mass, AddDensityToConsAtFixedVelTemp with the ConsToPrim that follows it, and the active list's
+index ranges.  The yardstick of tests/test_cluster_triggering_host.py and tests/test_gpu_cluster_triggering.py, written
+from the formulas in the manner of feedback_reference.py (which restates ConsToPrim): host scalars go through `math`
+(the libm of the C++), per-cell arithmetic is numpy float64, nothing fused or reassociated; squares of positions are
+products.  Every per-cell operation is a product, quotient, sum or square root: stored values are compared bit for bit,
+sums within a bound on the order of summation."""
+import math
+import sys
+from types import SimpleNamespace
+
+import numpy as np
+
+import feedback_reference as FB
+
+F = np.float64
+EPS = np.finfo(np.float64).eps
+DBL_MAX = sys.float_info.max
+NONE, COLD_GAS, BOOSTED_BONDI, BOOTH_SCHAYE = 0, 1, 2, 3
+
+
+def model(mode, **kw):
+    m = SimpleNamespace(mode=mode, accretion_radius=0.0, cold_temp_thresh=0.0, cold_t_acc=0.0, bondi_alpha=0.0, bondi_M_smbh=0.0,
+                        bondi_n0=0.0, bondi_beta=0.0, accretion_cfl=0.1, mean_molecular_mass=0.0, gravitational_constant=0.0)
+    m.__dict__.update(kw)
+    return m
+
+
+def accretion_rate(m, q):
+    """GetAccretionRate: q = cold_mass, or (total_mass, mass-weighted density, velocity, sound speed sums)"""
+    if m.mode == COLD_GAS:
+        return float(q) / m.cold_t_acc
+    if m.mode in (BOOSTED_BONDI, BOOTH_SCHAYE):
+        total, mwd, mwv, mwc = (float(x) for x in q)
+        rho, v, cs = mwd / total, mwv / total, mwc / total
+        if m.mode == BOOSTED_BONDI:
+            alpha = m.bondi_alpha
+        else:
+            n = rho / m.mean_molecular_mass
+            alpha = 1 if n <= m.bondi_n0 else math.pow(n / m.bondi_n0, m.bondi_beta)
+        return (alpha * 2 * math.pi * math.pow(m.gravitational_constant, 2) * math.pow(m.bondi_M_smbh, 2) * rho /
+                math.pow(math.pow(v, 2) + math.pow(cs, 2), 3. / 2.))
+    return 0.0
+
+
+def estimate_timestep(m, q):
+    if m.mode == COLD_GAS:
+        return m.accretion_cfl * m.cold_t_acc
+    if m.mode in (BOOSTED_BONDI, BOOTH_SCHAYE):
+        if float(q[0]) == 0:
+            return DBL_MAX
+        return m.accretion_cfl * float(q[0]) / accretion_rate(m, q)
+    return DBL_MAX
+
+
+def sphere(x1, x2, x3, radius):
+    """[k][j][i] mask of the cells with r2 = x*x + y*y + z*z < R*R (strict)"""
+    X, Y, Z = FB.grid(x1, x2, x3)
+    return X * X + Y * Y + Z * Z < F(radius) * F(radius)
+
+
+def index_range(x, radius):
+    """the active list's [lo, hi) of one direction: the cells with |x| < radius, one more per side, clipped"""
+    inside = np.nonzero(np.abs(x) < radius)[0]
+    if len(inside) == 0:
+        return 0, 0
+    return max(int(inside[0]) - 1, 0), min(int(inside[-1]) + 2, len(x))
+
+
+def bondi_terms(w, mask, vol, gamma):
+    """the four per-cell terms of ReduceBondiTriggeringQuantities on the masked cells, [4][n] in index order"""
+    rho, v1, v2, v3, p = (w[n][mask] for n in range(5))
+    m = rho * F(vol)
+    return np.array([m, m * rho, m * np.sqrt(v1 * v1 + v2 * v2 + v3 * v3), m * np.sqrt(F(gamma) * p / rho)])
+
+
+def temperature(w, mm_by_kb):
+    return F(mm_by_kb) * w[4] / w[0]
+
+
+def cold_mask(w, mask, mm_by_kb, thresh):
+    return mask & (temperature(w, mm_by_kb) <= F(thresh))
+
+
+def add_density_fixed_vel_temp(u, w, mask, density, gamma):
+    """AddDensityToConsAtFixedVelTemp with `density` [k][j][i] on the masked cells, then ConsToPrim there; (u, w) new"""
+    u, w = np.array(u, dtype=F), np.array(w, dtype=F)
+    with np.errstate(all="ignore"):
+        add = [density, density * w[1], density * w[2], density * w[3],
+               density * (0.5 * (w[1] * w[1] + w[2] * w[2] + w[3] * w[3]) + 1 / (F(gamma) - 1.0) * w[4] / w[0])]
+        un = u.copy()
+        for n in range(5):
+            un[n] = u[n] + add[n]
+        nh = 9 if u.shape[0] >= 9 else 5
+        wn = w.copy()
+        wn[:nh] = FB.cons_to_prim(un[:nh], gamma)
+    return np.where(mask[None], un, u), np.where(mask[None], wn, w)
+
+
+def cold_delta(w, cold_t_acc, dt):
+    return -w[0] / F(cold_t_acc) * F(dt)
+
+
+def bondi_delta(w, total_mass, rate, dt):
+    return -w[0] / F(total_mass) * F(rate) * F(dt)

@@ -1,7 +1,8 @@
 // feedback_check.cpp -- stand-alone host program for the cluster problem's AGN feedback model
 // (csrc/host/feedback_model.cpp): the derived jet numbers in the four ways of giving velocity and temperature, the per-stage
 // numbers, the power scaling with its two failures, the requirement messages, and one 8^3 block's initial tower field for
-// both potentials with its discrete divergence.  No GPU, no Python; meant to be compiled with sanitizers:
+// both potentials with its discrete divergence; AGN triggering's accretion rate in its three modes, its time-step rule, power
+// and mass rate with accretion, and the active list's index range.  No GPU, no Python; meant to be compiled with sanitizers:
 //   c++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I include \
 //       tools/cluster/feedback_check.cpp athenapk_amd/csrc/host/feedback_model.cpp -o /tmp/feedback_check && /tmp/feedback_check
 #include <cmath>
@@ -132,6 +133,59 @@ int main() {
     double b[3];
     tower_initial_field_block(t, jet_coords_at(0, 0, 0, 0), 1.0, x3, 1, x3, 1, x3, 1, d, b);
   });
-  std::printf("failures raised: %d of 9\n", caught);
-  return (ok && caught == 9) ? 0 : 1;
+
+  // AGN triggering: the suite's uniform gas in the deck's units, a sphere of 20 kpc
+  {
+    const double L = 3.0856775809623245e+24, M = 1.98841586e+47, T = 3.15576e+16;
+    const double mu = 1 / (0.25 * 3. / 4. + (1 - 0.25) * 2);
+    AgnTriggeringModel t;
+    t.accretion_radius = 0.02, t.cold_temp_thresh = 7198.523584993223, t.cold_t_acc = 0.1, t.bondi_alpha = 100, t.bondi_beta = 2;
+    t.bondi_M_smbh = 1e-6, t.mean_molecular_mass = mu * (1.660538921e-24 / M);
+    t.mean_molecular_mass_by_kb = t.mean_molecular_mass / (1.3806488e-16 / (M * L * L / (T * T)));
+    t.gravitational_constant = 6.67408e-08 / (std::pow(L, 3) / (M * std::pow(T, 2)));
+    const double rho = 14775.575892787225, vol = 4. / 3. * M_PI * std::pow(0.02, 3), v = 8.97e-4, cs = 1.32e-2;
+    t.bondi_n0 = 0.05 * rho / t.mean_molecular_mass;
+    AgnTriggeringModel::Reduced q;
+    q.cold_mass = q.total_mass = rho * vol;
+    q.mass_weighted_density = q.total_mass * rho, q.mass_weighted_velocity = q.total_mass * v, q.mass_weighted_cs = q.total_mass * cs;
+    const AgnTriggeringModel::Reduced none;
+    double rate[4], dt[4], dt0[4];
+    for (int mode : {APK_TRIG_NONE, APK_TRIG_COLD_GAS, APK_TRIG_BOOSTED_BONDI, APK_TRIG_BOOTH_SCHAYE}) {
+      t.mode = mode;
+      rate[mode] = t.accretion_rate(q), dt[mode] = t.estimate_timestep(q), dt0[mode] = t.estimate_timestep(none);
+      std::printf("triggering mode %d: rate %.17g, dt %.6e, dt before the first reduction %.6e\n", mode, rate[mode], dt[mode], dt0[mode]);
+    }
+    const double huge = std::numeric_limits<double>::max();
+    ok &= rate[APK_TRIG_NONE] == 0 && dt[APK_TRIG_NONE] == huge && rate[APK_TRIG_COLD_GAS] == q.cold_mass / 0.1;
+    ok &= dt[APK_TRIG_COLD_GAS] == 0.1 * 0.1 && dt0[APK_TRIG_COLD_GAS] == 0.1 * 0.1;
+    ok &= dt0[APK_TRIG_BOOSTED_BONDI] == huge && dt0[APK_TRIG_BOOTH_SCHAYE] == huge;
+    ok &= std::fabs(rate[APK_TRIG_BOOTH_SCHAYE] / (rate[APK_TRIG_BOOSTED_BONDI] / 100 * 400) - 1) < 1e-13;  // (n / n0)^2 = 400
+    ok &= std::fabs(dt[APK_TRIG_BOOSTED_BONDI] - 0.1 * q.total_mass / rate[APK_TRIG_BOOSTED_BONDI]) <= 1e-15 * dt[APK_TRIG_BOOSTED_BONDI];
+    t.mode = APK_TRIG_BOOTH_SCHAYE, t.bondi_n0 = q.mass_weighted_density / q.total_mass / t.mean_molecular_mass;  // n == n0: alpha = 1
+    const double at_n0 = t.accretion_rate(q);
+    t.mode = APK_TRIG_BOOSTED_BONDI, t.bondi_alpha = 1;
+    ok &= at_n0 == t.accretion_rate(q);
+    // power and mass rate with that accretion
+    AgnFeedbackModel fb = agn_feedback_model(deck_input());
+    const double p0 = fb.power(), m0 = fb.mass_rate();
+    fb.accretion_rate = rate[APK_TRIG_COLD_GAS];
+    const double c2 = std::pow(fb.in.speed_of_light, 2);
+    std::printf("power %.17g -> %.17g, mass rate %.17g -> %.17g\n", p0, fb.power(), m0, fb.mass_rate());
+    ok &= p0 == fb.in.fixed_power && fb.power() == fb.in.fixed_power + fb.accretion_rate * 1e-3 * c2;
+    ok &= fb.mass_rate() == fb.accretion_rate * (1 - 1e-3) + fb.in.fixed_power / (1e-3 * c2);
+    // the active list's range: 12 extended cells of a block whose interior starts at the origin, radius 2.4 cells
+    double xc[12];
+    for (int i = 0; i < 12; ++i) xc[i] = ((double)(i - 2) + 0.5) * 0.0125;
+    int lo = -1, hi = -1;
+    triggering_index_range(xc, 12, 0.03, &lo, &hi);
+    ok &= lo == 0 && hi == 5;  // cells 0 .. 3 lie inside, one more on the upper side, clipped below
+    triggering_index_range(xc + 6, 6, 0.03, &lo, &hi);
+    ok &= lo >= hi;
+    triggering_index_range(xc, 12, 0.03, &lo, &hi);
+    std::printf("index range of the block at the origin: [%d, %d)\n", lo, hi);
+  }
+  caught += raised("triggering mode", "Unrecognized AGNTriggeringMode", [] { (void)parse_agn_triggering_mode("EDDINGTON"); });
+  ok &= parse_agn_triggering_mode("BOOTH_SCHAYE") == APK_TRIG_BOOTH_SCHAYE && parse_agn_triggering_mode("NONE") == APK_TRIG_NONE;
+  std::printf("failures raised: %d of 10\n", caught);
+  return (ok && caught == 10) ? 0 : 1;
 }
