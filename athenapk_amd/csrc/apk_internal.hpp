@@ -133,13 +133,17 @@ inline int set_err(apk_ctx *ctx, int code, const char *what, hipError_t e = hipS
   return code;
 }
 
-// at least n doubles in ctx->d_partial (contents are not kept)
-inline int ensure_partial_doubles(apk_ctx *ctx, size_t n) {
+// at least n doubles in ctx->d_partial (contents are not kept).  A failure is APK_ERR_DEVICE with the words "partial
+// buffer", or with hip_words the failed call and HIP's name for the error, as APK_HIP_TRY words it
+inline int ensure_partial_doubles(apk_ctx *ctx, size_t n, bool hip_words = false) {
   if (ctx->partial_cap >= n) return APK_OK;
   if (ctx->d_partial) (void)hipFree(ctx->d_partial);
   ctx->d_partial = nullptr;
   ctx->partial_cap = 0;
-  if (hipMalloc(&ctx->d_partial, n * sizeof(double)) != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "partial buffer");
+  const hipError_t e = hipMalloc(&ctx->d_partial, n * sizeof(double));
+  if (e != hipSuccess)
+    return hip_words ? set_err(ctx, APK_ERR_DEVICE, "hipMalloc(&ctx->d_partial, n * sizeof(double))", e)
+                     : set_err(ctx, APK_ERR_DEVICE, "partial buffer");
   ctx->partial_cap = n;
   return APK_OK;
 }

@@ -99,16 +99,6 @@ bool same_shape(const apk_pack *a, const apk_pack *b) {
          x.nk == y.nk && x.ng == y.ng && x.sj == y.sj && x.sk == y.sk && x.sn == y.sn;
 }
 
-int ensure_partial(apk_ctx *ctx, size_t n) {
-  if (ctx->partial_cap >= n) return APK_OK;
-  if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-  ctx->d_partial = nullptr;
-  ctx->partial_cap = 0;
-  APK_HIP_TRY(ctx, hipMalloc(&ctx->d_partial, n * sizeof(double)));
-  ctx->partial_cap = n;
-  return APK_OK;
-}
-
 int ensure_mark(apk_ctx *ctx, size_t n) {
   if (ctx->mark_cap >= n) return APK_OK;
   if (ctx->d_mark) (void)hipFree(ctx->d_mark);
@@ -822,7 +812,7 @@ int apk_history(apk_ctx *ctx, const apk_pack *md, int fluid, double *out8, apk_s
   hipStream_t s = as_stream(stream);
   int nwg = 0;
   launch_history(md->view, fluid, nullptr, &nwg, nullptr, s);
-  int rc = ensure_partial(ctx, (size_t)nwg * 8 + 8);
+  int rc = ensure_partial_doubles(ctx, (size_t)nwg * 8 + 8, true);
   if (rc != APK_OK) return rc;
   double *d_out = ctx->d_partial + (size_t)nwg * 8;
   rc = launch_history(md->view, fluid, ctx->d_partial, &nwg, d_out, s);

@@ -477,30 +477,44 @@ bool cluster_needs_block_origins(const apk_sim *s) {
          (s->cluster.enabled && (s->agn_opt.configured || s->tower.potential != APK_TOWER_UNDEFINED));
 }
 
-// MagneticTowerReducePowerContribs with its reduction over ranks (magnetic_tower.cpp:301-317, hydro_driver.cpp:409-449):
-// every local block's pair into its slot of a zeroed array over all blocks, one sum over ranks, the slots added in global
-// block order.  Adding zeros is exact: the two sums do not depend on the distribution of the blocks.
-int cluster_tower_contribs(apk_sim *s, double time, double out[2]) {
+// The sum over all blocks of all ranks of nq per-block sums, out[nq]: d_local holds this rank's, nq per local block
+// (nullptr: zeros, nothing is read back).  Every local block's sums go into its slot of a zeroed array over all blocks,
+// one allreduce_sum, the slots added in global block order.  Adding zeros is exact: the result does not depend on the
+// distribution of the blocks, which is what makes two ranks reproduce one bit for bit.
+static int sum_blocks_in_global_order(apk_sim *s, const double *d_local, int nq, double *out) {
   const Mesh &m = s->mesh;
-  const int nlb = (int)m.local_gids.size();
+  const size_t nlb = m.local_gids.size();
+  std::vector<double> local(nq * nlb, 0.0), all((size_t)nq * m.nblocks_total, 0.0);
+  if (d_local) {
+    SIM_HIP(s, hipMemcpyAsync(local.data(), d_local, sizeof(double) * local.size(), hipMemcpyDeviceToHost, hs(s)));
+    SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  }
+  for (size_t lb = 0; lb < nlb; ++lb)
+    for (int q = 0; q < nq; ++q) all[(size_t)nq * m.local_gids[lb] + q] = local[nq * lb + q];
+  if (s->have_comm && s->nranks > 1 && s->comm.allreduce_sum(s->comm.user, all.data(), (int)all.size()) != 0)
+    return fail(s, APK_ERR_DEVICE, "allreduce_sum failed");
+  for (int q = 0; q < nq; ++q) out[q] = 0.0;
+  for (size_t g = 0; g < (size_t)m.nblocks_total; ++g)
+    for (int q = 0; q < nq; ++q) out[q] += all[nq * g + q];
+  return APK_OK;
+}
+
+static AgnTriggeringModel::Reduced reduced_of(const AgnTriggeringModel &t, const double *q) {
+  AgnTriggeringModel::Reduced r;
+  if (t.mode == APK_TRIG_COLD_GAS) r.cold_mass = q[0];
+  else r.total_mass = q[0], r.mass_weighted_density = q[1], r.mass_weighted_velocity = q[2], r.mass_weighted_cs = q[3];
+  return r;
+}
+
+// MagneticTowerReducePowerContribs with its reduction over ranks (magnetic_tower.cpp:301-317, hydro_driver.cpp:409-449)
+int cluster_tower_contribs(apk_sim *s, double time, double out[2]) {
+  const int nlb = (int)s->mesh.local_gids.size();
   if (!s->d_block_xmin) return fail(s, APK_ERR_INVALID, "magnetic_tower_contribs needs problem_id = cluster with a magnetic tower");
   SIM_TRY(s, sync_ghosts(s));  // (materialises the stored primitives when the cycle kept them out of memory)
   if (!s->d_tower_contribs) SIM_TRY(s, dev_alloc(s, "tower_contribs", sizeof(double) * 2 * (size_t)std::max(nlb, 1), &s->d_tower_contribs));
   const apk_jet_coords jet = jet_at(s, time);
   SIM_TRY(s, apk_magnetic_tower_power_contribs(s->ctx, s->mu0(), &s->tower, &jet, s->d_block_xmin, s->d_tower_contribs, s->stream));
-  std::vector<double> local(2 * (size_t)nlb), all(2 * (size_t)m.nblocks_total, 0.0);
-  SIM_HIP(s, hipMemcpyAsync(local.data(), s->d_tower_contribs, sizeof(double) * local.size(), hipMemcpyDeviceToHost, hs(s)));
-  SIM_HIP(s, hipStreamSynchronize(hs(s)));
-  for (int lb = 0; lb < nlb; ++lb)
-    for (int q = 0; q < 2; ++q) all[2 * (size_t)m.local_gids[lb] + q] = local[2 * (size_t)lb + q];
-  if (s->have_comm && s->nranks > 1 && s->comm.allreduce_sum(s->comm.user, all.data(), (int)all.size()) != 0)
-    return fail(s, APK_ERR_DEVICE, "allreduce_sum failed");
-  out[0] = out[1] = 0.0;
-  for (size_t g = 0; g < (size_t)m.nblocks_total; ++g) {
-    out[0] += all[2 * g];
-    out[1] += all[2 * g + 1];
-  }
-  return APK_OK;
+  return sum_blocks_in_global_order(s, s->d_tower_contribs, 2, out);
 }
 
 // the feedback part of ClusterUnsplitSrcTerm (cluster.cpp:76-80): AGNFeedback::FeedbackSrcTerm -- the thermal and kinetic
@@ -534,36 +548,24 @@ int cluster_feedback_sources(apk_sim *s, double beta_dt) {
 }
 
 // AGN triggering of one cycle (hydro_driver.cpp:360-394): AGNTriggeringResetTriggering, ReduceTriggering over this rank's
-// active list (COLD_GAS removes in the same launch), the sum over ranks -- every local block's sums into its slot of a
-// zeroed array over all blocks, one allreduce_sum, the slots added in global block order, as cluster_tower_contribs: the
-// result does not depend on the distribution of the blocks -- and what follows from the sums.
+// active list (COLD_GAS removes in the same launch), the sum over blocks and ranks (sum_blocks_in_global_order), and what
+// follows from the sums.
 static int triggering_reduce(apk_sim *s, double dt) {
-  const Mesh &m = s->mesh;
-  const int nlb = (int)m.local_gids.size();
   const AgnTriggeringModel &t = s->trig;
   SIM_TRY(s, sync_ghosts(s));  // (ghost cells of the boxes are read and written; materialises the stored primitives)
-  std::vector<double> local(4 * (size_t)nlb, 0.0), all(4 * (size_t)m.nblocks_total, 0.0);
-  if (!s->trig_boxes.empty()) {  // (a rank with no block in the list launches nothing)
+  const bool listed = !s->trig_boxes.empty();  // (a rank with no block in the list launches nothing and contributes zeros)
+  if (listed) {
     apk_agn_triggering_cfg cfg{};
     cfg.mode = t.mode, cfg.remove_accreted_mass = t.remove_accreted_mass ? 1 : 0;
     cfg.accretion_radius = t.accretion_radius, cfg.cold_temp_thresh = t.cold_temp_thresh, cfg.cold_t_acc = t.cold_t_acc;
     cfg.mean_molecular_mass_by_kb = t.mean_molecular_mass_by_kb;
     SIM_TRY(s, apk_agn_triggering_reduce(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, &cfg, s->d_trig_boxes, (int)s->trig_boxes.size(),
                                          s->trig_max_box_cells, s->d_block_xmin, dt, s->d_trig_sums, s->stream));
-    SIM_HIP(s, hipMemcpyAsync(local.data(), s->d_trig_sums, sizeof(double) * local.size(), hipMemcpyDeviceToHost, hs(s)));
-    SIM_HIP(s, hipStreamSynchronize(hs(s)));
   }
-  for (int lb = 0; lb < nlb; ++lb)
-    for (int q = 0; q < 4; ++q) all[4 * (size_t)m.local_gids[lb] + q] = local[4 * (size_t)lb + q];
-  if (s->have_comm && s->nranks > 1 && s->comm.allreduce_sum(s->comm.user, all.data(), (int)all.size()) != 0)
-    return fail(s, APK_ERR_DEVICE, "allreduce_sum failed");
-  double sum[4] = {0.0, 0.0, 0.0, 0.0};
-  for (size_t g = 0; g < (size_t)m.nblocks_total; ++g)
-    for (int q = 0; q < 4; ++q) sum[q] += all[4 * g + q];
+  double sum[4];
+  SIM_TRY(s, sum_blocks_in_global_order(s, listed ? s->d_trig_sums : nullptr, 4, sum));
   AgnTriggeringModel::Reduced &r = s->trig_q;
-  r = AgnTriggeringModel::Reduced{};
-  if (t.mode == APK_TRIG_COLD_GAS) r.cold_mass = sum[0];
-  else r.total_mass = sum[0], r.mass_weighted_density = sum[1], r.mass_weighted_velocity = sum[2], r.mass_weighted_cs = sum[3];
+  r = reduced_of(t, sum);
   s->trig_time = s->time, s->trig_dt = dt;
   if (t.mode != APK_TRIG_COLD_GAS && r.total_mass == 0) {
     s->trig_rate = s->agn.accretion_rate = 0.0;
@@ -811,13 +813,6 @@ int apk_sim_agn_triggering_state(const apk_sim *s, apk_agn_triggering_state *st)
   st->dt_limit = s->trig.estimate_timestep(r);
   st->time = s->trig_time, st->dt = s->trig_dt;
   return APK_OK;
-}
-
-static AgnTriggeringModel::Reduced reduced_of(const AgnTriggeringModel &t, const double *q) {
-  AgnTriggeringModel::Reduced r;
-  if (t.mode == APK_TRIG_COLD_GAS) r.cold_mass = q[0];
-  else r.total_mass = q[0], r.mass_weighted_density = q[1], r.mass_weighted_velocity = q[2], r.mass_weighted_cs = q[3];
-  return r;
 }
 
 int apk_sim_agn_triggering_accretion_rate(const apk_sim *s, const double *q, double *rate) {

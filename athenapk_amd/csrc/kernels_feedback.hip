@@ -7,7 +7,9 @@
 // and the C-ABI entries of include/apk_amd.h (apk_agn_feedback_src, apk_magnetic_tower_src,
 // apk_magnetic_tower_power_contribs).
 //
-// Kernel structure.  One lane per interior cell with cell_of / centre of cell_centre.hpp, as in kernels_gravity.hip.
+// Kernel structure.  One lane per interior cell.  The view of a cell is cell_centre.hpp's, shared with kernels_gravity.hip
+// and kernels_triggering.hip: cell_of names the lane's cell, cell_centre / cell_xyz give its centre (the host's number),
+// pack_problem says what an entry asks of its pack.
 // Which channels act (thermal_feedback > 0, thermal_density > 0, jet_density > 0, density_to_add > 0, the potential) are
 // kernel arguments: uniform over the launch, scalar compares.  Lane-dependent are the sphere, the cylinders and the
 // ceilings.  Ceilings that are +inf are not compiled into the launch (template flag CEIL, as LEAN in cons_to_prim_core).
@@ -21,7 +23,7 @@
 //
 // apk_magnetic_tower_src.  The reference fills a three-component potential one ghost layer deep and differences it in a
 // second kernel (48 B per cell written and read again, plus the array).  Here there is no potential array: a cell
-// evaluates the potential at its six neighbours' centres, centre() of the neighbour's index, so in the parity build every
+// evaluates the potential at its six neighbours' centres, cell_centre of the neighbour's index, so in the parity build every
 // value is the number the array would have held and the curl (/ dx / 2.0, the reference's association) is the same.
 // Six exponentials per cell and one more with mass injection.  Bytes per cell: prim B read (24 B), cons B, E and rho read
 // and written (80 B): 104 B.  An LDS tile (one evaluation per cell plus halo) was not tried.
@@ -29,7 +31,9 @@
 // apk_magnetic_tower_power_contribs.  Per block P = min(64, ceil(cells / 4096)) workgroups, each over a fixed contiguous
 // share of the block's cells: a lane adds its cells in index order, the workgroup reduces through a fixed LDS tree, a
 // second small kernel adds the block's P partial pairs in order.  No atomics: the pair of a block depends on nothing but
-// the block.  Bytes per cell: prim B read, 24 B; one exponential.
+// the block.  The order is the one block_sum.hpp defines for the triggering reductions; this pair of kernels keeps its own
+// statement of it and of the cell centre (see the note above tower_contribs_kernel).  Bytes per cell: prim B read, 24 B;
+// one exponential.
 //
 // Measured (product build, GLM-MHD packs, one MI355X, device events, each next to a device copy of the kernel's bytes timed
 // in the same run; profiles/feedback_cost.jsonl, tools/feedback_cost.py), 8 x 128^3 | one 64^3 block:
@@ -62,11 +66,8 @@ __global__ void __launch_bounds__(256) agn_feedback_kernel(PackView pv, apk_eos 
   int64_t off;
   if (!cell_of(pv, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b, i, j, k, off)) return;
   const apk_block_desc &bd = pv.blocks[b];
-  const double *corner = block_xmin + 3 * (int64_t)b;
-  const double *mesh = block_xmin + 3 * (int64_t)pv.nblocks;
-  const double x = centre(corner[0], mesh[0], bd.dx[0], i);
-  const double y = centre(corner[1], mesh[1], bd.dx[1], j);
-  const double z = centre(corner[2], mesh[2], bd.dx[2], k);
+  double x, y, z;
+  cell_xyz(bd, block_xmin, b, pv.nblocks, i, j, k, x, y, z);
   const int64_t sn = pv.sn;
   double *__restrict__ wp = bd.prim + off;
   double *__restrict__ up = bd.cons + off;
@@ -148,12 +149,11 @@ __global__ void __launch_bounds__(256) magnetic_tower_kernel(PackView pv, apk_ma
   int64_t off;
   if (!cell_of(pv, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b, i, j, k, off)) return;
   const apk_block_desc &bd = pv.blocks[b];
-  const double *corner = block_xmin + 3 * (int64_t)b;
-  const double *mesh = block_xmin + 3 * (int64_t)pv.nblocks;
-  const double dx1 = bd.dx[0], dx2 = bd.dx[1], dx3 = bd.dx[2];
-  const double x = centre(corner[0], mesh[0], dx1, i), xm = centre(corner[0], mesh[0], dx1, i - 1), xp = centre(corner[0], mesh[0], dx1, i + 1);
-  const double y = centre(corner[1], mesh[1], dx2, j), ym = centre(corner[1], mesh[1], dx2, j - 1), yp = centre(corner[1], mesh[1], dx2, j + 1);
-  const double z = centre(corner[2], mesh[2], dx3, k), zm = centre(corner[2], mesh[2], dx3, k - 1), zp = centre(corner[2], mesh[2], dx3, k + 1);
+  const double dx1 = cell_width(bd, 0), dx2 = cell_width(bd, 1), dx3 = cell_width(bd, 2);
+  const auto at = [&](int d, int n) { return cell_centre(bd, block_xmin, b, pv.nblocks, d, n); };
+  const double x = at(0, i), xm = at(0, i - 1), xp = at(0, i + 1);
+  const double y = at(1, j), ym = at(1, j - 1), yp = at(1, j + 1);
+  const double z = at(2, k), zm = at(2, k - 1), zp = at(2, k + 1);
   const int64_t sn = pv.sn;
   const double *__restrict__ w = bd.prim + off;
   double *__restrict__ u = bd.cons + off;
@@ -179,6 +179,11 @@ __global__ void __launch_bounds__(256) magnetic_tower_kernel(PackView pv, apk_ma
   u[IDN * sn] += cell_delta_rho;
 }
 
+// The power contributions keep their own statement of the block sum of block_sum.hpp and of the cell centre (centre() on
+// block_xmin's rows, as cell_xyz does), in the same order of additions: written with the shared helpers the kernel
+// compiles to other code than it had (same instruction count within two, another register allocation), and a timing on one
+// 64^3 block (18.6 us) does not repeat from process to process within the spread of its windows, so it cannot show the
+// two equal.
 constexpr int kContribCellsPerGroup = 4096, kContribMaxGroups = 64;
 inline int contrib_groups(int64_t ncell_block) {
   const int64_t p = (ncell_block + kContribCellsPerGroup - 1) / kContribCellsPerGroup;
@@ -244,15 +249,6 @@ bool tower_ok(const apk_magnetic_tower_cfg &t) {
   return t.l_scale > 0.0 && t.l_mass_scale >= 0.0;
 }
 
-const char *pack_problem(const apk_pack *md, bool need_mhd) {
-  const PackView &v = md->view;
-  if (need_mhd ? v.nhydro != 9 : (v.nhydro != 5 && v.nhydro != 9)) return need_mhd ? "the pack is not GLM-MHD" : "the pack is neither hydro nor GLM-MHD";
-  if (v.ndim != 3) return "the pack is not three-dimensional";
-  for (int b = 0; b < v.nblocks; ++b)
-    if (!md->h_blocks[b].prim || !md->h_blocks[b].cons) return "the pack needs cons and prim";
-  return nullptr;
-}
-
 }  // namespace
 }  // namespace apk
 
@@ -263,10 +259,10 @@ extern "C" {
 int apk_agn_feedback_src(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_agn_feedback_cfg *cfg,
                          const apk_jet_coords *jet, const double *block_xmin, apk_stream_t stream) {
   if (!ctx || !md || !eos || !cfg || !jet || !block_xmin) return set_err(ctx, APK_ERR_INVALID, "apk_agn_feedback_src: bad argument");
-  if (const char *why = pack_problem(md, false)) return set_err(ctx, APK_ERR_INVALID, (std::string("apk_agn_feedback_src: ") + why).c_str());
+  const char *why = pack_problem(md, PACK_3D | PACK_STORED);
+  if (!why) why = pack_problem(md, PACK_FLUID, fluid);  // (asked last here)
+  if (why) return pack_refused(ctx, "apk_agn_feedback_src", why);
   const PackView &v = md->view;
-  if ((fluid == APK_FLUID_GLMMHD) != (v.nhydro == 9) || (fluid != APK_FLUID_EULER && fluid != APK_FLUID_GLMMHD))
-    return set_err(ctx, APK_ERR_INVALID, "apk_agn_feedback_src: fluid does not match the pack");
   const int64_t ncell = (int64_t)v.nx1 * v.nx2 * v.nx3 * v.nblocks;
   if (ncell == 0) return APK_OK;
   // (nothing acts: the reference's loop would still run its closing ConsToPrim; so does this)
@@ -289,7 +285,7 @@ int apk_magnetic_tower_src(apk_ctx *ctx, const apk_pack *md, const apk_magnetic_
                            const double *block_xmin, double field_to_add, double mass_to_add, apk_stream_t stream) {
   if (!ctx || !md || !tower || !jet || !block_xmin) return set_err(ctx, APK_ERR_INVALID, "apk_magnetic_tower_src: bad argument");
   if (field_to_add == 0 && mass_to_add == 0) return APK_OK;  // (magnetic_tower.cpp:36-38)
-  if (const char *why = pack_problem(md, true)) return set_err(ctx, APK_ERR_INVALID, (std::string("apk_magnetic_tower_src: ") + why).c_str());
+  if (const char *why = pack_problem(md, PACK_MHD | PACK_3D | PACK_STORED)) return pack_refused(ctx, "apk_magnetic_tower_src", why);
   if (!tower_ok(*tower))
     return set_err(ctx, APK_ERR_INVALID, "apk_magnetic_tower_src: Unknown magnetic tower potential, or a length scale that is not positive");
   if (!(mass_to_add == 0.0 || tower->l_mass_scale > 0.0))
@@ -313,8 +309,7 @@ int apk_magnetic_tower_power_contribs(apk_ctx *ctx, const apk_pack *md, const ap
                                       apk_stream_t stream) {
   if (!ctx || !md || !tower || !jet || !block_xmin || !contribs)
     return set_err(ctx, APK_ERR_INVALID, "apk_magnetic_tower_power_contribs: bad argument");
-  if (const char *why = pack_problem(md, true))
-    return set_err(ctx, APK_ERR_INVALID, (std::string("apk_magnetic_tower_power_contribs: ") + why).c_str());
+  if (const char *why = pack_problem(md, PACK_MHD | PACK_3D | PACK_STORED)) return pack_refused(ctx, "apk_magnetic_tower_power_contribs", why);
   if (!tower_ok(*tower))
     return set_err(ctx, APK_ERR_INVALID, "apk_magnetic_tower_power_contribs: Unknown magnetic tower potential, or a length scale that is not positive");
   const PackView &v = md->view;

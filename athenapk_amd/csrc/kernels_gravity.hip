@@ -17,7 +17,8 @@
 // stream rate of DESIGN.md section 7.0).  Not measured: GLM-MHD packs (same bytes, a longer variable stride).
 //
 // Cell centres.  The centre is the number the problem generator used on the host, xc() of host/sim_pgen.cpp, rebuilt
-// from the blocks' lower interior corners: cell_of / centre of cell_centre.hpp, shared with kernels_feedback.hip.
+// from the blocks' lower interior corners: cell_of and cell_xyz of cell_centre.hpp, the view of a cell that
+// kernels_feedback.hip and kernels_triggering.hip share; pack_problem of the same header is the entry's pack check.
 //
 // Build forms.  The parity build (APK_FP_STRICT, -ffp-contract=off) keeps the reference's association order with IEEE
 // divides and roots: it agrees with a numpy restatement operation for operation, except for log, the one step that is
@@ -53,11 +54,8 @@ __global__ void __launch_bounds__(256) gravity_src_kernel(PackView pv, apk_clust
   int64_t off;
   if (!cell_of(pv, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b, i, j, k, off)) return;
   const apk_block_desc &bd = pv.blocks[b];
-  const double *corner = block_xmin + 3 * (int64_t)b;
-  const double *mesh = block_xmin + 3 * (int64_t)pv.nblocks;
-  const double x = centre(corner[0], mesh[0], bd.dx[0], i);
-  const double y = centre(corner[1], mesh[1], bd.dx[1], j);
-  const double z = centre(corner[2], mesh[2], bd.dx[2], k);
+  double x, y, z;
+  cell_xyz(bd, block_xmin, b, pv.nblocks, i, j, k, x, y, z);
   const int64_t sn = pv.sn;
   const double *__restrict__ w = bd.prim + off;
   double *__restrict__ u = bd.cons + off;
@@ -97,12 +95,11 @@ int apk_gravity_src(apk_ctx *ctx, const apk_pack *md, const apk_cluster_gravity 
                     double beta_dt, apk_stream_t stream) {
   if (!ctx || !md || !gravity || !block_xmin) return set_err(ctx, APK_ERR_INVALID, "apk_gravity_src: bad argument");
   if (!gravity_ok(*gravity)) return set_err(ctx, APK_ERR_INVALID, "apk_gravity_src: Unknown BCG type or a scale radius that is not positive");
+  if (const char *why = pack_problem(md, 0)) return pack_refused(ctx, "apk_gravity_src", why);
   const PackView &v = md->view;
-  if (v.nhydro != 5 && v.nhydro != 9) return set_err(ctx, APK_ERR_INVALID, "apk_gravity_src: the pack is neither hydro nor GLM-MHD");
   const int64_t ncell = (int64_t)v.nx1 * v.nx2 * v.nx3 * v.nblocks;
-  if (ncell == 0) return APK_OK;
-  for (int b = 0; b < v.nblocks; ++b)
-    if (!md->h_blocks[b].prim || !md->h_blocks[b].cons) return set_err(ctx, APK_ERR_INVALID, "apk_gravity_src: the pack needs cons and prim");
+  if (ncell == 0) return APK_OK;  // (an empty pack is not asked for its arrays, nor any pack for three dimensions)
+  if (const char *why = pack_problem(md, PACK_STORED)) return pack_refused(ctx, "apk_gravity_src", why);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ScopedTiming span(ctx, APK_T_GRAVITY, s);
   hipLaunchKernelGGL(gravity_src_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, s, v, *gravity, block_xmin, beta_dt);

@@ -9,14 +9,17 @@
 // the host hands over an active list (apk_trig_box: a block and an index box in its extended index space, ghost cells
 // included, that holds every cell whose centre can lie inside the sphere) and the grid is (P, entries of the list).
 // Each workgroup of 256 takes a fixed contiguous share of its box's cells, i fastest so that loads coalesce along a row
-// of the box; a box is clipped to the block's arrays before it is used.  The cell centre is centre() of cell_centre.hpp
-// with the index counted from the first interior cell (negative in the lower ghost zone), the number the host's
-// generators and a neighbouring block form for that cell; r2 = x * x + y * y + z * z and the test is the strict r2 < R^2.
+// of the box; a box is clipped to the block's arrays before it is used.  The cell centre is cell_centre of
+// cell_centre.hpp with the index counted from the first interior cell (negative in the lower ghost zone), the number the
+// host's generators and a neighbouring block form for that cell; r2 = x * x + y * y + z * z and the test is the strict
+// r2 < R^2.
 //
-// Reductions.  A lane adds its cells in index order, the workgroup reduces through a fixed LDS tree, and a second small
-// kernel adds a block's P partials in order: no atomics, a block's sums are a function of the block and its box alone
-// (the pattern of tower_contribs_kernel).  Only interior cells enter the sums.  Blocks outside the list report zeros (the
-// output is cleared first).
+// Reductions.  The deterministic block sum of block_sum.hpp with a box as the entry: P, a workgroup's share and the order
+// of every addition are defined there (the tower's power contributions of kernels_feedback.hip add in the same order, in
+// kernels of their own); no atomics, a block's sums are a function of the block and its box alone.  The kernels here
+// supply the terms of a cell (four Bondi sums, or one cold mass and three zeros); the final kernel writes the four to the
+// slots of the block an entry names.  Only interior cells enter
+// the sums.  Blocks outside the list report zeros (the output is cleared first).
 //
 // In-place updates (COLD_GAS with removal in the reduction's launch, and the Bondi removal).  A lane owns its cell: it
 // reads cons and prim of that cell only, applies AddDensityToConsAtFixedVelTemp on the stored primitives, re-derives the
@@ -40,18 +43,13 @@
 #include <cstdint>
 
 #include "apk_internal.hpp"
+#include "block_sum.hpp"
 #include "cell_centre.hpp"
 #include "hydro_math.hpp"
 
 namespace apk {
 
 namespace {
-
-constexpr int kTrigCellsPerGroup = 4096, kTrigMaxGroups = 64;
-inline int trig_groups(int64_t max_box_cells) {
-  const int64_t p = (max_box_cells + kTrigCellsPerGroup - 1) / kTrigCellsPerGroup;
-  return (int)(p < 1 ? 1 : (p > kTrigMaxGroups ? kTrigMaxGroups : p));
-}
 
 // the box of entry `e`, clipped to the block's arrays, and this workgroup's share [first, last) of its cells
 struct BoxShare {
@@ -70,11 +68,7 @@ APK_DEV bool box_share(const PackView &pv, const apk_trig_box *__restrict__ boxe
     s.lo[d] = lo;
     s.n[d] = hi > lo ? hi - lo : 0;
   }
-  const int64_t ncell = (int64_t)s.n[0] * s.n[1] * s.n[2];
-  // a whole number of 256-cell rounds, the same for every workgroup of the box
-  const int64_t share = ((ncell + P - 1) / P + 255) / 256 * 256;
-  s.first = (int64_t)p * share;
-  s.last = (s.first + share < ncell) ? s.first + share : ncell;
+  block_sum_share((int64_t)s.n[0] * s.n[1] * s.n[2], p, P, s.first, s.last);
   return true;
 }
 
@@ -86,17 +80,12 @@ struct TrigCell {
 };
 APK_DEV TrigCell trig_cell(const PackView &pv, const BoxShare &s, const apk_block_desc &bd, const double *__restrict__ block_xmin,
                            int64_t q) {
-  const int64_t nrow = s.n[0], nplane = nrow * s.n[1];
-  const int kk = (int)(q / nplane);
-  const int64_t r = q - (int64_t)kk * nplane;
-  const int jj = (int)(r / nrow);
-  const int ii = (int)(r - (int64_t)jj * nrow);
+  const int64_t nrow = s.n[0];
+  int ii, jj, kk;
+  box_ijk(q, nrow, nrow * s.n[1], ii, jj, kk);
   const int i = s.lo[0] + ii, j = s.lo[1] + jj, k = s.lo[2] + kk;
-  const double *corner = block_xmin + 3 * (int64_t)s.b;
-  const double *mesh = block_xmin + 3 * (int64_t)pv.nblocks;
-  const double x = centre(corner[0], mesh[0], bd.dx[0], i - pv.is);
-  const double y = centre(corner[1], mesh[1], bd.dx[1], j - pv.js);
-  const double z = centre(corner[2], mesh[2], bd.dx[2], k - pv.ks);
+  double x, y, z;
+  cell_xyz(bd, block_xmin, s.b, pv.nblocks, i - pv.is, j - pv.js, k - pv.ks, x, y, z);
   TrigCell c;
   c.off = (int64_t)k * pv.sk + (int64_t)j * pv.sj + i;
   c.r2 = x * x + y * y + z * z;
@@ -132,25 +121,6 @@ APK_DEV unsigned add_density_fixed_vel_temp(const apk_eos &eos, const apk_block_
   return flags;
 }
 
-// the workgroup's NS sums through a fixed LDS tree into partial[(e * P + p) * 4 + n]
-template <int NS>
-APK_DEV void reduce_store(double (&red)[4][256], const double (&acc)[4], int e, int p, int P, double *__restrict__ partial) {
-#pragma unroll
-  for (int n = 0; n < NS; ++n) red[n][threadIdx.x] = acc[n];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int n = 0; n < NS; ++n) red[n][threadIdx.x] += red[n][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int n = 0; n < 4; ++n) partial[((int64_t)e * P + p) * 4 + n] = n < NS ? red[n][0] : 0.0;
-  }
-}
-
 // ReduceBondiTriggeringQuantities (agn_triggering.cpp:234-256): grid (P, entries)
 __global__ void __launch_bounds__(256) trig_reduce_bondi_kernel(PackView pv, double gamma, double accretion_radius,
                                                                 const apk_trig_box *__restrict__ boxes,
@@ -176,7 +146,7 @@ __global__ void __launch_bounds__(256) trig_reduce_bondi_kernel(PackView pv, dou
       acc[3] += cell_mass * sqrt(gamma * pr / rho);
     }
   }
-  reduce_store<4>(red, acc, e, p, P, partial);
+  block_sum_store<4, 4>(red, acc, e, p, P, partial);
 }
 
 // ReduceColdMass (agn_triggering.cpp:162-195): grid (P, entries)
@@ -208,20 +178,7 @@ __global__ void __launch_bounds__(256) trig_reduce_cold_kernel(PackView pv, apk_
     }
   }
   if (flags) atomicOr(d_flags, flags);
-  reduce_store<1>(red, acc, e, p, P, partial);
-}
-
-// the P partials of every listed block, added in order: one lane per (entry, sum)
-__global__ void __launch_bounds__(64) trig_reduce_final_kernel(const double *__restrict__ partial, int P, int nboxes, int nblocks,
-                                                               const apk_trig_box *__restrict__ boxes, double *__restrict__ sums) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= 4 * nboxes) return;
-  const int e = q >> 2, n = q & 3;
-  const int b = boxes[e].block;
-  if (b < 0 || b >= nblocks) return;
-  double sum = 0.0;
-  for (int p = 0; p < P; ++p) sum += partial[((int64_t)e * P + p) * 4 + n];
-  sums[4 * (int64_t)b + n] = sum;
+  block_sum_store<1, 4>(red, acc, e, p, P, partial);
 }
 
 // RemoveBondiAccretedGas (agn_triggering.cpp:296-314): grid (P, entries)
@@ -246,17 +203,6 @@ __global__ void __launch_bounds__(256) trig_remove_bondi_kernel(PackView pv, apk
   if (flags) atomicOr(d_flags, flags);
 }
 
-const char *trig_pack_problem(const apk_pack *md, int fluid) {
-  const PackView &v = md->view;
-  if (v.nhydro != 5 && v.nhydro != 9) return "the pack is neither hydro nor GLM-MHD";
-  if ((fluid == APK_FLUID_GLMMHD) != (v.nhydro == 9) || (fluid != APK_FLUID_EULER && fluid != APK_FLUID_GLMMHD))
-    return "fluid does not match the pack";
-  if (v.ndim != 3) return "the pack is not three-dimensional";
-  for (int b = 0; b < v.nblocks; ++b)
-    if (!md->h_blocks[b].prim || !md->h_blocks[b].cons) return "the pack needs cons and prim";
-  return nullptr;
-}
-
 }  // namespace
 }  // namespace apk
 
@@ -269,7 +215,7 @@ int apk_agn_triggering_reduce(apk_ctx *ctx, const apk_pack *md, int fluid, const
                               double *sums, apk_stream_t stream) {
   if (!ctx || !md || !eos || !cfg || !block_xmin || !sums || nboxes < 0 || (nboxes > 0 && !boxes))
     return set_err(ctx, APK_ERR_INVALID, "apk_agn_triggering_reduce: bad argument");
-  if (const char *why = trig_pack_problem(md, fluid)) return set_err(ctx, APK_ERR_INVALID, (std::string("apk_agn_triggering_reduce: ") + why).c_str());
+  if (const char *why = pack_problem(md, PACK_FLUID | PACK_3D | PACK_STORED, fluid)) return pack_refused(ctx, "apk_agn_triggering_reduce", why);
   if (cfg->mode != APK_TRIG_COLD_GAS && cfg->mode != APK_TRIG_BOOSTED_BONDI && cfg->mode != APK_TRIG_BOOTH_SCHAYE)
     return set_err(ctx, APK_ERR_INVALID, "apk_agn_triggering_reduce: Unrecognized AGNTriggeringMode");
   const PackView &v = md->view;
@@ -279,11 +225,11 @@ int apk_agn_triggering_reduce(apk_ctx *ctx, const apk_pack *md, int fluid, const
   ScopedTiming span(ctx, APK_T_TRIGGERING, s);
   APK_HIP_TRY(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 4 * (size_t)v.nblocks, s));
   if (nboxes == 0) return APK_OK;
-  const int P = trig_groups(max_box_cells);
+  const int P = block_sum_groups(max_box_cells);
   const int rc = ensure_partial_doubles(ctx, (size_t)nboxes * P * 4);
   if (rc != APK_OK) return rc;
   const dim3 grid((unsigned)P, (unsigned)nboxes), block(256);
-  if (cfg->mode == APK_TRIG_COLD_GAS) {
+  if (cfg->mode == APK_TRIG_COLD_GAS) {  // (one sum; the other three slots are written as zeros)
     if (fluid == APK_FLUID_GLMMHD)
       hipLaunchKernelGGL((trig_reduce_cold_kernel<APK_FLUID_GLMMHD>), grid, block, 0, s, v, *eos, *cfg, dt, boxes, block_xmin, ctx->d_partial, ctx->d_flags);
     else
@@ -291,8 +237,7 @@ int apk_agn_triggering_reduce(apk_ctx *ctx, const apk_pack *md, int fluid, const
   } else {
     hipLaunchKernelGGL(trig_reduce_bondi_kernel, grid, block, 0, s, v, eos->gamma, cfg->accretion_radius, boxes, block_xmin, ctx->d_partial);
   }
-  hipLaunchKernelGGL(trig_reduce_final_kernel, dim3((unsigned)((4 * nboxes + 63) / 64)), dim3(64), 0, s, ctx->d_partial, P, nboxes,
-                     v.nblocks, boxes, sums);
+  block_sum_final_by_box<4>(ctx->d_partial, P, nboxes, v.nblocks, boxes, sums, s);
   if (hipGetLastError() != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "AGN triggering reduction launch failed");
   return APK_OK;
 }
@@ -302,15 +247,15 @@ int apk_agn_triggering_remove_bondi(apk_ctx *ctx, const apk_pack *md, int fluid,
                                     double total_mass, double accretion_rate, double dt, apk_stream_t stream) {
   if (!ctx || !md || !eos || !block_xmin || nboxes < 0 || (nboxes > 0 && !boxes))
     return set_err(ctx, APK_ERR_INVALID, "apk_agn_triggering_remove_bondi: bad argument");
-  if (const char *why = trig_pack_problem(md, fluid))
-    return set_err(ctx, APK_ERR_INVALID, (std::string("apk_agn_triggering_remove_bondi: ") + why).c_str());
+  if (const char *why = pack_problem(md, PACK_FLUID | PACK_3D | PACK_STORED, fluid))
+    return pack_refused(ctx, "apk_agn_triggering_remove_bondi", why);
   const PackView &v = md->view;
   if (v.nblocks == 0 || nboxes == 0) return APK_OK;
   if (nboxes > v.nblocks || nboxes > 65535)
     return set_err(ctx, APK_ERR_INVALID, "apk_agn_triggering_remove_bondi: more entries than blocks, or than 65535");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ScopedTiming span(ctx, APK_T_TRIGGERING, s);
-  const dim3 grid((unsigned)trig_groups(max_box_cells), (unsigned)nboxes), block(256);
+  const dim3 grid((unsigned)block_sum_groups(max_box_cells), (unsigned)nboxes), block(256);
   if (fluid == APK_FLUID_GLMMHD)
     hipLaunchKernelGGL((trig_remove_bondi_kernel<APK_FLUID_GLMMHD>), grid, block, 0, s, v, *eos, accretion_radius, total_mass, accretion_rate,
                        dt, boxes, block_xmin, ctx->d_flags);

@@ -336,16 +336,6 @@ __global__ void __launch_bounds__(256) user_reldivb_kernel(PackView pv, double B
   store_partials<1>(h, partial);
 }
 
-int ensure_partial_cap(apk_ctx *ctx, size_t n) {
-  if (ctx->partial_cap >= n) return APK_OK;
-  if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-  ctx->d_partial = nullptr;
-  ctx->partial_cap = 0;
-  if (hipMalloc(&ctx->d_partial, n * sizeof(double)) != hipSuccess) return APK_ERR_DEVICE;
-  ctx->partial_cap = n;
-  return APK_OK;
-}
-
 // run a partial-sum kernel result through the final reduction and bring NQ doubles to the host
 // The kick with the work of the two tasks that follow it on the same cell: FillDerived (ConsToPrim, floors
 // included, prim in place: the kick is the last thing to touch the cell before the next stage reads it) and
@@ -548,7 +538,7 @@ int apk_turb_mean_momentum(apk_ctx *ctx, const apk_pack *md, const apk_fmft *f, 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (ensure_partial_cap(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "partial buffer");
+  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
   hipLaunchKernelGGL(turb_mean_momentum_kernel, g, dim3(64, 4, 1), 0, s, md->view, f->d_blocks, ctx->d_partial);
   return finish_sums<4>(ctx, nwg, sums4, s);
 }
@@ -561,7 +551,7 @@ int apk_turb_remove_mean(apk_ctx *ctx, const apk_pack *md, apk_fmft *f, const do
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (ensure_partial_cap(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "partial buffer");
+  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
   hipLaunchKernelGGL(turb_remove_mean_kernel, g, dim3(64, 4, 1), 0, s, md->view, f->d_blocks, sums4[1] / sums4[0],
                      sums4[2] / sums4[0], sums4[3] / sums4[0], ctx->d_partial);
   return finish_sums<1>(ctx, nwg, ampl_sum, s);
@@ -590,7 +580,7 @@ int apk_turbulence_history(apk_ctx *ctx, const apk_pack *md, int fluid, double g
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (ensure_partial_cap(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "partial buffer");
+  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
   if (fluid == APK_FLUID_EULER)
     hipLaunchKernelGGL(turb_history_kernel<APK_FLUID_EULER>, g, dim3(64, 4, 1), 0, s, md->view, gamma, ctx->d_partial);
   else
@@ -604,7 +594,7 @@ int apk_history_user_reldivb(apk_ctx *ctx, const apk_pack *md, double B0, double
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (ensure_partial_cap(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "partial buffer");
+  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
   hipLaunchKernelGGL(user_reldivb_kernel, g, dim3(64, 4, 1), 0, s, md->view, B0, ctx->d_partial);
   return finish_sums<1>(ctx, nwg, out, s);
 }

@@ -307,3 +307,40 @@ def test_a_radius_smaller_than_a_cell_can_leave_the_list_empty_of_interior_cells
     """radius 0.001 on the 16^3 mesh (dx = 0.0125): no centre is inside, every direction's range is empty, no block listed"""
     p = _plan(_mesh(16, 8, (-0.1,) * 3, (0.1,) * 3) + [TRIG + "accretion_radius=0.001"])
     assert p.agn_triggering_active_list() == [] and p.agn_triggering_options().active_box_cells == 0
+
+
+# ---- the restated order of the device's block sum ------------------------------------------------------------------------
+def _pairwise(v):
+    """the halving tree on a list whose length is a power of two, written as a recursion: (lower half + upper half)"""
+    if len(v) == 1:
+        return v[0]
+    h = len(v) // 2
+    return _pairwise([a + b for a, b in zip(v[:h], v[h:])])
+
+
+@pytest.mark.parametrize("n,P", [(1, 1), (2, 1), (255, 1), (257, 1), (4096, 1), (4097, 2), (13824, 4), (13824, 3), (300, 4)])
+def test_block_sum_restatement(n, P):
+    """TR.block_sum, the yardstick of the GPU test of the shared sum, on random positive terms: within (N - 1) eps sum |t|
+    of math.fsum, which bounds every order of adding N numbers.  Where its order is simple enough to write down another
+    way it is that order bit for bit: terms on lane 0 only (cells 0, 256, 512, ...) with P = 1 give the plain in-order sum
+    (adding zeros is exact); N <= 2 with P = 1 likewise; N <= 256 with P = 1 gives the halving tree of the terms padded
+    with zeros to 256, one term per lane."""
+    rng = np.random.default_rng(n + P)
+    t = rng.uniform(0.5, 1.5, (3, n))
+    got = TR.block_sum(t, P)
+    for row, g in zip(t, got):
+        assert abs(g - math.fsum(row)) <= max(n - 1, 0) * EPS * math.fsum(np.abs(row))
+    if P == 1:
+        on_lane0 = np.where(np.arange(n) % TR.BLOCK_SUM_LANES == 0, t[0], 0.0)
+        want = 0.0
+        for x in on_lane0[::TR.BLOCK_SUM_LANES]:
+            want += x
+        assert TR.block_sum(on_lane0, 1) == want
+        if n <= 2:
+            assert got[0] == sum(t[0].tolist())
+        if n <= TR.BLOCK_SUM_LANES:
+            assert got[0] == _pairwise(t[0].tolist() + [0.0] * (TR.BLOCK_SUM_LANES - n))
+
+
+def test_block_sum_groups():
+    assert [TR.block_sum_groups(n) for n in (0, 1, 4096, 4097, 13824, 64 * 4096, 10 ** 9)] == [1, 1, 1, 2, 4, 64, 64]

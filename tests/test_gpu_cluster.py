@@ -10,23 +10,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cluster_reference as R  # noqa: E402
-from _spawn import spawn  # noqa: E402
+from cluster_cases import assert_two_ranks_equal_one, box as _box, centres as _centres, geom as _geom, mesh as _mesh  # noqa: E402
+from cluster_cases import read as _read, sim as _deck_sim  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = np.finfo(np.float64).eps
 SCHURE = os.path.join(ROOT, "tests", "golden", "schure.cooling_1.0Z")
-
-
-def _mesh(n, mb):
-    n = (n,) * 3 if isinstance(n, int) else n
-    mb = (mb,) * 3 if isinstance(mb, int) else mb
-    return (["parthenon/mesh/nx%d=%d" % (d + 1, n[d]) for d in range(3)] +
-            ["parthenon/meshblock/nx%d=%d" % (d + 1, mb[d]) for d in range(3)])
-
-
-def _box(lo, hi):
-    return (["parthenon/mesh/x%dmin=%r" % (d + 1, lo[d]) for d in range(3)] +
-            ["parthenon/mesh/x%dmax=%r" % (d + 1, hi[d]) for d in range(3)])
 
 
 def _components(nfw, bcg, smbh):
@@ -36,8 +25,7 @@ def _components(nfw, bcg, smbh):
 
 
 def _sim(overrides, strict=True, **kw):
-    from athenapk_amd import decks, driver
-    return driver.Simulation(decks.load("cluster_hse"), list(overrides), strict=strict, **kw)
+    return _deck_sim("cluster_hse", overrides, strict=strict, **kw)
 
 
 def _gravity_struct(g):
@@ -124,7 +112,7 @@ def _source_state(s, fluid, seed):
         s.write_block(lb, u)
     s.exchange_ghosts()
     s.fill_derived()
-    return [(s.read_block(lb, "cons"), s.read_block(lb, "prim")) for lb in range(s.info.nblocks_local)]
+    return _read(s)
 
 
 def _run_source(mesh, fluid, comps, strict, beta_dt=1e-3, seed=5):
@@ -134,10 +122,8 @@ def _run_source(mesh, fluid, comps, strict, beta_dt=1e-3, seed=5):
     s.initialize()
     before = _source_state(s, fluid, seed)
     s.gravity_src(beta_dt)
-    after = [(s.read_block(lb, "cons"), s.read_block(lb, "prim")) for lb in range(s.info.nblocks_local)]
-    info = s.info
-    geom = dict(ng=info.ng, mb=tuple(info.mb), dx=tuple(info.dx), xmin=tuple(info.xmin),
-                loc=[s.block_gid(lb)[1] for lb in range(info.nblocks_local)], smoothing=smoothing)
+    after, geom = _read(s), _geom(s)
+    geom.smoothing = smoothing
     s.close()
     return before, after, geom
 
@@ -157,14 +143,14 @@ def test_gravity_source_against_the_restatement(mesh, comps, fluid):
     beta_dt = 1e-3
     before, after, geom = _run_source(mesh, fluid, comps, True, beta_dt)
     grav = R.deck_model(*comps)[0]
-    grav.smoothing_r = np.float64(geom["smoothing"])
-    ng, mb = geom["ng"], geom["mb"]
+    grav.smoothing_r = np.float64(geom.smoothing)
+    ng, mb = geom.ng, geom.mb
     inner = (slice(ng, ng + mb[2]), slice(ng, ng + mb[1]), slice(ng, ng + mb[0]))
     hit_zero = False
     strict_new = []
-    for (u0, w0), (u1, w1), loc in zip(before, after, geom["loc"]):
+    for (u0, w0), (u1, w1), loc in zip(before, after, geom.loc):
         assert np.array_equal(w0, w1)  # the stored primitives
-        xs = [R.cell_centres(geom["xmin"][d], geom["dx"][d], loc[d] * mb[d], mb[d]) for d in range(3)]
+        xs = _centres(geom, loc)
         rho, v1, v2, v3 = (w0[(n,) + inner] for n in range(4))
         src, d1, d2, d3, de = R.gravity_src(grav, xs[0], xs[1], xs[2], rho, v1, v2, v3, beta_dt)
         r = R.radius(*xs)
@@ -341,43 +327,11 @@ def test_reflection_symmetry_on_the_decks_box():
 TWO_RANK_OV = _mesh(32, 16) + ["problem/cluster/hydrostatic_equilibrium/test_he_sphere=false"]
 
 
-def _rank_worker(rank, world, port, outdir):
-    sys.path.insert(0, ROOT)
-    import torch
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    try:
-        s = _sim(TWO_RANK_OV, rank=rank, nranks=world).initialize()
-        for _ in range(3):
-            s.step()
-        blocks = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
-        np.savez(os.path.join(outdir, "rank%d.npz" % rank), time=s.time, dt=s.dt, **{"b%d" % g: a for g, a in blocks.items()})
-        s.close()
-    finally:
-        dist.destroy_process_group()
-
-
 @pytest.mark.gpu
 def test_two_ranks_equal_one(tmp_path):
     """cluster_hse at 32^3 in 16^3 blocks, 3 cycles, two ranks sharing the GPU (gloo): every block equals the one-rank
     run's bit for bit -- nothing in the generator or the source is global"""
-    s = _sim(TWO_RANK_OV).initialize()
-    for _ in range(3):
-        s.step()
-    one = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
-    time, dt = s.time, s.dt
-    s.close()
-    spawn(_rank_worker, lambda port: (2, port, str(tmp_path)), 2)
-    seen = set()
-    for r in range(2):
-        z = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
-        assert z["time"] == time and z["dt"] == dt
-        for key in z.files:
-            if key.startswith("b"):
-                seen.add(int(key[1:]))
-                assert np.array_equal(z[key], one[int(key[1:])]), "rank %d block %s" % (r, key)
-    assert seen == set(one) and len(seen) == 8
+    assert_two_ranks_equal_one(tmp_path, "cluster_hse", TWO_RANK_OV, 3)
 
 
 # ---- 7. the order of the unsplit sources --------------------------------------------------------------------------------

@@ -13,26 +13,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cluster_reference as R  # noqa: E402
 import feedback_reference as FB  # noqa: E402
-from _spawn import spawn  # noqa: E402
+from cluster_cases import assert_two_ranks_equal_one, box as _box, centres as _centres, geom as _geom, mesh as _mesh  # noqa: E402
+from cluster_cases import next_dt as _next_dt, random_block as _random_block, read as _read, sim as _sim  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = np.finfo(np.float64).eps
 GAMMA = R.DECK_GAMMA
 AGN = "problem/cluster/agn_feedback/"
 TOWER = "problem/cluster/magnetic_tower/"
 JET = "problem/cluster/precessing_jet/"
-
-
-def _mesh(n, mb):
-    n = (n,) * 3 if isinstance(n, int) else n
-    mb = (mb,) * 3 if isinstance(mb, int) else mb
-    return (["parthenon/mesh/nx%d=%d" % (d + 1, n[d]) for d in range(3)] +
-            ["parthenon/meshblock/nx%d=%d" % (d + 1, mb[d]) for d in range(3)])
-
-
-def _box(lo, hi):
-    return (["parthenon/mesh/x%dmin=%r" % (d + 1, lo[d]) for d in range(3)] +
-            ["parthenon/mesh/x%dmax=%r" % (d + 1, hi[d]) for d in range(3)])
 
 
 # the gravity test's shapes (tests/test_gpu_cluster.py SRC_MESHES)
@@ -44,29 +32,8 @@ MESHES = {
 }
 
 
-def _sim(deck, overrides, strict=True, **kw):
-    from athenapk_amd import decks, driver
-    return driver.Simulation(decks.load(deck), list(overrides), strict=strict, **kw)
-
-
-def _geom(s):
-    info = s.info
-    return SimpleNamespace(ng=info.ng, mb=tuple(info.mb), dx=tuple(info.dx), xmin=tuple(info.xmin), nb=info.nblocks_local,
-                           loc=[tuple(s.block_gid(lb)[1]) for lb in range(info.nblocks_local)],
-                           gid=[s.block_gid(lb)[0] for lb in range(info.nblocks_local)])
-
-
 def _inner(g):
     return (slice(g.ng, g.ng + g.mb[2]), slice(g.ng, g.ng + g.mb[1]), slice(g.ng, g.ng + g.mb[0]))
-
-
-def _centres(g, loc, ext=0):
-    """the host's cell centres of a block's interior, `ext` cells beyond it on both sides"""
-    return [R.cell_centres(g.xmin[d], g.dx[d], loc[d] * g.mb[d] - ext, g.mb[d] + 2 * ext) for d in range(3)]
-
-
-def _read(s):
-    return [(s.read_block(lb, "cons"), s.read_block(lb, "prim")) for lb in range(s.info.nblocks_local)]
 
 
 def _random_state(s, fluid, seed, speed=(0.5, 1.0)):
@@ -77,23 +44,6 @@ def _random_state(s, fluid, seed, speed=(0.5, 1.0)):
         s.write_block(lb, _random_block(rng, s.block_shape, fluid, speed))
     s.exchange_ghosts()
     s.fill_derived()
-
-
-def _random_block(rng, shape, fluid, speed=(0.5, 1.0)):
-    u = np.zeros(shape)
-    u[0] = rng.uniform(0.5, 1.5, shape[1:])
-    for d in range(3):
-        u[1 + d] = u[0] * rng.uniform(speed[0], speed[1], shape[1:])
-    u[4] = rng.uniform(4.0, 5.0, shape[1:]) + 0.5 * (u[1] ** 2 + u[2] ** 2 + u[3] ** 2) / u[0]
-    if fluid == "glmmhd":
-        u[5:8] = rng.uniform(-0.3, 0.3, (3,) + shape[1:])
-        u[8] = rng.uniform(-0.01, 0.01, shape[1:])
-    return u
-
-
-def _next_dt(s):
-    """the step the next cycle takes (apk_sim_step clips the estimate at tlim)"""
-    return s.tlim - s.time if (s.time < s.tlim and s.tlim - s.time < s.dt) else s.dt
 
 
 def _ns(struct):
@@ -625,41 +575,9 @@ def test_gravity_then_feedback_then_tower_power_then_tower_fixed(gpu_ctx_strict)
 
 
 # ---- I. two ranks ------------------------------------------------------------------------------------------------------------------------
-def _rank_worker(rank, world, port, outdir):
-    sys.path.insert(0, ROOT)
-    import torch
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    try:
-        s = _sim("cluster_magnetic_tower", TOWER_CYCLE_OV, rank=rank, nranks=world).initialize()
-        for _ in range(2):
-            s.step()
-        blocks = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
-        np.savez(os.path.join(outdir, "rank%d.npz" % rank), time=s.time, dt=s.dt, **{"b%d" % g: a for g, a in blocks.items()})
-        s.close()
-    finally:
-        dist.destroy_process_group()
-
-
 @pytest.mark.gpu
 def test_two_ranks_equal_one_in_power_mode(tmp_path):
     """the tower deck in power mode at 16^3 in 8^3 blocks, 2 cycles, two ranks sharing the GPU (gloo): every block equals
     the one-rank run's bit for bit -- the scale factor comes from sums whose slots are added in global block order,
     whatever the distribution of the blocks"""
-    s = _sim("cluster_magnetic_tower", TOWER_CYCLE_OV).initialize()
-    for _ in range(2):
-        s.step()
-    one = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
-    time, dt = s.time, s.dt
-    s.close()
-    spawn(_rank_worker, lambda port: (2, port, str(tmp_path)), 2)
-    seen = set()
-    for r in range(2):
-        z = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
-        assert z["time"] == time and z["dt"] == dt
-        for key in z.files:
-            if key.startswith("b"):
-                seen.add(int(key[1:]))
-                assert np.array_equal(z[key], one[int(key[1:])]), "rank %d block %s" % (r, key)
-    assert seen == set(one) and len(seen) == 8
+    assert_two_ranks_equal_one(tmp_path, "cluster_magnetic_tower", TOWER_CYCLE_OV, 2)

@@ -14,26 +14,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cluster_reference as R  # noqa: E402
 import feedback_reference as FB  # noqa: E402
 import triggering_reference as TR  # noqa: E402
-from _spawn import spawn  # noqa: E402
+from cluster_cases import assert_two_ranks_equal_one, box as _box, centres as _centres, geom as _geom, mesh as _mesh  # noqa: E402
+from cluster_cases import next_dt as _next_dt, random_block as _random_block, read as _read, sim as _deck_sim  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = np.finfo(np.float64).eps
 GAMMA = R.DECK_GAMMA
 TRIG = "problem/cluster/agn_triggering/"
 AGN = "problem/cluster/agn_feedback/"
 DECK = "cluster_agn_triggering"
-
-
-def _mesh(n, mb):
-    n = (n,) * 3 if isinstance(n, int) else n
-    mb = (mb,) * 3 if isinstance(mb, int) else mb
-    return (["parthenon/mesh/nx%d=%d" % (d + 1, n[d]) for d in range(3)] +
-            ["parthenon/meshblock/nx%d=%d" % (d + 1, mb[d]) for d in range(3)])
-
-
-def _box(lo, hi):
-    return (["parthenon/mesh/x%dmin=%r" % (d + 1, lo[d]) for d in range(3)] +
-            ["parthenon/mesh/x%dmax=%r" % (d + 1, hi[d]) for d in range(3)])
 
 
 # the feedback test's shapes (tests/test_gpu_cluster_feedback.py MESHES), each with an accretion radius of a few cells:
@@ -49,15 +37,7 @@ MESHES = {
 
 
 def _sim(overrides, strict=True, **kw):
-    from athenapk_amd import decks, driver
-    return driver.Simulation(decks.load(DECK), list(overrides), strict=strict, **kw)
-
-
-def _geom(s):
-    info = s.info
-    return SimpleNamespace(ng=info.ng, mb=tuple(info.mb), dx=tuple(info.dx), xmin=tuple(info.xmin), nb=info.nblocks_local,
-                           loc=[tuple(s.block_gid(lb)[1]) for lb in range(info.nblocks_local)],
-                           vol=np.float64(info.dx[0]) * np.float64(info.dx[1]) * np.float64(info.dx[2]))
+    return _deck_sim(DECK, overrides, strict=strict, **kw)
 
 
 def _interior_mask(g):
@@ -66,31 +46,9 @@ def _interior_mask(g):
     return m
 
 
-def _centres(g, loc):
-    """the host's cell centres of every cell of a block, ghost cells included"""
-    return [R.cell_centres(g.xmin[d], g.dx[d], loc[d] * g.mb[d] - g.ng, g.mb[d] + 2 * g.ng) for d in range(3)]
-
-
 def _spheres(g, radius):
     """per block the [k][j][i] mask of the extended cells with r2 < R^2"""
-    return [TR.sphere(*_centres(g, loc), radius) for loc in g.loc]
-
-
-def _read(s):
-    return [(s.read_block(lb, "cons"), s.read_block(lb, "prim")) for lb in range(s.info.nblocks_local)]
-
-
-def _random_block(rng, shape, fluid):
-    """rho in [0.5, 1.5], v in [0.5, 1]^3, E - e_k in [4, 5], B in [-0.3, 0.3]^3 and psi (the feedback test's state)"""
-    u = np.zeros(shape)
-    u[0] = rng.uniform(0.5, 1.5, shape[1:])
-    for d in range(3):
-        u[1 + d] = u[0] * rng.uniform(0.5, 1.0, shape[1:])
-    u[4] = rng.uniform(4.0, 5.0, shape[1:]) + 0.5 * (u[1] ** 2 + u[2] ** 2 + u[3] ** 2) / u[0]
-    if fluid == "glmmhd":
-        u[5:8] = rng.uniform(-0.3, 0.3, (3,) + shape[1:])
-        u[8] = rng.uniform(-0.01, 0.01, shape[1:])
-    return u
+    return [TR.sphere(*_centres(g, loc, g.ng), radius) for loc in g.loc]
 
 
 def _random_sim(mesh, fluid, overrides=(), seed=5, strict=True):
@@ -113,10 +71,6 @@ def _bondi_sums(state, g, masks):
 
 def _state_sums(st):
     return np.array([st.total_mass, st.mass_weighted_density, st.mass_weighted_velocity, st.mass_weighted_cs])
-
-
-def _next_dt(s):
-    return s.tlim - s.time if (s.time < s.tlim and s.tlim - s.time < s.dt) else s.dt
 
 
 def _model(s):
@@ -168,6 +122,28 @@ def test_bondi_reduce(fluid):
     assert n1 == n and np.all(np.abs(got1 - want1) <= bound) and np.all(np.abs(got1 - first) <= bound)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("fluid", ["euler", "glmmhd"])
+def test_bondi_sums_in_the_shared_order(fluid):
+    """The order of the additions, which the bound of test_bondi_reduce cannot see.  One 16^3 block on +-0.1 with
+    accretion_radius = 0.3: every cell, ghost cells included, lies inside the sphere (the farthest centre is at
+    sqrt(3) (0.1 + (ng - 1/2) dx) < 0.25), so the active box is the block's whole arrays, (16 + 2 ng)^3 > 4096 cells: two or
+    more workgroups share it.  The four sums equal TR.block_sum of the restated terms in array order, zero on ghost cells,
+    bit for bit (strict build; a skipped cell and an added zero are the same bits)."""
+    s = _random_sim("one_block", fluid, [TRIG + "triggering_mode=BOOSTED_BONDI", TRIG + "accretion_radius=0.3"])
+    g, o, ((_, w),) = _geom(s), s.agn_triggering_options(), _read(s)
+    got = _state_sums(s.agn_triggering_reduce(1e-3))
+    s.close()
+    ncell = (16 + 2 * g.ng) ** 3
+    assert _spheres(g, o.accretion_radius)[0].all() and o.active_blocks == 1 and o.active_box_cells == ncell
+    P = TR.block_sum_groups(o.active_box_cells)
+    assert P >= 2
+    terms = TR.bondi_terms(w, np.ones(w.shape[1:], bool), g.vol, GAMMA)
+    want = TR.block_sum(np.where(_interior_mask(g).ravel(), terms, 0.0), P)
+    print("P = %d, device %s, restated %s" % (P, got, want))
+    assert np.array_equal(got, want)
+
+
 # ---- B. the strict edge ---------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_the_sphere_is_strict():
@@ -180,7 +156,7 @@ def test_the_sphere_is_strict():
                                                     "problem/cluster/gravity/m_smbh=0.3"])  # (removes about 1 % in 1e-3)
         g, before = _geom(s), _read(s)
         mask, = _spheres(g, radius)
-        xs = _centres(g, g.loc[0])
+        xs = _centres(g, g.loc[0], g.ng)
         i, j, k = (int(np.nonzero(xs[0] == 0.25)[0][0]), int(np.nonzero(xs[1] == 0.0)[0][0]), int(np.nonzero(xs[2] == 0.0)[0][0]))
         on = (radius == 0.25)
         assert mask[k, j, i] == (not on)
@@ -473,7 +449,7 @@ def test_accretion_drives_the_feedback_power():
     sl = (slice(None),) + (slice(g.ng, g.ng + g.mb[2]), slice(g.ng, g.ng + g.mb[1]), slice(g.ng, g.ng + g.mb[0]))
     rose = 0
     for (u0, w0), (u1, w1), loc in zip(removed, after, g.loc):
-        xs = [x[g.ng:-g.ng] for x in _centres(g, loc)]
+        xs = [x[g.ng:-g.ng] for x in _centres(g, loc, g.ng)]
         u_want, w_want, info = FB.agn_feedback_src(u0[sl], w0[sl], xs[0], xs[1], xs[2], cfg, jet, GAMMA)
         assert np.array_equal(u1[sl], u_want) and np.array_equal(w1[sl], w_want)
         gain = (u1[sl][4] - u0[sl][4])[info.sphere]
@@ -507,46 +483,12 @@ def test_zero_power_skips_the_feedback_source():
 RANKS_OV = _mesh(16, 8) + ["parthenon/time/tlim=10.0", TRIG + "accretion_radius=0.03", TRIG + "triggering_mode=BOOSTED_BONDI"]
 
 
-def _rank_worker(rank, world, port, outdir):
-    sys.path.insert(0, ROOT)
-    import torch
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    try:
-        s = _sim(RANKS_OV, rank=rank, nranks=world).initialize()
-        for _ in range(3):
-            s.step()
-        blocks = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
-        st = s.agn_triggering_state()
-        np.savez(os.path.join(outdir, "rank%d.npz" % rank), time=s.time, dt=s.dt, rate=st.accretion_rate, mass=st.total_mass,
-                 **{"b%d" % g: a for g, a in blocks.items()})
-        s.close()
-    finally:
-        dist.destroy_process_group()
-
-
 @pytest.mark.gpu
 def test_two_ranks_equal_one(tmp_path):
     """BOOSTED_BONDI with removal on eight 8^3 blocks, 3 cycles, two ranks sharing the GPU (gloo): every block, ghost cells
     included, the time step and the reduced quantities equal the one-rank run's bit for bit -- every block's sums sit in
     their own slot and the slots are added in global block order, whatever the distribution of the blocks"""
-    s = _sim(RANKS_OV).initialize()
-    for _ in range(3):
-        s.step()
-    one = {s.block_gid(lb)[0]: s.read_block(lb, "cons") for lb in range(s.info.nblocks_local)}
-    time, dt, st = s.time, s.dt, s.agn_triggering_state()
-    s.close()
-    spawn(_rank_worker, lambda port: (2, port, str(tmp_path)), 2)
-    seen = set()
-    for r in range(2):
-        z = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
-        assert z["time"] == time and z["dt"] == dt and z["rate"] == st.accretion_rate and z["mass"] == st.total_mass
-        for key in z.files:
-            if key.startswith("b"):
-                seen.add(int(key[1:]))
-                assert np.array_equal(z[key], one[int(key[1:])]), "rank %d block %s" % (r, key)
-    assert seen == set(one) and len(seen) == 8
+    assert_two_ranks_equal_one(tmp_path, DECK, RANKS_OV, 3, triggering=True)
 
 
 # ---- I. a sphere without a cell -----------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """numpy restatement of the cluster problem's AGN triggering, in the operation order of the code under test: the
 accretion rate of the three modes and the time-step rule from reduced quantities, the mask of the accretion sphere, the
-Bondi sums and the cold mass, AddDensityToConsAtFixedVelTemp with the ConsToPrim that follows it, and the active list's
-index ranges.  The yardstick of tests/test_cluster_triggering_host.py and tests/test_gpu_cluster_triggering.py, written
+Bondi sums and the cold mass, the order in which the device adds a box's terms (block_sum), AddDensityToConsAtFixedVelTemp
+with the ConsToPrim that follows it, and the active list's index ranges.  The yardstick of tests/test_cluster_triggering_host.py and tests/test_gpu_cluster_triggering.py, written
 from the formulas in the manner of feedback_reference.py (which restates ConsToPrim): host scalars go through `math`
 (the libm of the C++), per-cell arithmetic is numpy float64, nothing fused or reassociated; squares of positions are
 products.  Every per-cell operation is a product, quotient, sum or square root: stored values are compared bit for bit,
@@ -73,6 +73,38 @@ def bondi_terms(w, mask, vol, gamma):
     rho, v1, v2, v3, p = (w[n][mask] for n in range(5))
     m = rho * F(vol)
     return np.array([m, m * rho, m * np.sqrt(v1 * v1 + v2 * v2 + v3 * v3), m * np.sqrt(F(gamma) * p / rho)])
+
+
+# the deterministic block sum (athenapk_amd/csrc/block_sum.hpp): lanes of a workgroup, cells per workgroup, most workgroups
+BLOCK_SUM_LANES, BLOCK_SUM_CELLS_PER_GROUP, BLOCK_SUM_MAX_GROUPS = 256, 4096, 64
+
+
+def block_sum_groups(ncell):
+    """P, the workgroups per box: one per 4096 cells of the largest box, between 1 and 64"""
+    return min(max(-(-ncell // BLOCK_SUM_CELLS_PER_GROUP), 1), BLOCK_SUM_MAX_GROUPS)
+
+
+def block_sum(terms, P):
+    """The sum of terms[..., N] along the last axis in the device's order.  The terms are those of a box in box-cell order,
+    zero for cells that do not count.  Workgroup p of P takes the cells [p share, (p + 1) share), share the least multiple
+    of 256 with P share >= N; each of its 256 lanes adds its cells first + lane, first + lane + 256, ... in that order; the
+    lane sums are halved 128 -> 1, lane l adding lane l + s to itself; the P partials are added in order."""
+    t = np.asarray(terms, dtype=F)
+    n, lead = t.shape[-1], t.shape[:-1]
+    share = (-(-n // P) + BLOCK_SUM_LANES - 1) // BLOCK_SUM_LANES * BLOCK_SUM_LANES
+    total = np.zeros(lead)
+    for p in range(P):
+        first, last = p * share, min(p * share + share, n)
+        lanes = np.zeros(lead + (BLOCK_SUM_LANES,))
+        for start in range(first, last, BLOCK_SUM_LANES):
+            chunk = t[..., start:min(start + BLOCK_SUM_LANES, last)]
+            lanes[..., :chunk.shape[-1]] = lanes[..., :chunk.shape[-1]] + chunk
+        s = BLOCK_SUM_LANES // 2
+        while s > 0:
+            lanes[..., :s] = lanes[..., :s] + lanes[..., s:2 * s]
+            s //= 2
+        total = total + lanes[..., 0]
+    return total
 
 
 def temperature(w, mm_by_kb):
