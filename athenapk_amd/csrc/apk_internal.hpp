@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -51,6 +52,55 @@ inline PackView make_view(const apk_pack_desc &d, const apk_block_desc *dev_bloc
   return v;
 }
 
+// ---- the context's scratch: 16 device words (apk_ctx::d_u64) and 256 bytes of pinned host memory (apk_ctx::h_pinned) --
+// Device words.  kWordFlags follows kWordStageDt: the end-of-cycle read-back fetches both with one 16-byte copy.
+enum : int {
+  kWordMin = 0,       // one-shot seeded minimum of the stand-alone time-step estimators (min_seed / min_fetch)
+  kWordCounter = 2,   // cells counted by FirstOrderFluxCorrect / apk_count_unphysical
+  kWordStageDt = 4,   // the stage's time-step minimum (prepare_dt_word; apk_stage_dt_read / apk_stage_dt_flags_read)
+  kWordFlags = 5,     // two 32-bit flag words, apk_ctx::d_flags: [0] latched, [1] trial stage
+  kWordStageBad = 6,  // the fused stage's count of unphysical cells (apk_stage_unphysical_read)
+  kWordPlusMax = 15,  // constant +max, the neutral element the time-step word is reset from
+  kNumWords = 16
+};
+// Pinned block.  Its first 8 u64 slots receive device words -- slot w word w, except that the one-shot minimum comes
+// back into kPinMin beside its seed --, then three regions of their own (byte offsets).
+enum : int {
+  kPinSeed = 0,  // u64 slot: the seed on its way to kWordMin
+  kPinMin = 1,   // u64 slot: kWordMin read back
+  kPinU64Slots = 8,
+  kPinHistory = 64,       // 8 doubles: apk_history
+  kPinSums = 128,         // kPinSumsMax doubles: the turbulence driver's sums (finish_sums)
+  kPinSumsMax = 4,
+  kPinPolledFlags = 192,  // one unsigned: apk_poll_device_flags
+  kPinnedBytes = 256
+};
+static_assert(kWordFlags == kWordStageDt + 1, "time-step word and flag words are read back with one 16-byte copy");
+static_assert(kPinSeed != kPinMin && kPinMin < kWordCounter && kWordStageBad < kPinU64Slots && kWordPlusMax < kNumWords,
+              "u64 slots: seed, minimum and the mirrored words are distinct");
+static_assert(kPinU64Slots * 8 <= kPinHistory && kPinHistory + 8 * 8 <= kPinSums &&
+                  kPinSums + kPinSumsMax * 8 <= kPinPolledFlags && kPinPolledFlags + 4 <= kPinnedBytes,
+              "pinned regions are disjoint and fit the block");
+
+}  // namespace apk
+
+struct apk_ctx;
+namespace apk {
+// A device buffer of an apk_ctx that grows on demand.
+template <class T>
+struct DeviceBuf {
+  T *p = nullptr;
+  size_t cap = 0;  // in elements
+  // At least n elements; grows by free + allocate of exactly n, contents are not kept.  A live buffer is freed only
+  // after `s` has drained (the kernels that use these buffers run on the caller's stream); the wait is paid only when
+  // a buffer grows, where hipFree waits for the device in any case.  A failure is APK_ERR_DEVICE, worded by APK_HIP_TRY.
+  int reserve(apk_ctx *ctx, size_t n, hipStream_t s);
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
 }  // namespace apk
 
 struct apk_pack {
@@ -63,13 +113,20 @@ struct apk_pack {
 
 struct apk_ctx {
   int device = -1;
-  unsigned *d_flags = nullptr;       // latched APK_FLAG_* bits
-  unsigned long long *d_u64 = nullptr;  // [8] scratch words (min-reduction, counters)
-  double *d_partial = nullptr;       // reduction partials
-  size_t partial_cap = 0;            // in doubles
-  unsigned char *d_mark = nullptr;   // FOFC cell marks
-  size_t mark_cap = 0;
-  void *h_pinned = nullptr;          // 256 B pinned host staging
+  unsigned *d_flags = nullptr;       // latched APK_FLAG_* bits: the two halves of word kWordFlags
+  unsigned long long *d_u64 = nullptr;  // [kNumWords] scratch words, laid out by the kWord* names above
+  unsigned long long *word(int w) const { return d_u64 + w; }
+  unsigned long long *min_word() const { return word(apk::kWordMin); }
+  unsigned long long *counter_word() const { return word(apk::kWordCounter); }
+  unsigned long long *dt_word() const { return word(apk::kWordStageDt); }
+  unsigned long long *bad_count_word() const { return word(apk::kWordStageBad); }
+  apk::DeviceBuf<double> d_partial;       // reduction partials
+  apk::DeviceBuf<unsigned char> d_mark;   // FOFC cell marks
+  void *h_pinned = nullptr;          // kPinnedBytes of pinned host staging, laid out by the kPin* names above
+  unsigned long long *pinned_u64() const { return static_cast<unsigned long long *>(h_pinned); }
+  double *pinned_history() const { return reinterpret_cast<double *>(static_cast<char *>(h_pinned) + apk::kPinHistory); }
+  double *pinned_sums() const { return reinterpret_cast<double *>(static_cast<char *>(h_pinned) + apk::kPinSums); }
+  unsigned *pinned_polled_flags() const { return reinterpret_cast<unsigned *>(static_cast<char *>(h_pinned) + apk::kPinPolledFlags); }
   // End-of-cycle gather (capi.hip: cycle_gather_kernel): ONE small kernel writes the stage's time-step word, the flag
   // words and the per-block tag criteria straight into pinned host memory and leaves the device words ready for the
   // next cycle (+max / 0) -- instead of two device-to-host copies, two fills and the next cycle's device-to-device reset
@@ -77,22 +134,19 @@ struct apk_ctx {
   // holds; everything that reduces into those words goes through prepare_dt_word / the tag launch, which clear them.
   unsigned long long *h_pinned_dev = nullptr;  // device address of h_pinned (null: no mapping, copies as before)
   double *h_partial_dev = nullptr;             // device address of h_partial
-  unsigned long long *d_tagmax = nullptr;      // per-block criterion maxima of apk_tag_blocks (bit patterns), own buffer
-  size_t tagmax_cap = 0;
-  // the minimum apk_stage_dt_flags_read last took out of word 4 (the read resets the word): repeated reads, and a following
-  // apk_stage_dt_read, return it until the next reduction into the word starts (prepare_dt_word)
+  apk::DeviceBuf<unsigned long long> d_tagmax;  // per-block criterion maxima of apk_tag_blocks (bit patterns), own buffer
+  // the minimum apk_stage_dt_flags_read last took out of the time-step word (the read resets the word): repeated reads,
+  // and a following apk_stage_dt_read, return it until the next reduction into the word starts (prepare_dt_word)
   double last_stage_min = 0.0;
   bool last_stage_min_valid = false;
-  bool dt_word_clean = false;                  // word 4 holds +max ...
+  bool dt_word_clean = false;                  // the time-step word holds +max ...
   hipStream_t clean_stream = nullptr;          // ... as of the gather enqueued on this stream (another stream: reset again)
   int tag_words_clean = 0;                     // the first n words of d_tagmax hold 0
   int tags_pending = 0;                        // criteria of this many blocks reduced, not yet in h_partial
-  double *h_partial = nullptr;       // pinned host mirror of d_partial (per-block reductions read back every cycle)
+  double *h_partial = nullptr;       // pinned host mirror of d_tagmax (the per-block criteria, read back every cycle)
   size_t h_partial_cap = 0;
-  double *d_du = nullptr;            // fused path: flux-difference accumulator
-  size_t du_cap = 0;                 // in doubles
-  double *d_mflux = nullptr;         // fused path with passive scalars: mass flux per face, [3][nblocks][sn]
-  size_t mflux_cap = 0;
+  apk::DeviceBuf<double> d_du;       // fused path: flux-difference accumulator
+  apk::DeviceBuf<double> d_mflux;    // fused path with passive scalars: mass flux per face, [3][nblocks][sn]
   // optional kernel timing (apk_kernel_timing_*)
   bool timing_on = false;
   struct TimedSpan {
@@ -133,26 +187,45 @@ inline int set_err(apk_ctx *ctx, int code, const char *what, hipError_t e = hipS
   return code;
 }
 
-// at least n doubles in ctx->d_partial (contents are not kept).  A failure is APK_ERR_DEVICE with the words "partial
-// buffer", or with hip_words the failed call and HIP's name for the error, as APK_HIP_TRY words it
-inline int ensure_partial_doubles(apk_ctx *ctx, size_t n, bool hip_words = false) {
-  if (ctx->partial_cap >= n) return APK_OK;
-  if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-  ctx->d_partial = nullptr;
-  ctx->partial_cap = 0;
-  const hipError_t e = hipMalloc(&ctx->d_partial, n * sizeof(double));
-  if (e != hipSuccess)
-    return hip_words ? set_err(ctx, APK_ERR_DEVICE, "hipMalloc(&ctx->d_partial, n * sizeof(double))", e)
-                     : set_err(ctx, APK_ERR_DEVICE, "partial buffer");
-  ctx->partial_cap = n;
-  return APK_OK;
-}
-
 #define APK_HIP_TRY(ctx, expr)                                              \
   do {                                                                      \
     hipError_t e__ = (expr);                                                \
     if (e__ != hipSuccess) return apk::set_err((ctx), APK_ERR_DEVICE, #expr, e__); \
   } while (0)
+
+template <class T>
+int DeviceBuf<T>::reserve(apk_ctx *ctx, size_t n, hipStream_t s) {
+  if (cap >= n) return APK_OK;
+  if (p) (void)hipStreamSynchronize(s);
+  release();
+  APK_HIP_TRY(ctx, hipMalloc(&p, n * sizeof(T)));
+  cap = n;
+  return APK_OK;
+}
+
+// One-shot minimum: min_seed puts the neutral element into the word, the caller's kernel reduces into ctx->min_word(),
+// min_fetch waits for it and returns the minimum.
+inline int min_seed(apk_ctx *ctx, double seed, hipStream_t s) {
+  unsigned long long *h = ctx->pinned_u64() + kPinSeed;
+  std::memcpy(h, &seed, sizeof(seed));
+  APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->min_word(), h, sizeof(seed), hipMemcpyHostToDevice, s));
+  return APK_OK;
+}
+inline int min_fetch(apk_ctx *ctx, double *m, hipStream_t s) {
+  unsigned long long *h = ctx->pinned_u64() + kPinMin;
+  APK_HIP_TRY(ctx, hipMemcpyAsync(h, ctx->min_word(), sizeof(*m), hipMemcpyDeviceToHost, s));
+  APK_HIP_TRY(ctx, hipStreamSynchronize(s));
+  std::memcpy(m, h, sizeof(*m));
+  return APK_OK;
+}
+// A counter word (kWordCounter, kWordStageBad), zeroed before the kernel that counted in it was launched: read back.
+inline int counter_fetch(apk_ctx *ctx, int w, unsigned long long *n, hipStream_t s) {
+  unsigned long long *h = ctx->pinned_u64() + w;
+  APK_HIP_TRY(ctx, hipMemcpyAsync(h, ctx->word(w), sizeof(*n), hipMemcpyDeviceToHost, s));
+  APK_HIP_TRY(ctx, hipStreamSynchronize(s));
+  *n = *h;
+  return APK_OK;
+}
 
 // ---- kernel launchers implemented in the .hip translation units ---------------------
 // input of the boundary-plane fluxes taken from the conserved state (flux_kernel.hpp: face_states_from_cons)
@@ -221,7 +294,7 @@ int launch_copy_regions(const apk_copy_plan &plan, hipStream_t s, int c2p_fluid 
 int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
                        const apk_stage_args &a, double dedner_coeff, hipStream_t s, const char *&why);
 
-// +max into the stage's time-step word (word 4) before a kernel reduces into it -- unless the stream already holds it
+// +max into the stage's time-step word (kWordStageDt) before a kernel reduces into it -- unless the stream already holds it
 int prepare_dt_word(apk_ctx *ctx, hipStream_t s);
 // the gather described at apk_ctx::h_pinned_dev: time-step word + flag words (+ pending tag criteria) to the host
 int launch_cycle_gather(apk_ctx *ctx, hipStream_t s);

@@ -99,21 +99,11 @@ bool same_shape(const apk_pack *a, const apk_pack *b) {
          x.nk == y.nk && x.ng == y.ng && x.sj == y.sj && x.sk == y.sk && x.sn == y.sn;
 }
 
-int ensure_mark(apk_ctx *ctx, size_t n) {
-  if (ctx->mark_cap >= n) return APK_OK;
-  if (ctx->d_mark) (void)hipFree(ctx->d_mark);
-  ctx->d_mark = nullptr;
-  ctx->mark_cap = 0;
-  APK_HIP_TRY(ctx, hipMalloc(&ctx->d_mark, n));
-  ctx->mark_cap = n;
-  return APK_OK;
-}
-
 }  // namespace
 
 namespace apk {
 namespace {
-// word 4 = the stage's time-step minimum, word 5 = the two flag words; h = pinned host memory (device address)
+// u64 = the context's device words, h = its pinned host block (device address): apk_internal.hpp names the layout
 __global__ void cycle_gather_kernel(unsigned long long *u64, unsigned long long *h, const unsigned long long *tag_words, double *h_tags,
                                     int ntags) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -122,10 +112,10 @@ __global__ void cycle_gather_kernel(unsigned long long *u64, unsigned long long 
     const_cast<unsigned long long *>(tag_words)[t] = 0ull;
   }
   if (t == 0) {
-    h[4] = u64[4];
-    h[5] = u64[5];
-    u64[4] = u64[15];                                  // +max: ready for the next reduction
-    reinterpret_cast<unsigned *>(u64 + 5)[0] = 0u;     // latched flags handed over ([1], the trial stage's, stays)
+    h[kWordStageDt] = u64[kWordStageDt];
+    h[kWordFlags] = u64[kWordFlags];
+    u64[kWordStageDt] = u64[kWordPlusMax];                  // +max: ready for the next reduction
+    reinterpret_cast<unsigned *>(u64 + kWordFlags)[0] = 0u;  // latched flags handed over ([1], the trial stage's, stays)
   }
 }
 }  // namespace
@@ -133,7 +123,7 @@ __global__ void cycle_gather_kernel(unsigned long long *u64, unsigned long long 
 int prepare_dt_word(apk_ctx *ctx, hipStream_t s) {
   if (!ctx->dt_word_clean || ctx->clean_stream != s) {
     // +max (neutral element of the min), device to device so the launch path never blocks the host
-    if (hipMemcpyAsync(ctx->d_u64 + 4, ctx->d_u64 + 15, sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return APK_ERR_DEVICE;
+    if (hipMemcpyAsync(ctx->dt_word(), ctx->word(kWordPlusMax), sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return APK_ERR_DEVICE;
   }
   ctx->dt_word_clean = false;  // (about to be reduced into)
   ctx->last_stage_min_valid = false;
@@ -144,7 +134,7 @@ int launch_cycle_gather(apk_ctx *ctx, hipStream_t s) {
   const int ntags = (ctx->tags_pending > 0 && ctx->h_partial_dev) ? ctx->tags_pending : 0;
   const int blocks = ntags > 0 ? (ntags + 255) / 256 : 1;
   hipLaunchKernelGGL(cycle_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ctx->d_u64, ctx->h_pinned_dev,
-                     ctx->d_tagmax, ctx->h_partial_dev, ntags);
+                     ctx->d_tagmax.p, ctx->h_partial_dev, ntags);
   if (hipGetLastError() != hipSuccess) return APK_ERR_DEVICE;
   ctx->dt_word_clean = true;
   ctx->clean_stream = s;
@@ -186,18 +176,18 @@ int apk_create(apk_ctx **out) {
     delete ctx;
     return APK_ERR_NO_DEVICE;
   }
-  if (hipMalloc(&ctx->d_u64, 16 * sizeof(unsigned long long)) != hipSuccess ||
-      hipHostMalloc(&ctx->h_pinned, 256, hipHostMallocDefault) != hipSuccess) {
+  if (hipMalloc(&ctx->d_u64, kNumWords * sizeof(unsigned long long)) != hipSuccess ||
+      hipHostMalloc(&ctx->h_pinned, kPinnedBytes, hipHostMallocDefault) != hipSuccess) {
     apk_destroy(ctx);
     return APK_ERR_DEVICE;
   }
-  // the flag words ([0] latched, [1] trial stage) are word 5 of d_u64, next to the stage's time-step word 4: one
-  // 16-byte read-back fetches both at the end of a cycle (apk_stage_dt_flags_read)
-  ctx->d_flags = reinterpret_cast<unsigned *>(ctx->d_u64 + 5);
-  (void)hipMemset(ctx->d_u64, 0, 16 * sizeof(unsigned long long));
+  // the flag words ([0] latched, [1] trial stage) follow the stage's time-step word: one 16-byte read-back fetches
+  // both at the end of a cycle (apk_stage_dt_flags_read)
+  ctx->d_flags = reinterpret_cast<unsigned *>(ctx->word(kWordFlags));
+  (void)hipMemset(ctx->d_u64, 0, kNumWords * sizeof(unsigned long long));
   {
-    const double huge = 1.7976931348623157e308;  // word 15: constant +max, the neutral element of the dt min
-    (void)hipMemcpy(ctx->d_u64 + 15, &huge, sizeof(double), hipMemcpyHostToDevice);
+    const double huge = 1.7976931348623157e308;  // the neutral element of the dt min
+    (void)hipMemcpy(ctx->word(kWordPlusMax), &huge, sizeof(double), hipMemcpyHostToDevice);
   }
   {
     void *dev = nullptr;  // (pinned host memory is mapped into the device's address space by default; if not: copies)
@@ -211,11 +201,11 @@ int apk_create(apk_ctx **out) {
 void apk_destroy(apk_ctx *ctx) {
   if (!ctx) return;
   if (ctx->d_u64) (void)hipFree(ctx->d_u64);  // (d_flags points into it)
-  if (ctx->d_mflux) (void)hipFree(ctx->d_mflux);
-  if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-  if (ctx->d_tagmax) (void)hipFree(ctx->d_tagmax);
-  if (ctx->d_mark) (void)hipFree(ctx->d_mark);
-  if (ctx->d_du) (void)hipFree(ctx->d_du);
+  ctx->d_mflux.release();
+  ctx->d_partial.release();
+  ctx->d_tagmax.release();
+  ctx->d_mark.release();
+  ctx->d_du.release();
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->h_partial) (void)hipHostFree(ctx->h_partial);
   for (auto &sp : ctx->spans) {
@@ -398,12 +388,10 @@ int apk_stage_form(const apk_pack_desc *shape, const apk_stage_args *args, apk_s
 
 int apk_stage_unphysical_read(apk_ctx *ctx, long long *count, apk_stream_t stream) {
   if (!ctx || !count) return APK_ERR_INVALID;
-  hipStream_t s = as_stream(stream);
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
-  APK_HIP_TRY(ctx, hipMemcpyAsync(h + 6, ctx->d_u64 + 6, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  APK_HIP_TRY(ctx, hipStreamSynchronize(s));
-  *count = (long long)h[6];
-  return APK_OK;
+  unsigned long long n = 0;
+  const int rc = counter_fetch(ctx, kWordStageBad, &n, as_stream(stream));
+  *count = (long long)n;
+  return rc;
 }
 
 // The three older queries: each describes a hypothetical whole stage on this pack, asks the plan and reads the form.
@@ -462,7 +450,7 @@ int apk_cons_to_prim_dt_skip(apk_ctx *ctx, const apk_pack *md, int fluid, const 
       md->view.nhydro != ((fluid == APK_FLUID_EULER) ? 5 : 9))
     return set_err(ctx, APK_ERR_INVALID, "apk_cons_to_prim_dt: bad argument");
   hipStream_t s = as_stream(stream);
-  unsigned long long *dt_bits = ctx->d_u64 + 4;  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
+  unsigned long long *dt_bits = ctx->dt_word();  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
   if (apk::prepare_dt_word(ctx, s) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "time-step word reset", hipGetLastError());
   ScopedTiming timing(ctx, APK_T_C2P, s);
   int rc = launch_cons_to_prim(md->view, fluid, *eos, ctx->d_flags, s, false, nullptr, 0, false, face_neighbor, dt_bits, ghost_depth);
@@ -481,7 +469,7 @@ int apk_cons_to_prim_dt_select(apk_ctx *ctx, const apk_pack *md, int fluid, cons
   if (!eos_is_lean(*eos) || eos->dfloor > 0.0 || eos->efloor > 0.0)
     return set_err(ctx, APK_ERR_UNSUPPORTED, "apk_cons_to_prim_dt_select: floors / ceilings need the full ConsToPrim");
   hipStream_t s = as_stream(stream);
-  unsigned long long *dt_bits = ctx->d_u64 + 4;  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
+  unsigned long long *dt_bits = ctx->dt_word();  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
   if (apk::prepare_dt_word(ctx, s) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "time-step word reset", hipGetLastError());
   ScopedTiming timing(ctx, APK_T_C2P, s);
   // (store_vars = every primitive is the pass apk_cons_to_prim_dt_skip runs; ~0u is the kernels' word for it)
@@ -519,7 +507,7 @@ int apk_cons_to_prim_faces_dt(apk_ctx *ctx, const apk_pack *md, int fluid, const
       md->view.nhydro != ((fluid == APK_FLUID_EULER) ? 5 : 9))
     return set_err(ctx, APK_ERR_INVALID, "apk_cons_to_prim_faces_dt: bad argument");
   hipStream_t s = as_stream(stream);
-  unsigned long long *dt_bits = ctx->d_u64 + 4;  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
+  unsigned long long *dt_bits = ctx->dt_word();  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
   if (apk::prepare_dt_word(ctx, s) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "time-step word reset", hipGetLastError());
   ScopedTiming timing(ctx, APK_T_C2P, s);
   int rc = launch_cons_to_prim(md->view, fluid, *eos, ctx->d_flags, s, false, nullptr, 0, true, face_neighbor, dt_bits);
@@ -556,11 +544,11 @@ int apk_stage_dt_read(apk_ctx *ctx, double cfl, double *dt_out, apk_stream_t str
     return APK_OK;
   }
   hipStream_t s = as_stream(stream);
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
-  APK_HIP_TRY(ctx, hipMemcpyAsync(h + 4, ctx->d_u64 + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  unsigned long long *h = ctx->pinned_u64() + kWordStageDt;
+  APK_HIP_TRY(ctx, hipMemcpyAsync(h, ctx->dt_word(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   APK_HIP_TRY(ctx, hipStreamSynchronize(s));
   double m;
-  std::memcpy(&m, h + 4, sizeof(m));
+  std::memcpy(&m, h, sizeof(m));
   *dt_out = cfl * m;  // hydro.cpp:909
   return APK_OK;
 }
@@ -571,22 +559,15 @@ int apk_estimate_timestep(apk_ctx *ctx, const apk_pack *md, int fluid, const apk
       md->view.nhydro != ((fluid == APK_FLUID_EULER) ? 5 : 9))
     return set_err(ctx, APK_ERR_INVALID, "apk_estimate_timestep: bad argument");
   hipStream_t s = as_stream(stream);
-  const double huge = std::numeric_limits<double>::max();
-  unsigned long long bits;
-  std::memcpy(&bits, &huge, sizeof(bits));
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
-  h[0] = bits;
-  APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_u64, h, sizeof(bits), hipMemcpyHostToDevice, s));
-  int rc;
+  int rc = min_seed(ctx, std::numeric_limits<double>::max(), s);
+  if (rc != APK_OK) return rc;
   {
     ScopedTiming timing(ctx, APK_T_MIN_DT, s);
-    rc = launch_min_dt(md->view, fluid, eos->gamma, ctx->d_u64, s);
+    rc = launch_min_dt(md->view, fluid, eos->gamma, ctx->min_word(), s);
   }
   if (rc != APK_OK) return set_err(ctx, rc, "min_dt kernel launch failed", hipGetLastError());
-  APK_HIP_TRY(ctx, hipMemcpyAsync(h + 1, ctx->d_u64, sizeof(bits), hipMemcpyDeviceToHost, s));
-  APK_HIP_TRY(ctx, hipStreamSynchronize(s));
   double m;
-  std::memcpy(&m, h + 1, sizeof(m));
+  if ((rc = min_fetch(ctx, &m, s)) != APK_OK) return rc;
   *dt_out = cfl * m;  // hydro.cpp:909
   return APK_OK;
 }
@@ -665,17 +646,11 @@ int apk_estimate_diffusion_timestep_v2(apk_ctx *ctx, const apk_pack *md, const a
     dt = std::fmin(dt, iso_fixed(cfg->thermal_diff_coeff));
   } else if (cfg->conduction != APK_COND_NONE) {  // the general branch: anisotropic, or Spitzer
     hipStream_t s = as_stream(stream);
-    unsigned long long bits;
-    std::memcpy(&bits, &huge, sizeof(bits));
-    auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
-    h[0] = bits;
-    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_u64, h, sizeof(bits), hipMemcpyHostToDevice, s));
-    rc = launch_cond_dt(v, cfg->conduction, cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, sp, ctx->d_u64, s);
+    if ((rc = min_seed(ctx, huge, s)) != APK_OK) return rc;
+    rc = launch_cond_dt(v, cfg->conduction, cfg->thermal_diff_coeff, cfg->conduction_sat_prefac, sp, ctx->min_word(), s);
     if (rc != APK_OK) return set_err(ctx, rc, "conduction dt kernel launch failed", hipGetLastError());
-    APK_HIP_TRY(ctx, hipMemcpyAsync(h + 1, ctx->d_u64, sizeof(bits), hipMemcpyDeviceToHost, s));
-    APK_HIP_TRY(ctx, hipStreamSynchronize(s));
     double m;
-    std::memcpy(&m, h + 1, sizeof(m));
+    if ((rc = min_fetch(ctx, &m, s)) != APK_OK) return rc;
     dt = std::fmin(dt, cfl_diff * fac * m);
   }
   if (cfg->viscosity != APK_VISC_NONE) dt = std::fmin(dt, iso_fixed(cfg->mom_diff_coeff));
@@ -766,23 +741,19 @@ int apk_first_order_flux_correct(apk_ctx *ctx, const apk_pack *u0, const apk_pac
   for (int d = 0; d < u0->view.ndim; ++d)
     if (!u0->have_flux[d]) return set_err(ctx, APK_ERR_INVALID, "u0 pack has no flux arrays");
   hipStream_t s = as_stream(stream);
-  int rc = ensure_mark(ctx, (size_t)u0->view.nblocks * (size_t)u0->view.sn);
+  int rc = ctx->d_mark.reserve(ctx, (size_t)u0->view.nblocks * (size_t)u0->view.sn, s);
   if (rc != APK_OK) return rc;
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
   long long total = 0;
   unsigned long long corrected = 0;
   int attempts = 0;
   do {  // hydro.cpp:1265-1339: <= 4 attempts, one host sync per attempt
-    APK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_u64 + 2, 0, sizeof(unsigned long long), s));
-    rc = launch_fofc_mark(u0->view, u1->view, fluid, gam0, gam1, beta_dt, attempts, ctx->d_mark,
-                          ctx->d_u64 + 2, s);
+    APK_HIP_TRY(ctx, hipMemsetAsync(ctx->counter_word(), 0, sizeof(unsigned long long), s));
+    rc = launch_fofc_mark(u0->view, u1->view, fluid, gam0, gam1, beta_dt, attempts, ctx->d_mark.p,
+                          ctx->counter_word(), s);
     if (rc != APK_OK) return set_err(ctx, rc, "fofc mark kernel launch failed", hipGetLastError());
-    APK_HIP_TRY(ctx, hipMemcpyAsync(h + 2, ctx->d_u64 + 2, sizeof(unsigned long long),
-                                    hipMemcpyDeviceToHost, s));
-    APK_HIP_TRY(ctx, hipStreamSynchronize(s));
-    corrected = h[2];
+    if ((rc = counter_fetch(ctx, kWordCounter, &corrected, s)) != APK_OK) return rc;
     if (corrected > 0) {
-      rc = launch_fofc_fix(u0->view, fluid, eos->gamma, c_h, ctx->d_mark, s);
+      rc = launch_fofc_fix(u0->view, fluid, eos->gamma, c_h, ctx->d_mark.p, s);
       if (rc != APK_OK) return set_err(ctx, rc, "fofc fix kernel launch failed", hipGetLastError());
     }
     total += (long long)corrected;
@@ -796,14 +767,13 @@ int apk_count_unphysical(apk_ctx *ctx, const apk_pack *md, int fluid, long long 
   if (!ctx || !md || !count || md->view.nhydro != ((fluid == APK_FLUID_EULER) ? 5 : 9))
     return set_err(ctx, APK_ERR_INVALID, "apk_count_unphysical: bad argument");
   hipStream_t s = as_stream(stream);
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
-  APK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_u64 + 2, 0, sizeof(unsigned long long), s));
-  int rc = launch_count_unphysical(md->view, fluid, ctx->d_u64 + 2, s);
+  APK_HIP_TRY(ctx, hipMemsetAsync(ctx->counter_word(), 0, sizeof(unsigned long long), s));
+  int rc = launch_count_unphysical(md->view, fluid, ctx->counter_word(), s);
   if (rc != APK_OK) return set_err(ctx, rc, "count_unphysical launch failed", hipGetLastError());
-  APK_HIP_TRY(ctx, hipMemcpyAsync(h + 2, ctx->d_u64 + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  APK_HIP_TRY(ctx, hipStreamSynchronize(s));
-  *count = (long long)h[2];
-  return APK_OK;
+  unsigned long long n = 0;
+  rc = counter_fetch(ctx, kWordCounter, &n, s);
+  *count = (long long)n;
+  return rc;
 }
 
 int apk_history(apk_ctx *ctx, const apk_pack *md, int fluid, double *out8, apk_stream_t stream) {
@@ -812,12 +782,12 @@ int apk_history(apk_ctx *ctx, const apk_pack *md, int fluid, double *out8, apk_s
   hipStream_t s = as_stream(stream);
   int nwg = 0;
   launch_history(md->view, fluid, nullptr, &nwg, nullptr, s);
-  int rc = ensure_partial_doubles(ctx, (size_t)nwg * 8 + 8, true);
+  int rc = ctx->d_partial.reserve(ctx, (size_t)nwg * 8 + 8, s);
   if (rc != APK_OK) return rc;
-  double *d_out = ctx->d_partial + (size_t)nwg * 8;
-  rc = launch_history(md->view, fluid, ctx->d_partial, &nwg, d_out, s);
+  double *d_out = ctx->d_partial.p + (size_t)nwg * 8;
+  rc = launch_history(md->view, fluid, ctx->d_partial.p, &nwg, d_out, s);
   if (rc != APK_OK) return set_err(ctx, rc, "history kernel launch failed", hipGetLastError());
-  auto *h = static_cast<double *>(ctx->h_pinned) + 8;
+  double *h = ctx->pinned_history();
   APK_HIP_TRY(ctx, hipMemcpyAsync(h, d_out, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
   APK_HIP_TRY(ctx, hipStreamSynchronize(s));
   std::memcpy(out8, h, 8 * sizeof(double));
@@ -827,32 +797,33 @@ int apk_history(apk_ctx *ctx, const apk_pack *md, int fluid, double *out8, apk_s
 int apk_stage_dt_flags_read(apk_ctx *ctx, double cfl, double *dt_out, unsigned *flags, apk_stream_t stream) {
   if (!ctx || !dt_out || !flags) return APK_ERR_INVALID;
   hipStream_t s = as_stream(stream);
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
+  const unsigned long long *h = ctx->pinned_u64();
   if (ctx->last_stage_min_valid) {  // (already consumed: the word on the device has been reset)
     *dt_out = cfl * ctx->last_stage_min;
     return apk_poll_device_flags(ctx, flags, stream);
   }
   if (ctx->h_pinned_dev) {
-    // one small kernel hands words 4 / 5 (and the tag criteria an apk_tag_blocks_begin left pending) to the host and
-    // leaves the device words ready for the next cycle
+    // one small kernel hands the time-step and flag words (and the tag criteria an apk_tag_blocks_begin left pending) to
+    // the host and leaves the device words ready for the next cycle
     if (apk::launch_cycle_gather(ctx, s) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "cycle gather launch", hipGetLastError());
   } else {
-    // words 4 (the stage's minimum) and 5 (the flag words) in one copy
-    APK_HIP_TRY(ctx, hipMemcpyAsync(h + 4, ctx->d_u64 + 4, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    // the stage's minimum and the flag words that follow it in one copy
+    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned_u64() + kWordStageDt, ctx->dt_word(), 2 * sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, s));
     APK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(unsigned), s));
-    // (the same consume-on-read semantics as the gather kernel's: word 4 back to +max, ready for the next reduction)
-    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_u64 + 4, ctx->d_u64 + 15, sizeof(double), hipMemcpyDeviceToDevice, s));
+    // (the same consume-on-read semantics as the gather kernel's: the word back to +max, ready for the next reduction)
+    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->dt_word(), ctx->word(kWordPlusMax), sizeof(double), hipMemcpyDeviceToDevice, s));
     ctx->dt_word_clean = true;
     ctx->clean_stream = s;
   }
   APK_HIP_TRY(ctx, hipStreamSynchronize(s));
   double m;
-  std::memcpy(&m, h + 4, sizeof(m));
+  std::memcpy(&m, h + kWordStageDt, sizeof(m));
   ctx->last_stage_min = m;
   ctx->last_stage_min_valid = true;
   *dt_out = cfl * m;  // hydro.cpp:909
   unsigned f[2];
-  std::memcpy(f, h + 5, sizeof(f));
+  std::memcpy(f, h + kWordFlags, sizeof(f));
   *flags = f[0];
   return APK_OK;
 }
@@ -879,7 +850,7 @@ int apk_trial_flags(apk_ctx *ctx, int keep, apk_stream_t stream) {
 int apk_poll_device_flags(apk_ctx *ctx, unsigned *flags, apk_stream_t stream) {
   if (!ctx || !flags) return APK_ERR_INVALID;
   hipStream_t s = as_stream(stream);
-  auto *h = reinterpret_cast<unsigned *>(static_cast<char *>(ctx->h_pinned) + 192);
+  unsigned *h = ctx->pinned_polled_flags();
   APK_HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   APK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(unsigned), s));
   APK_HIP_TRY(ctx, hipStreamSynchronize(s));

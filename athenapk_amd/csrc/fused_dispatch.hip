@@ -54,18 +54,8 @@ int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
   sp.mflux = nullptr;
   if (u0.nvar != u0.nhydro) {
     // passive scalars: the sweeps leave the mass fluxes in a workspace of the handle
-    const size_t need = 3 * (size_t)u0.nblocks * (size_t)u0.sn;
-    if (need > ctx->mflux_cap) {
-      if (ctx->d_mflux) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(ctx->d_mflux);
-      }
-      ctx->d_mflux = nullptr;
-      ctx->mflux_cap = 0;
-      if (hipMalloc(&ctx->d_mflux, need * sizeof(double)) != hipSuccess) return APK_ERR_DEVICE;
-      ctx->mflux_cap = need;
-    }
-    sp.mflux = ctx->d_mflux;
+    if (ctx->d_mflux.reserve(ctx, 3 * (size_t)u0.nblocks * (size_t)u0.sn, s) != APK_OK) return APK_ERR_DEVICE;
+    sp.mflux = ctx->d_mflux.p;
   }
   sp.gamma = a.eos.gamma;
   sp.c_h = a.c_h;
@@ -81,7 +71,7 @@ int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
   sp.ctx = ctx;
   sp.eos = a.eos;
   sp.flags = ctx->d_flags + (a.trial ? 1 : 0);
-  sp.dt_bits = ctx->d_u64 + 4;  // word 4: min of the finishing sweep (apk_stage_dt_read)
+  sp.dt_bits = ctx->dt_word();  // min of the finishing sweep (apk_stage_dt_read)
   sp.bad_count = nullptr;
   sp.out_delta = a.cons_out_delta;
   sp.face_nbr = a.face_neighbor;
@@ -95,8 +85,8 @@ int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
   }
   // (only the stage whose primitives go out of place may drop its conserved result; a windowed phase keeps everything)
   sp.cons_store = (a.fill_derived == 2 && !a.trial && a.cons_out_delta == 0) ? a.cons_store : 0;
-  if (a.count_unphysical) {     // word 6: cells failing FirstOrderFluxCorrect's test (apk_stage_unphysical_read)
-    sp.bad_count = ctx->d_u64 + 6;
+  if (a.count_unphysical) {     // cells failing FirstOrderFluxCorrect's test (apk_stage_unphysical_read)
+    sp.bad_count = ctx->bad_count_word();
     if (a.phase != 2 && hipMemsetAsync(sp.bad_count, 0, sizeof(unsigned long long), s) != hipSuccess) return APK_ERR_DEVICE;
   }
   sp.prim_to_u1 = (a.fill_derived >= 2) ? 1 : 0;
@@ -110,18 +100,9 @@ int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
     if (prepare_dt_word(ctx, s) != APK_OK) return APK_ERR_DEVICE;
   }
   if (u0.ndim > 1) {
-    const size_t need = (size_t)u0.nblocks * (size_t)u0.nvar * (size_t)u0.sn;
-    if (need > ctx->du_cap) {  // workspace owned by the handle, grown on demand
-      if (ctx->d_du) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(ctx->d_du);
-      }
-      ctx->d_du = nullptr;
-      ctx->du_cap = 0;
-      if (hipMalloc(&ctx->d_du, need * sizeof(double)) != hipSuccess) return APK_ERR_DEVICE;
-      ctx->du_cap = need;
-    }
-    sp.du = ctx->d_du;
+    // workspace owned by the handle, grown on demand
+    if (ctx->d_du.reserve(ctx, (size_t)u0.nblocks * (size_t)u0.nvar * (size_t)u0.sn, s) != APK_OK) return APK_ERR_DEVICE;
+    sp.du = ctx->d_du.p;
   }
   if (a.cfg.fluid == APK_FLUID_EULER) {
     if (a.cfg.riemann == APK_RS_HLLE) return launch_fused_euler_hlle(u0, u1, a.cfg.recon, sp, plan, s);

@@ -670,13 +670,10 @@ int apk_tag_blocks_begin(apk_ctx *ctx, const apk_pack *md, int criterion, int *p
 namespace {
 // the per-block maxima' words and their pinned host copy, cleared for a new reduction
 int tag_words_prepare(apk_ctx *ctx, int nb, hipStream_t s) {
-  if (ctx->tagmax_cap < (size_t)nb) {
-    if (ctx->d_tagmax) (void)hipFree(ctx->d_tagmax);
-    ctx->d_tagmax = nullptr;
-    ctx->tagmax_cap = 0;
+  if (ctx->d_tagmax.cap < (size_t)nb) {  // (a new buffer, with slack: nothing of it is known to hold 0)
     ctx->tag_words_clean = 0;
-    APK_HIP_TRY(ctx, hipMalloc(&ctx->d_tagmax, sizeof(unsigned long long) * (nb + 64)));
-    ctx->tagmax_cap = nb + 64;
+    const int rc = ctx->d_tagmax.reserve(ctx, (size_t)nb + 64, s);
+    if (rc != APK_OK) return rc;
   }
   if (ctx->h_partial_cap < (size_t)nb) {  // (pinned: a pageable destination costs a staging copy every cycle)
     if (ctx->h_partial) (void)hipHostFree(ctx->h_partial);
@@ -690,7 +687,7 @@ int tag_words_prepare(apk_ctx *ctx, int nb, hipStream_t s) {
     else (void)hipGetLastError();
   }
   // (the gather at the end of the previous cycle left the words at zero: apk_ctx::tag_words_clean)
-  if (ctx->tag_words_clean < nb || ctx->clean_stream != s) APK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_tagmax, 0, sizeof(unsigned long long) * nb, s));
+  if (ctx->tag_words_clean < nb || ctx->clean_stream != s) APK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_tagmax.p, 0, sizeof(unsigned long long) * nb, s));
   ctx->tag_words_clean = 0;
   return APK_OK;
 }
@@ -701,7 +698,7 @@ int tag_words_request(apk_ctx *ctx, int nb, hipStream_t s, int *pending) {
     // reads that next -- the driver does --, else apk_tag_blocks_end fetches them
     ctx->tags_pending = nb;
   } else {
-    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partial, ctx->d_tagmax, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partial, ctx->d_tagmax.p, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
     ctx->tags_pending = 0;
   }
   *pending = 1;
@@ -724,7 +721,7 @@ int apk_tag_blocks_begin_skip(apk_ctx *ctx, const apk_pack *md, int criterion, c
     return set_err(ctx, APK_ERR_UNSUPPORTED, "xyvelocity_gradient needs at least two dimensions");
   const int rc = tag_words_prepare(ctx, nb, s);
   if (rc != APK_OK) return rc;
-  unsigned long long *d_max = ctx->d_tagmax;
+  unsigned long long *d_max = ctx->d_tagmax.p;
   const int kchunks = (pv.nx3 >= 12 && nb < 4096) ? 3 : 1;
   const dim3 grid = rect_grid(pv.nx1 + 2, pv.nx2 + 2, nb * kchunks), block(64, 4, 1);
   if (criterion == APK_TAG_PRESSURE_GRADIENT)
@@ -751,7 +748,7 @@ int apk_tag_blocks_dt_from_cons(apk_ctx *ctx, const apk_pack *md, int fluid, con
   int rc = tag_words_prepare(ctx, nb, s);
   if (rc != APK_OK) return rc;
   if (apk::prepare_dt_word(ctx, s) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "time-step word reset", hipGetLastError());
-  rc = apk::launch_tag_pgrad_from_cons(pv, fluid, *eos, ctx->d_flags, ctx->d_u64 + 4, ctx->d_tagmax, face_neighbor, s);
+  rc = apk::launch_tag_pgrad_from_cons(pv, fluid, *eos, ctx->d_flags, ctx->dt_word(), ctx->d_tagmax.p, face_neighbor, s);
   if (rc != APK_OK) return set_err(ctx, rc, "tag_pgrad_from_cons kernel launch failed", hipGetLastError());
   return tag_words_request(ctx, nb, s, pending);
 }
@@ -770,7 +767,7 @@ int apk_tag_blocks_end(apk_ctx *ctx, int nblocks, int criterion, int pending, do
   }
   if ((size_t)nblocks > ctx->h_partial_cap) return set_err(ctx, APK_ERR_INVALID, "apk_tag_blocks_end without apk_tag_blocks_begin");
   if (ctx->tags_pending > 0) {  // (nobody gathered them meanwhile)
-    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partial, ctx->d_tagmax, sizeof(double) * ctx->tags_pending, hipMemcpyDeviceToHost,
+    APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partial, ctx->d_tagmax.p, sizeof(double) * ctx->tags_pending, hipMemcpyDeviceToHost,
                                     reinterpret_cast<hipStream_t>(stream)));
     ctx->tags_pending = 0;
   }

@@ -518,23 +518,17 @@ int apk_estimate_cooling_timestep(apk_ctx *ctx, const apk_pack *md, const apk_co
   }
   const PackView &v = md->view;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const double inf = INFINITY;
-  unsigned long long bits;
-  std::memcpy(&bits, &inf, sizeof(bits));
-  auto *h = static_cast<unsigned long long *>(ctx->h_pinned);
-  h[0] = bits;
-  APK_HIP_TRY(ctx, hipMemcpyAsync(ctx->d_u64, h, sizeof(bits), hipMemcpyHostToDevice, s));
+  int rc = min_seed(ctx, INFINITY, s);
+  if (rc != APK_OK) return rc;
   const int64_t ncell = interior_cells(v);
   if (ncell > 0) {
     const dim3 grid((unsigned)((ncell + 255) / 256)), block(256);
     const double gm1 = table->p.gamma - 1.0;
-    hipLaunchKernelGGL(cool_dt_kernel, grid, block, 0, s, v, table->dev, gm1, ctx->d_u64, ctx->d_flags);
+    hipLaunchKernelGGL(cool_dt_kernel, grid, block, 0, s, v, table->dev, gm1, ctx->min_word(), ctx->d_flags);
     if (hipGetLastError() != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "cooling time-step launch failed");
   }
-  APK_HIP_TRY(ctx, hipMemcpyAsync(h + 1, ctx->d_u64, sizeof(bits), hipMemcpyDeviceToHost, s));
-  APK_HIP_TRY(ctx, hipStreamSynchronize(s));
   double m;
-  std::memcpy(&m, h + 1, sizeof(m));
+  if ((rc = min_fetch(ctx, &m, s)) != APK_OK) return rc;
   *dt_out = cfl * m;
   return APK_OK;
 }

@@ -316,13 +316,13 @@ int apk_magnetic_tower_power_contribs(apk_ctx *ctx, const apk_pack *md, const ap
   if (v.nblocks == 0) return APK_OK;
   if (v.nblocks > 65535) return set_err(ctx, APK_ERR_UNSUPPORTED, "apk_magnetic_tower_power_contribs: more than 65535 blocks in a pack");
   const int P = contrib_groups((int64_t)v.nx1 * v.nx2 * v.nx3);
-  const int rc = ensure_partial_doubles(ctx, (size_t)v.nblocks * P * 2);
-  if (rc != APK_OK) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = ctx->d_partial.reserve(ctx, (size_t)v.nblocks * P * 2, s);
+  if (rc != APK_OK) return rc;
   ScopedTiming span(ctx, APK_T_TOWER_CONTRIBS, s);
   hipLaunchKernelGGL(tower_contribs_kernel, dim3((unsigned)P, (unsigned)v.nblocks), dim3(256), 0, s, v, *tower, *jet, block_xmin,
-                     ctx->d_partial);
-  hipLaunchKernelGGL(tower_contribs_final_kernel, dim3((unsigned)((2 * v.nblocks + 63) / 64)), dim3(64), 0, s, ctx->d_partial, P,
+                     ctx->d_partial.p);
+  hipLaunchKernelGGL(tower_contribs_final_kernel, dim3((unsigned)((2 * v.nblocks + 63) / 64)), dim3(64), 0, s, ctx->d_partial.p, P,
                      v.nblocks, contribs);
   if (hipGetLastError() != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "magnetic tower power contributions launch failed");
   return APK_OK;

@@ -226,18 +226,18 @@ int apk_agn_triggering_reduce(apk_ctx *ctx, const apk_pack *md, int fluid, const
   APK_HIP_TRY(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 4 * (size_t)v.nblocks, s));
   if (nboxes == 0) return APK_OK;
   const int P = block_sum_groups(max_box_cells);
-  const int rc = ensure_partial_doubles(ctx, (size_t)nboxes * P * 4);
+  const int rc = ctx->d_partial.reserve(ctx, (size_t)nboxes * P * 4, s);
   if (rc != APK_OK) return rc;
   const dim3 grid((unsigned)P, (unsigned)nboxes), block(256);
   if (cfg->mode == APK_TRIG_COLD_GAS) {  // (one sum; the other three slots are written as zeros)
     if (fluid == APK_FLUID_GLMMHD)
-      hipLaunchKernelGGL((trig_reduce_cold_kernel<APK_FLUID_GLMMHD>), grid, block, 0, s, v, *eos, *cfg, dt, boxes, block_xmin, ctx->d_partial, ctx->d_flags);
+      hipLaunchKernelGGL((trig_reduce_cold_kernel<APK_FLUID_GLMMHD>), grid, block, 0, s, v, *eos, *cfg, dt, boxes, block_xmin, ctx->d_partial.p, ctx->d_flags);
     else
-      hipLaunchKernelGGL((trig_reduce_cold_kernel<APK_FLUID_EULER>), grid, block, 0, s, v, *eos, *cfg, dt, boxes, block_xmin, ctx->d_partial, ctx->d_flags);
+      hipLaunchKernelGGL((trig_reduce_cold_kernel<APK_FLUID_EULER>), grid, block, 0, s, v, *eos, *cfg, dt, boxes, block_xmin, ctx->d_partial.p, ctx->d_flags);
   } else {
-    hipLaunchKernelGGL(trig_reduce_bondi_kernel, grid, block, 0, s, v, eos->gamma, cfg->accretion_radius, boxes, block_xmin, ctx->d_partial);
+    hipLaunchKernelGGL(trig_reduce_bondi_kernel, grid, block, 0, s, v, eos->gamma, cfg->accretion_radius, boxes, block_xmin, ctx->d_partial.p);
   }
-  block_sum_final_by_box<4>(ctx->d_partial, P, nboxes, v.nblocks, boxes, sums, s);
+  block_sum_final_by_box<4>(ctx->d_partial.p, P, nboxes, v.nblocks, boxes, sums, s);
   if (hipGetLastError() != hipSuccess) return set_err(ctx, APK_ERR_DEVICE, "AGN triggering reduction launch failed");
   return APK_OK;
 }

@@ -416,15 +416,16 @@ turb_apply_fill_kernel(PackView pv, const apk_fmft_block *blocks, double norm, d
 
 template <int NQ>
 int finish_sums(apk_ctx *ctx, int nwg, double *out, hipStream_t s) {
-  double *d_out = ctx->d_partial + (size_t)nwg * NQ;
+  static_assert(NQ <= kPinSumsMax, "the sums' pinned region (apk_internal.hpp) holds NQ doubles");
+  double *d_out = ctx->d_partial.p + (size_t)nwg * NQ;
   if (nwg > 8 * kMidGroups) {  // (callers reserve nwg * 4 + kMidGroups * 4 + 8 doubles)
     double *d_mid = d_out + NQ;
-    hipLaunchKernelGGL(mid_sum_kernel<NQ>, dim3(kMidGroups), dim3(256), 0, s, ctx->d_partial, nwg, d_mid);
+    hipLaunchKernelGGL(mid_sum_kernel<NQ>, dim3(kMidGroups), dim3(256), 0, s, ctx->d_partial.p, nwg, d_mid);
     hipLaunchKernelGGL(final_sum_kernel<NQ>, dim3(1), dim3(256), 0, s, d_mid, kMidGroups, d_out);
   } else {
-    hipLaunchKernelGGL(final_sum_kernel<NQ>, dim3(1), dim3(256), 0, s, ctx->d_partial, nwg, d_out);
+    hipLaunchKernelGGL(final_sum_kernel<NQ>, dim3(1), dim3(256), 0, s, ctx->d_partial.p, nwg, d_out);
   }
-  auto *h = static_cast<double *>(ctx->h_pinned) + 16;
+  double *h = ctx->pinned_sums();
   if (hipMemcpyAsync(h, d_out, NQ * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) return APK_ERR_DEVICE;
   if (hipStreamSynchronize(s) != hipSuccess) return APK_ERR_DEVICE;
   std::memcpy(out, h, NQ * sizeof(double));
@@ -455,7 +456,7 @@ int turb_apply_fill_impl(apk_ctx *ctx, const apk_pack *md, apk_fmft *f, double n
   for (const auto &b : md->h_blocks)
     if (store_prim && !b.prim) return set_err(ctx, APK_ERR_INVALID, "apk_turb_apply_fill: block without prim pointer");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  unsigned long long *dt_bits = ctx->d_u64 + 4;  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
+  unsigned long long *dt_bits = ctx->dt_word();  // the stage's word: apk_stage_dt_read / apk_stage_dt_flags_read
   if (estimate_dt && apk::prepare_dt_word(ctx, s) != APK_OK) return set_err(ctx, APK_ERR_DEVICE, "apk_turb_apply_fill", hipGetLastError());
   const dim3 g = igrid(md->view), blk(64, 4, 1);
 #define APK_LAUNCH_KICK(FL, DT, SP) \
@@ -538,8 +539,8 @@ int apk_turb_mean_momentum(apk_ctx *ctx, const apk_pack *md, const apk_fmft *f, 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
-  hipLaunchKernelGGL(turb_mean_momentum_kernel, g, dim3(64, 4, 1), 0, s, md->view, f->d_blocks, ctx->d_partial);
+  if (const int rc = ctx->d_partial.reserve(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8, s)) return rc;
+  hipLaunchKernelGGL(turb_mean_momentum_kernel, g, dim3(64, 4, 1), 0, s, md->view, f->d_blocks, ctx->d_partial.p);
   return finish_sums<4>(ctx, nwg, sums4, s);
 }
 
@@ -551,9 +552,9 @@ int apk_turb_remove_mean(apk_ctx *ctx, const apk_pack *md, apk_fmft *f, const do
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
+  if (const int rc = ctx->d_partial.reserve(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8, s)) return rc;
   hipLaunchKernelGGL(turb_remove_mean_kernel, g, dim3(64, 4, 1), 0, s, md->view, f->d_blocks, sums4[1] / sums4[0],
-                     sums4[2] / sums4[0], sums4[3] / sums4[0], ctx->d_partial);
+                     sums4[2] / sums4[0], sums4[3] / sums4[0], ctx->d_partial.p);
   return finish_sums<1>(ctx, nwg, ampl_sum, s);
 }
 
@@ -580,11 +581,11 @@ int apk_turbulence_history(apk_ctx *ctx, const apk_pack *md, int fluid, double g
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
+  if (const int rc = ctx->d_partial.reserve(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8, s)) return rc;
   if (fluid == APK_FLUID_EULER)
-    hipLaunchKernelGGL(turb_history_kernel<APK_FLUID_EULER>, g, dim3(64, 4, 1), 0, s, md->view, gamma, ctx->d_partial);
+    hipLaunchKernelGGL(turb_history_kernel<APK_FLUID_EULER>, g, dim3(64, 4, 1), 0, s, md->view, gamma, ctx->d_partial.p);
   else
-    hipLaunchKernelGGL(turb_history_kernel<APK_FLUID_GLMMHD>, g, dim3(64, 4, 1), 0, s, md->view, gamma, ctx->d_partial);
+    hipLaunchKernelGGL(turb_history_kernel<APK_FLUID_GLMMHD>, g, dim3(64, 4, 1), 0, s, md->view, gamma, ctx->d_partial.p);
   return finish_sums<3>(ctx, nwg, out3, s);
 }
 
@@ -594,8 +595,8 @@ int apk_history_user_reldivb(apk_ctx *ctx, const apk_pack *md, double B0, double
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 g = igrid(md->view);
   const int nwg = g.x * g.y * g.z;
-  if (const int rc = ensure_partial_doubles(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8)) return rc;
-  hipLaunchKernelGGL(user_reldivb_kernel, g, dim3(64, 4, 1), 0, s, md->view, B0, ctx->d_partial);
+  if (const int rc = ctx->d_partial.reserve(ctx, (size_t)nwg * 4 + kMidGroups * 4 + 8, s)) return rc;
+  hipLaunchKernelGGL(user_reldivb_kernel, g, dim3(64, 4, 1), 0, s, md->view, B0, ctx->d_partial.p);
   return finish_sums<1>(ctx, nwg, out, s);
 }
 
