@@ -69,6 +69,7 @@ class Table:
         self.x_H_over_m_h2 = (xh / mh) * (xh / mh)
         self.X_by_mh2 = math.pow((1 - He) / mh, 2)
         self.T_floor, self.d_e_tol, self.max_iter, self.cfl = T_floor, d_e_tol, max_iter, cfl
+        self._noise = None  # (rate_noise)
         self.temp_cool_floor = math.pow(10.0, self.log_temp_start)
         self.temp_final = math.pow(10.0, self.log_temp_final)
         temp_floor = T_floor if T_floor > self.temp_cool_floor else self.temp_cool_floor
@@ -111,7 +112,18 @@ class Table:
         if ll is None:
             return 0.0, True
         lam = math.pow(10., ll)
-        return -lam * self.x_H_over_m_h2 * rho, True
+        d = -lam * self.x_H_over_m_h2 * rho
+        if self._noise is not None:
+            delta, rng = self._noise
+            d *= 1.0 + delta * rng.uniform(-1.0, 1.0)
+        return d, True
+
+    def rate_noise(self, delta=0.0, seed=0):
+        """every non-zero DeDt from now on is multiplied by 1 + delta * xi, xi uniform in [-1, 1] from a generator
+        seeded with `seed` (delta = 0: off, DeDt as the reference computes it).  A probe of how far a last-bit
+        difference in log10 / pow moves a result."""
+        self._noise = (float(delta), np.random.default_rng(seed)) if delta else None
+        return self
 
 
 def _rk12(h, y0, f):
@@ -143,14 +155,30 @@ def _rk45(h, y0, f):
 STEPPERS = {"rk12": (_rk12, 2), "rk45": (_rk45, 5)}
 
 
-def subcycle_cell(T, integrator, rho, e0, dt, counts=None):
+EVENTS = ("reject", "clamp_min", "accept_over_tol", "invalid_retry", "to_floor", "err_zero", "grow", "end_at_floor")
+
+
+def subcycle_cell(T, integrator, rho, e0, dt, counts=None, events=None):
     """SubcyclingFixedIntSrcTerm for one cell: the final specific internal energy (counts: a list the number of
-    accepted substeps is appended to)"""
+    accepted substeps is appended to; events: a dict whose EVENTS counters are incremented, one per branch taken:
+    reject         d_e_err >= d_e_tol with sub_dt > min_sub_dt
+    clamp_min      a rejected step whose new sub_dt is clamped to min_sub_dt
+    accept_over_tol  a step accepted (at the minimum substep) with d_e_err >= d_e_tol
+    invalid_retry  an invalid step (a stage's energy negative) retried at the minimum substep
+    to_floor       an invalid step at the minimum substep: to the floor and the end of dt
+    err_zero       an accepted step with d_e_err == 0 (a step to the floor before any valid attempt set it is one):
+                   the next substep is the rest of dt
+    grow           an accepted step whose next sub_dt is larger than the one just taken
+    end_at_floor   a cell whose final energy is clamped to the floor)"""
     step, order = STEPPERS[integrator]
     f = lambda e: T.dedt(e, rho)  # noqa: E731
     opt = lambda h, err, tol: 0.95 * h * math.pow(tol / err, order)  # noqa: E731
     max_iter, d_e_tol, floor = T.max_iter, T.d_e_tol, T.e_floor_sub
     min_sub_dt = dt / max_iter
+
+    def ev(name):
+        if events is not None:
+            events[name] = events.get(name, 0) + 1
     e = e0
     d0, _ = f(e0)
     if d0 == 0.0 or e0 <= floor:
@@ -168,9 +196,11 @@ def subcycle_cell(T, integrator, rho, e0, dt, counts=None):
             again = False
             if not valid:
                 if sub_dt == min_sub_dt:
+                    ev("to_floor")
                     sub_dt = dt - sub_t
                     e_h = floor
                 else:
+                    ev("invalid_retry")
                     again, sub_dt = True, min_sub_dt
             else:
                 if e_h != 0:
@@ -180,32 +210,51 @@ def subcycle_cell(T, integrator, rho, e0, dt, counts=None):
                 if math.isnan(d_e_err):
                     again, sub_dt = True, min_sub_dt
                 elif d_e_err >= d_e_tol and sub_dt > min_sub_dt:
+                    ev("reject")
                     again = True
                     sub_dt = min_sub_dt if d_e_tol == 0 else opt(sub_dt, d_e_err, d_e_tol)
                     if sub_dt < min_sub_dt or attempt >= max_iter:
+                        ev("clamp_min")
                         sub_dt = min_sub_dt
+                elif d_e_err >= d_e_tol:
+                    ev("accept_over_tol")
             if not again:
                 break
         sub_t += sub_dt
         e = e_h
+        taken = sub_dt
+        if d_e_err == 0:
+            ev("err_zero")
         sub_dt = dt - sub_t if d_e_err == 0 else opt(sub_dt, d_e_err, d_e_tol)
         if d_e_tol == 0:
             sub_dt = min_sub_dt
         sub_dt = min_sub_dt if sub_dt < min_sub_dt else sub_dt
         sub_dt = (dt - sub_t) if (dt - sub_t) < sub_dt else sub_dt
+        if sub_dt > taken:
+            ev("grow")
         sub_iter += 1
     if counts is not None:
         counts.append(sub_iter)
+    if not e > floor:
+        ev("end_at_floor")
     return e if e > floor else floor
 
 
-def townsend_cell(T, rho, e, dt):
-    """TownsendSrcTerm for one cell: the final specific internal energy"""
+def townsend_cell(T, rho, e, dt, crossed=None):
+    """TownsendSrcTerm for one cell: the final specific internal energy (crossed: a list the number of temperature
+    bins the cell moved down is appended to; 0 for a cell that is not cooled)"""
+    e1, bins = _townsend(T, rho, e, dt)
+    if crossed is not None:
+        crossed.append(bins)
+    return e1
+
+
+def _townsend(T, rho, e, dt):
     if e <= T.e_floor_town:
-        return T.e_floor_town
+        return T.e_floor_town, 0
     temp = T.mbar_gm1_over_kb * e
     if temp < T.temp_cool_floor:
-        return e
+        return e, 0
     n_h2_by_rho = rho * T.X_by_mh2
     nb = T.n - 1
     idx = 0
@@ -215,12 +264,14 @@ def townsend_cell(T, rho, e, dt):
     tef = T.Y_k[idx] + (T.lambda_final / T.lambdas[idx]) * (T.temps[idx] / T.temp_final) * \
         (math.pow(T.temps[idx] / temp, am1) - 1.0) / am1
     tef_adj = tef + T.lambda_final * dt / T.temp_final * T.mbar_gm1_over_kb * n_h2_by_rho
+    idx0 = idx
     while idx > 0 and tef_adj > T.Y_k[idx]:
         idx -= 1
     a = T.alpha_k[idx]
     temp_new = T.temps[idx] * math.pow(1 - (1.0 - a) * (T.lambdas[idx] / T.lambda_final) *
                                        (T.temp_final / T.temps[idx]) * (tef_adj - T.Y_k[idx]), 1.0 / (1.0 - a))
-    return temp_new / T.mbar_gm1_over_kb if temp_new > T.temp_cool_floor else T.temp_cool_floor / T.mbar_gm1_over_kb
+    e1 = temp_new / T.mbar_gm1_over_kb if temp_new > T.temp_cool_floor else T.temp_cool_floor / T.mbar_gm1_over_kb
+    return e1, idx0 - idx
 
 
 def specific_internal_e(u, mhd):

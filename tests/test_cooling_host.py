@@ -195,3 +195,41 @@ def test_cooling_selects_the_flux_array_stage_path():
     assert off.cooling_options()[0] is False and off.info.fused == 1
     # enable_cooling = none changes nothing: the same plan as a deck without the block
     assert _plan([], deck="sod").info.fused == 1 and _plan([], deck="sod").cooling_options()[0] is False
+
+
+@pytest.mark.parametrize("integ", ["rk12", "rk45"])
+def test_adaptive_cases_reach_every_branch(integ):
+    """the cases of test_gpu_cooling_per_cell.py::test_adaptive_src_term_per_cell, in the restatement alone: every
+    branch of the error control is taken at least 20 times in some case, and in some case the accepted substeps of
+    the cooled cells of one wave (64 consecutive interior cells from a multiple of 64) differ by a factor 10 or more"""
+    import cooling_cases as C
+    most = dict.fromkeys(R.EVENTS, 0)
+    span = 0.0
+    for case in C.ADAPTIVE_CASES:
+        if case[0] != integ:
+            continue
+        o = C.adaptive_restated(*case, probes=False)
+        for k in R.EVENTS:
+            most[k] = max(most[k], o["events"].get(k, 0))
+        n = o["counts"]
+        assert len(n) == C.NB * o["mask"].sum() and n.max() <= o["kw"]["max_iter"]
+        for s in range(0, len(n), 64):
+            w = n[s:s + 64]
+            w = w[w > 0]
+            if len(w):
+                span = max(span, w.max() / w.min())
+    assert min(most.values()) >= 20, most
+    assert span >= 10.0, span
+
+
+def test_rate_noise_is_off_by_default_and_seeded():
+    import cooling_cases as C
+    rows = C.rows("schure")
+    T = C.restated(rows, "rk45", T_floor=C.T_FLOOR)
+    rho, e = 147.7557589278723, 1e6 / C.MBAR_GM1_OVER_KB
+    plain = T.dedt(e, rho)[0]
+    a = [T.rate_noise(1e-13, 4).dedt(e, rho)[0] for _ in range(2)]
+    b = [T.rate_noise(1e-13, 4).dedt(e, rho)[0] for _ in range(2)]
+    assert a == b and a[0] != plain and abs(a[0] - plain) <= 1e-13 * abs(plain) * (1 + 1e-3)
+    assert T.rate_noise(0.0).dedt(e, rho)[0] == plain
+    assert T.rate_noise(1e-13, 4).dedt(1e3 / C.MBAR_GM1_OVER_KB, rho) == (0.0, True)  # (below the table: stays 0)

@@ -9,36 +9,15 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cooling_cases as C  # noqa: E402
 import cooling_reference as R  # noqa: E402
+from cooling_cases import GAMMA, HE, MBAR_GM1_OVER_KB, NB, NG, ROOT, SCHURE, T_FLOOR, U  # noqa: E402
 from golden import make_cooling_tables as M  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCHURE = os.path.join(ROOT, "tests", "golden", "schure.cooling_1.0Z")
-GAMMA, HE = 1.6666666666666667, 0.25
-U = R.CLUSTER_UNITS
-MBAR_OVER_KB = R.composition(U, HE)[3]
-MBAR_GM1_OVER_KB = MBAR_OVER_KB * (GAMMA - 1.0)
-NX, NG, NB = (8, 4, 3), 2, 2
-T_FLOOR = 2e4
-
-
-def _rows(name, tmp_path=None):
-    if name == "schure":
-        return R.read_table(SCHURE)
-    return M.power_law_table()
-
-
-def _params(integrator="rk12", **kw):
-    from athenapk_amd import lib as L
-    return L.make_cooling_params(integrator=integrator, lambda_units=U.lambda_units(1.0), gamma=GAMMA,
-                                 mbar_over_kb=MBAR_OVER_KB, He_mass_fraction=HE, mh=U.mh, **kw)
-
-
-def _restated(rows, integrator="rk12", **kw):
-    lt, ll = rows
-    return R.Table(lt, ll, U.lambda_units(1.0), GAMMA, MBAR_OVER_KB, HE, U.mh, townsend=integrator == "townsend", **kw)
+NX = C.NX_ONE_WG
+_rows, _restated, _edge_temps, _params, _src = C.rows, C.restated, C.edge_temps, C.params, C.src
 
 
 def _loglam_tol(T, e):
@@ -47,20 +26,6 @@ def _loglam_tol(T, e):
     ulp apart"""
     ll = T.log_lambda(e)
     return 2e-14 if ll is None else max(2e-14, 1.5 * math.log(10.0) * np.spacing(abs(ll)))
-
-
-def _edge_temps(T, lt):
-    """the edge rows: e < 0, NaN, below the table, below T_floor, above the table, and table nodes whose lookup the
-    restatement's REQUIRE accepts"""
-    e = [-1.0e-3, float("nan"), 10 ** 3.5 / MBAR_GM1_OVER_KB, 1.5e4 / MBAR_GM1_OVER_KB, 10 ** 9.2 / MBAR_GM1_OVER_KB]
-    for k in range(3, len(lt) - 1, max(1, len(lt) // 7)):
-        ek = 10 ** lt[k] / MBAR_GM1_OVER_KB
-        x = math.log10(MBAR_GM1_OVER_KB * ek)
-        i = min(int((x - T.log_temp_start) / T.d_log_temp), T.n - 2)
-        lti = T.log_temp_start + T.d_log_temp * i
-        if lti <= x <= lti + T.d_log_temp:
-            e.append(ek)
-    return e
 
 
 @pytest.mark.parametrize("build", ["strict", "fast"])
@@ -85,68 +50,19 @@ def test_dedt_pointwise(gpu_ctx_strict, gpu_ctx_fast, build, table):
     assert (~valid).sum() == 2  # e < 0 and NaN
 
 
-def _state(fluid, T, lt, seed, nodes=True):
-    """conserved and primitive arrays of NB blocks [NB, nvar, nk, nj, ni] and the interior mask of one block; row
-    (k, j) = (0, 0) of block 0 holds the edge cases"""
-    from athenapk_amd import lib as L  # noqa: F401
-    mhd = fluid == "glmmhd"
-    nvar = 9 if mhd else 5
-    ni, nj, nk = NX[0] + 2 * NG, NX[1] + 2 * NG, NX[2] + 2 * NG
-    rng = np.random.default_rng(seed)
-    shape = (NB, nk, nj, ni)
-    rho = 147.7557589278723 * 10 ** rng.uniform(-1, 1, shape)
-    e = 10 ** rng.uniform(3.5, 8.5, shape) / MBAR_GM1_OVER_KB
-    v = [0.05 * rng.standard_normal(shape) for _ in range(3)]
-    b = [0.02 * rng.standard_normal(shape) for _ in range(3)] if mhd else [np.zeros(shape)] * 3
-    edge = _edge_temps(T, lt)[: NX[0]]
-    for i, ei in enumerate(edge):
-        e[0, NG, NG, NG + i] = ei
-    u = np.zeros((NB, nvar) + shape[1:])
-    u[:, 0] = rho
-    for d in range(3):
-        u[:, 1 + d] = rho * v[d]
-    kin = 0.5 * rho * (v[0] ** 2 + v[1] ** 2 + v[2] ** 2)
-    mag = 0.5 * (b[0] ** 2 + b[1] ** 2 + b[2] ** 2)
-    u[:, 4] = rho * e + kin + mag
-    if mhd:
-        for d in range(3):
-            u[:, 5 + d] = b[d]
-        u[:, 8] = 0.01 * rng.standard_normal(shape)
-    # e < 0: the stored total energy below the kinetic + magnetic part
-    u[0, 4, NG, NG, NG] = kin[0, NG, NG, NG] + mag[0, NG, NG, NG] - 1e-3 * rho[0, NG, NG, NG]
-    prim = u.copy()
-    for d in range(3):
-        prim[:, 1 + d] = v[d]
-    prim[:, 4] = (u[:, 4] - kin - mag) * (GAMMA - 1.0)
-    mask = np.zeros(shape[1:], dtype=bool)
-    mask[NG:NG + NX[2], NG:NG + NX[1], NG:NG + NX[0]] = True
-    return u, prim, mask
-
-
-def _src(ctx, fluid, rows, params, u, prim, dt):
-    from athenapk_amd import hydro
-    md = hydro.MeshData(ctx, NX, NG, u.shape[1], dx=(0.1, 0.1, 0.1), nblocks=NB, cons=u, prim=prim)
-    tab = hydro.TabularCooling(ctx, rows[0], rows[1], params)
-    tab.SrcTerm(md, fluid, dt)
-    return md.cons_host(), md, tab
-
-
 SRC_CASES = [(integ, fluid, table) for integ in ("rk12", "rk45", "townsend") for fluid in ("euler", "glmmhd")
              for table in ("schure", "power_law")]
 
 
-@pytest.mark.parametrize("integ,fluid,table", SRC_CASES)
-def test_src_term_against_restatement(gpu_ctx_strict, gpu_ctx_fast, integ, fluid, table):
-    """rk12 / rk45 with d_e_tol = 0 (a fixed number of substeps) and Townsend: per cell within 1e-12 of the
-    restatement (parity build), the product build within 1e-12 of the parity build; nothing but IEN changes"""
+def _check_src_term(ctx_strict, ctx_fast, integ, fluid, table, nx):
     rows = _rows(table)
     kw = dict(T_floor=T_FLOOR, d_e_tol=0.0, max_iter=8)
     T = _restated(rows, integ, **kw)
-    u, prim, mask = _state(fluid, T, rows[0], seed=len(integ) + 3 * len(fluid) + len(table))
+    u, prim, mask = C.state(fluid, T, rows[0], len(integ) + 3 * len(fluid) + len(table), nx)
     mhd = fluid == "glmmhd"
     dt = 2e-4
-    got, _, _ = _src(gpu_ctx_strict, fluid, rows, _params(integ, **kw), u, prim, dt)
-    fast, _, _ = _src(gpu_ctx_fast, fluid, rows, _params(integ, **kw), u, prim, dt)
+    got, _, _ = _src(ctx_strict, fluid, rows, _params(integ, **kw), u, prim, dt, nx)
+    fast, _, _ = _src(ctx_fast, fluid, rows, _params(integ, **kw), u, prim, dt, nx)
     for b in range(NB):
         want = R.src_term(T, integ, u[b], mhd, dt, mask)
         assert np.array_equal(np.delete(got[b], 4, axis=0), np.delete(u[b], 4, axis=0), equal_nan=True)
@@ -161,28 +77,71 @@ def test_src_term_against_restatement(gpu_ctx_strict, gpu_ctx_fast, integ, fluid
         assert cooled.sum() >= mask.sum() // 2, "the source cooled too few cells to test anything"
 
 
-@pytest.mark.parametrize("build", ["strict", "fast"])
-@pytest.mark.parametrize("table", ["schure", "power_law"])
-def test_cooling_timestep(gpu_ctx_strict, gpu_ctx_fast, build, table):
+@pytest.mark.parametrize("integ,fluid,table", SRC_CASES)
+def test_src_term_against_restatement(gpu_ctx_strict, gpu_ctx_fast, integ, fluid, table):
+    """rk12 / rk45 with d_e_tol = 0 (a fixed number of substeps) and Townsend: per cell within 1e-12 of the
+    restatement (parity build), the product build within 1e-12 of the parity build; nothing but IEN changes"""
+    _check_src_term(gpu_ctx_strict, gpu_ctx_fast, integ, fluid, table, NX)
+
+
+@pytest.mark.parametrize("integ,fluid,table", [("townsend", "euler", "schure"), ("townsend", "glmmhd", "power_law"),
+                                               ("rk45", "euler", "power_law"), ("rk45", "glmmhd", "schure")])
+def test_src_term_two_workgroups(gpu_ctx_strict, gpu_ctx_fast, integ, fluid, table):
+    """the same comparison on 360 interior cells: a second, partial workgroup, and the boundary between the blocks
+    (flat index 180) inside the first"""
+    _check_src_term(gpu_ctx_strict, gpu_ctx_fast, integ, fluid, table, C.NX_TWO_WG)
+
+
+def _check_timestep(ctx, table, nx, fastest=None):
+    """fastest: (block, k, j, i) of an interior cell that is given the shortest cooling time by far"""
     from athenapk_amd import hydro
-    ctx = gpu_ctx_strict if build == "strict" else gpu_ctx_fast
     rows = _rows(table)
     T = _restated(rows, T_floor=T_FLOOR)
-    u, prim, mask = _state("euler", T, rows[0], seed=5)
+    u, prim, mask = C.state("euler", T, rows[0], 5, nx)
     prim[0, 4, NG, NG, NG] = 1.0  # (the e < 0 row holds a valid state in the primitives)
     prim[0, 4, NG, NG, NG + 1] = 1.0
-    md = hydro.MeshData(ctx, NX, NG, 5, dx=(0.1, 0.1, 0.1), nblocks=NB, cons=u, prim=prim)
+    if fastest is not None:
+        others = min(R.cooling_timestep(T, prim[b], mask) for b in range(NB))
+        b, k, j, i = fastest
+        assert mask[k, j, i]
+        rho = 147.7557589278723e3  # (a hundred times the densest of the random cells, near the peak of the rates)
+        prim[b, 0, k, j, i], prim[b, 4, k, j, i] = rho, rho * (10 ** 5.3 / MBAR_GM1_OVER_KB) * (GAMMA - 1.0)
+        only = np.zeros_like(mask)
+        only[k, j, i] = True
+        assert R.cooling_timestep(T, prim[b], only) < 0.5 * others
+    md = hydro.MeshData(ctx, nx, NG, 5, dx=(0.1, 0.1, 0.1), nblocks=NB, cons=u, prim=prim)
     want = min(R.cooling_timestep(T, prim[b], mask) for b in range(NB))
     tab = hydro.TabularCooling(ctx, rows[0], rows[1], _params(T_floor=T_FLOOR))
     got = tab.EstimateTimeStep(md)
     tol = 2e-14 + 1.5 * math.log(10.0) * np.spacing(max(abs(v) for v in T.log_lambdas))
     assert abs(got - want) <= tol * want, (got, want)
+    return T, prim, mask, md, rows
+
+
+@pytest.mark.parametrize("build", ["strict", "fast"])
+@pytest.mark.parametrize("table", ["schure", "power_law"])
+def test_cooling_timestep(gpu_ctx_strict, gpu_ctx_fast, build, table):
+    from athenapk_amd import hydro
+    ctx = gpu_ctx_strict if build == "strict" else gpu_ctx_fast
+    T, prim, mask, md, rows = _check_timestep(ctx, table, NX)
     for cfl, expect in ((0.0, np.finfo(np.float64).max), (-1.0, np.finfo(np.float64).max), (float("nan"), math.inf),
                         (math.inf, math.inf)):
         t2 = hydro.TabularCooling(ctx, rows[0], rows[1], _params(T_floor=T_FLOOR, cfl=cfl))
         assert t2.EstimateTimeStep(md) == expect
         T.cfl = cfl
         assert R.cooling_timestep(T, prim[0], mask) == expect
+
+
+@pytest.mark.parametrize("build", ["strict", "fast"])
+@pytest.mark.parametrize("table", ["schure", "power_law"])
+@pytest.mark.parametrize("where", ["random", "flat_359", "flat_180"])
+def test_cooling_timestep_two_workgroups(gpu_ctx_strict, gpu_ctx_fast, build, table, where):
+    """the minimum over 360 interior cells, wherever it falls, then in the last cell of block 1 (flat index 359, in
+    the partial second workgroup) and in the first cell of block 1 (flat index 180, inside the first workgroup)"""
+    nx = C.NX_TWO_WG
+    cell = {"random": None, "flat_359": (1, NG + nx[2] - 1, NG + nx[1] - 1, NG + nx[0] - 1),
+            "flat_180": (1, NG, NG, NG)}[where]
+    _check_timestep(gpu_ctx_strict if build == "strict" else gpu_ctx_fast, table, nx, cell)
 
 
 # ---- the native driver -------------------------------------------------------------------------------------------
