@@ -1,6 +1,7 @@
 """`python -m athenapk_amd -i deck.in [-d outdir] [block/key=value ...]` -- runs an input deck
-the way `athenaPK -i deck.in block/key=value` does for the scope of this package (uniform grid,
-hydro / GLM-MHD flux-divergence update, history and linear-wave error outputs).  Under
+the way `athenaPK -i deck.in block/key=value` does for the scope of this package (hydro / GLM-MHD
+flux-divergence update; history, linear-wave error and field snapshot outputs: `file_type = hst` and
+`file_type = npy` blocks, the latter read back with athenapk_amd.snapshots.load; no restart files).  Under
 `python -m torch.distributed.run --nproc-per-node N` it runs one rank per GPU over RCCL.
 """
 import argparse

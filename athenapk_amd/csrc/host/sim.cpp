@@ -776,6 +776,7 @@ int create_common(const char *deck, const char *const *overrides, int noverrides
       if ((s->mesh.bc_in[d] == BC_REFLECT || s->mesh.bc_out[d] == BC_REFLECT) && s->pkg.fluid != APK_FLUID_EULER)
         throw std::runtime_error("Reflecting boundary conditions for MHD need special treatment.");
     tracers_initialize(s);  // <tracers> (after the hydro package, as the reference's Initialize order)
+    snapshot_initialize(s);  // the npy output blocks (host/snapshot.cpp)
   } catch (const std::exception &e) {
     if (errbuf && errlen) std::snprintf(errbuf, errlen, "%s", e.what());
     delete s;
@@ -928,6 +929,7 @@ void apk_sim_destroy(apk_sim *s) {
     for (auto &t : s->d_x1_tab) dev_free(s, static_cast<double *>(t));
     sts_free(s);
     tracers_free(s);
+    snapshot_free(s);
     dev_free(s, s->d_acc);
     dev_free(s, s->d_phases);
     dev_free(s, s->d_block_xmin);
@@ -1579,7 +1581,8 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     const std::string base = s->pin.GetOrAddString("parthenon/job", "problem_id", "parthenon");
     for (const std::string &blk : s->pin.BlocksWithPrefix("parthenon/output")) {
       if (blk == "parthenon/output_defaults" || !s->pin.DoesParameterExist(blk, "file_type")) continue;
-      if (s->pin.GetString(blk, "file_type") != "hst") continue;  // hdf5 / rst outputs are out of scope
+      // npy: field snapshots, parsed at creation (host/snapshot.cpp: s->snap_outs); hdf5 / rst outputs are out of scope
+      if (s->pin.GetString(blk, "file_type") != "hst") continue;
       const std::string num = blk.substr(std::string("parthenon/output").size());
       const double out_dt = s->pin.GetReal(blk, "dt");
       if (!(out_dt > 0.0)) throw std::runtime_error("<" + blk + ">: dt must be positive for hst outputs");
@@ -1628,6 +1631,21 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     SIM_TRY(s, write_tracers(o));
     o.next = o.dt;
   }
+  // the field snapshots: <outdir>/<problem_id>.<id>.<NNNNN>, the cadence rule of the history outputs
+  struct SnapOut {
+    const apk::SnapshotOutput *o;
+    double next;
+    int dumps;
+  };
+  std::vector<SnapOut> snaps;
+  for (const auto &o : s->snap_outs) snaps.push_back({&o, o.dt, 0});
+  auto write_snapshot = [&](SnapOut &so) -> int {
+    char num[16];
+    std::snprintf(num, sizeof num, "%05d", so.dumps++);
+    const std::string base = s->pin.GetOrAddString("parthenon/job", "problem_id", "parthenon");
+    return snapshot_write(s, std::string(outdir) + "/" + base + "." + so.o->id + "." + num, so.o->codes, so.o->names, so.o->single);
+  };
+  for (auto &so : snaps) SIM_TRY(s, write_snapshot(so));
   int n = 0;
   // parthenon/time/perf_cycle_offset: cycles left out of the performance figure (first-touch
   // allocations, e.g. the flux-difference workspace and the spare prim buffer, happen there)
@@ -1651,6 +1669,11 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
         SIM_TRY(s, apk_sim_write_history(s, o.path.c_str()));
         SIM_TRY(s, write_tracers(o));
         while (o.next <= s->time) o.next += o.dt;
+      }
+    for (auto &so : snaps)
+      if (s->time >= so.next || last) {
+        SIM_TRY(s, write_snapshot(so));
+        while (so.next <= s->time) so.next += so.o->dt;
       }
   }
   SIM_TRY(s, sync_ghosts(s));

@@ -156,6 +156,15 @@ struct TracerState {
   std::string csv_path;  // apk_sim_execute: <outdir>/correlations.csv, a row per cycle (empty: no file)
 };
 
+// one <parthenon/outputN> block with file_type = npy (host/snapshot.cpp): a field snapshot output
+struct SnapshotOutput {
+  std::string block, id;  // the deck block and the id of the file names (default out<N>)
+  double dt = 0.0;
+  bool single = false;             // single_precision_output
+  std::vector<int> codes;          // apk_output_component, duplicates collapsed, deck order
+  std::vector<std::string> names;  // their canonical names
+};
+
 }  // namespace apk
 
 namespace apk {
@@ -424,6 +433,13 @@ struct apk_sim {
   bool sts_fused = false;
   // tracer particles (host/tracers.cpp): null unless tracers/enabled = true
   std::unique_ptr<apk::TracerState> tracers;
+  // field snapshots (host/snapshot.cpp): the deck's npy outputs, the staging bound of apk_amd/snapshot_staging_mb in
+  // bytes, and the two staging buffers (allocated on first use, grown when a component list needs more)
+  std::vector<apk::SnapshotOutput> snap_outs;
+  size_t snap_staging_bytes = 0;
+  double *d_snap = nullptr;
+  void *h_snap = nullptr;  // pinned (hipHostMalloc)
+  size_t snap_dev_cap = 0, snap_host_cap = 0;
   int sts_last_s = 0;           // sub-stages of the last half step taken
   double sts_last_ratio = 0.0;  // its 2 tau / dt_diff
   long long overlapped = 0;

@@ -123,6 +123,10 @@ int tracers_seed_initial(apk_sim *s);          // upload what the deck seeded, s
 int tracers_cycle(apk_sim *s, double dt);      // the tracer step after the last stage (hydro_driver.cpp:615-660)
 int tracers_write_outputs(apk_sim *s, const std::string &prefix);
 void tracers_free(apk_sim *s);
+void snapshot_initialize(apk_sim *s);  // the npy output blocks and apk_amd/snapshot_staging_mb (host/snapshot.cpp), at creation
+int snapshot_write(apk_sim *s, const std::string &prefix, const std::vector<int> &codes, const std::vector<std::string> &names,
+                   bool single);       // one dump: <prefix>.rank<r>.npy on every rank, <prefix>.json on rank 0
+void snapshot_free(apk_sim *s);
 double xc(const apk_sim *s, const double x0[3], int d, int idx);
 void block_origin(const apk_sim *s, int lb, double x0[3]);
 void lw_eigensystem(double gm1, double v1, double v2, double v3, double h, double ev[5], double rem[5][5]);

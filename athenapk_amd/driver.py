@@ -219,6 +219,41 @@ class _ClusterHost:
         return out
 
 
+def _variables(variables):
+    """a `variables` list as the C API takes it: "cons, prim.rho" or ["cons", "prim.rho"]"""
+    return (variables if isinstance(variables, str) else ",".join(variables)).encode()
+
+
+class _SnapshotHost:
+    """Field snapshots (include/apk_host.h): what needs no device state; works on host-only sims too."""
+
+    def _snapshot_check(self, rc):
+        if rc != L.APK_OK:
+            raise L.ApkError(rc, self.lib.apk_sim_last_error(self.h).decode())
+
+    def snapshot_outputs(self):
+        """the deck's npy output blocks as parsed: [{"number", "id", "dt", "single", "components"}]"""
+        size = C.c_int(0)
+        self._snapshot_check(self.lib.apk_sim_snapshot_outputs(self.h, None, 0, C.byref(size)))
+        out = (L.SnapshotOutputInfo * max(size.value, 1))()
+        self._snapshot_check(self.lib.apk_sim_snapshot_outputs(self.h, out, size.value, C.byref(size)))
+        return [{"number": o.number, "id": o.id.decode(), "dt": o.dt, "single": bool(o.single),
+                 "components": o.components.decode().split(",")} for o in out[:size.value]]
+
+    def snapshot_shape(self, variables, single=False):
+        """(component names, (nblocks_local, ncomp, nx3, nx2, nx1), numpy dtype) of snapshot(variables, single)"""
+        nb, nc, item, nx = C.c_int(0), C.c_int(0), C.c_int(0), (C.c_int * 3)()
+        names = C.create_string_buffer(2048)
+        self._snapshot_check(self.lib.apk_sim_snapshot_shape(self.h, _variables(variables), int(bool(single)), C.byref(nb),
+                                                             C.byref(nc), C.byref(nx), C.byref(item), names, len(names)))
+        return names.value.decode().split(","), (nb.value, nc.value, nx[2], nx[1], nx[0]), np.dtype("<f%d" % item.value)
+
+    def write_snapshot_index(self, path, variables="cons", single=False):
+        """the JSON index of a dump alone (a host-only sim: time 0, cycle 0)"""
+        self._snapshot_check(self.lib.apk_sim_write_snapshot_index(self.h, str(path).encode(), _variables(variables),
+                                                                   int(bool(single))))
+
+
 class _MeshView:
     """Block placement and ghost-exchange plans of a sim handle (valid without a GPU)."""
 
@@ -301,7 +336,7 @@ class _MeshView:
         return self.info
 
 
-class Simulation(_FmftHost, _ClusterHost, _MeshView):
+class Simulation(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
     """apk_sim: deck + overrides -> mesh partition, packs, ghost plans, stage loop (C++).
 
     COLLECTIVE accessors on N > 1 ranks: read_block / write_block / gather / history / turbulence_history / reldivb and
@@ -620,6 +655,21 @@ class Simulation(_FmftHost, _ClusterHost, _MeshView):
                                             out.ctypes.data_as(L.c_dp)))
         return out
 
+    def snapshot(self, variables, single=False):
+        """(names, array[nblocks_local][ncomp][nx3][nx2][nx1]) of the current state's interior cells: conserved
+        components as stored, primitives as ConsToPrim would give them, derived fields; float32 with single.  One fused
+        kernel over the conserved state (apk_output_pack): a LOCAL call that reads no ghost zone, exchanges nothing and
+        leaves the driver's state alone, unlike read_block / gather"""
+        names, shape, dtype = self.snapshot_shape(variables, single)
+        out = np.empty(shape, dtype=dtype)
+        self._check(self.lib.apk_sim_snapshot_read(self.h, _variables(variables), int(bool(single)),
+                                                   out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return names, out
+
+    def write_snapshot(self, prefix, variables, single=False):
+        """one dump: <prefix>.rank<r>.npy on every rank, <prefix>.json on rank 0 (athenapk_amd.snapshots.load reads it)"""
+        self._check(self.lib.apk_sim_write_snapshot(self.h, str(prefix).encode(), _variables(variables), int(bool(single))))
+
     @property
     def fofc_fallback_stages(self):
         return self.lib.apk_sim_fofc_fallback_stages(self.h)
@@ -665,7 +715,7 @@ class Simulation(_FmftHost, _ClusterHost, _MeshView):
         self._check(self.lib.apk_sim_write_linear_wave_errors(self.h, str(path).encode()))
 
     def execute(self, outdir):
-        """initialize + main loop + the deck's hst outputs + the linear-wave error file"""
+        """initialize + main loop + the deck's hst and npy (field snapshot) outputs + the linear-wave error file"""
         n = C.c_int(0)
         self._check(self.lib.apk_sim_execute(self.h, str(outdir).encode(), C.byref(n)))
         return n.value
@@ -933,7 +983,7 @@ def _tracers_read(lib, h, names):
     return {name: raw[name][order] for name in raw}
 
 
-class HostPlan(_FmftHost, _ClusterHost, _MeshView):
+class HostPlan(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
     """Host-only view of a rank's mesh partition and ghost-exchange plan (no GPU needed)."""
 
     def __init__(self, deck, overrides=(), rank=0, nranks=1, strict=False):

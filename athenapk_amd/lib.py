@@ -337,6 +337,31 @@ class TracersOptions(C.Structure):
                 ("num_tracers_per_cell", C.c_double), ("rng_seed", C.c_longlong), ("num_tracers_per_block", C.c_longlong)]
 
 
+# apk_output_component: APK_OUT_CONS + n, APK_OUT_PRIM + n, and the derived fields
+OUT_CONS, OUT_PRIM = 0, 64
+OUT_DERIVED = {"temperature": 128, "mach_sonic": 129, "B_mag": 130, "mach_alfven": 131, "plasma_beta": 132}
+OUT_MAX_COMPONENTS = 48
+
+
+class OutputDesc(C.Structure):
+    """apk_output_desc: what apk_output_pack stores per interior cell"""
+    _fields_ = [("ncomp", C.c_int), ("single", C.c_int), ("gamma", C.c_double), ("mbar_over_kb", C.c_double),
+                ("comp", C.c_int * OUT_MAX_COMPONENTS)]
+
+
+def make_output_desc(codes, single=False, gamma=5.0 / 3.0, mbar_over_kb=1.0):
+    d = OutputDesc(len(codes), int(bool(single)), float(gamma), float(mbar_over_kb))
+    for q, c in enumerate(codes):
+        d.comp[q] = int(c)
+    return d
+
+
+class SnapshotOutputInfo(C.Structure):
+    """apk_snapshot_output_info: one npy output block of the deck as parsed"""
+    _fields_ = [("number", C.c_int), ("single", C.c_int), ("ncomp", C.c_int), ("dt", C.c_double), ("id", C.c_char * 64),
+                ("components", C.c_char * 1024)]
+
+
 class AmrOpInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("level", C.c_int), ("src_kind", C.c_int), ("src_block", C.c_int),
                 ("dst_kind", C.c_int), ("dst_block", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3),
@@ -447,6 +472,7 @@ def _signatures():
         "apk_tracers_sort": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerArrays), C.POINTER(TracerGeom), vp, i, vp]),
         "apk_tracers_lookback": (i, [vp, C.POINTER(TracerArrays), ll, d, vp, ll, vp, vp]),
         "apk_tracers_step_fused_lookback": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), d, vp, ll, vp, ll, vp, vp]),
+        "apk_output_pack": (i, [vp, vp, i, E, C.POINTER(OutputDesc), i, i, vp, vp]),
         "apk_kernel_timing_enable": (i, [vp, i]),
         "apk_kernel_timing_read": (i, [vp, i, c_dp, C.POINTER(ll)]),
         # apk_host.h
@@ -563,6 +589,12 @@ def _signatures():
         "apk_sim_comm_error": (C.c_char_p, [vp]),
         "apk_rccl_selftest": (i, [i, C.c_char_p, C.c_size_t]),
         "apk_sim_amr_apply_tags": (i, [vp, C.POINTER(i), i, C.POINTER(i)]),
+        "apk_sim_snapshot_outputs": (i, [vp, C.POINTER(SnapshotOutputInfo), i, C.POINTER(i)]),
+        "apk_sim_snapshot_shape": (i, [vp, C.c_char_p, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_int * 3), C.POINTER(i),
+                                       C.c_char_p, C.c_size_t]),
+        "apk_sim_snapshot_read": (i, [vp, C.c_char_p, i, vp, C.c_size_t]),
+        "apk_sim_write_snapshot": (i, [vp, C.c_char_p, C.c_char_p, i]),
+        "apk_sim_write_snapshot_index": (i, [vp, C.c_char_p, C.c_char_p, i]),
     }
 
 

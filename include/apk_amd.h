@@ -1021,6 +1021,39 @@ int apk_agn_triggering_remove_bondi(apk_ctx *ctx, const apk_pack *md, int fluid,
                                     const apk_trig_box *boxes, int nboxes, int64_t max_box_cells, const double *block_xmin,
                                     double total_mass, double accretion_rate, double dt, apk_stream_t stream);
 
+/* ---- field snapshots: one fused pass from the conserved state to a dense staging buffer (csrc/kernels_output.hip) ----
+ * Component codes.  APK_OUT_CONS + n: conserved variable n as stored (n < nhydro + nscalars); APK_OUT_PRIM + n: primitive
+ * n as ConsToPrim would give it (passive scalars: r_n = s_n / rho); the derived fields of the reference's
+ * Cluster::UserWorkBeforeOutput (src/pgen/cluster.cpp:866-924), with SQR(x) = x * x and sums left to right:
+ *   temperature = mbar_over_kb * P / rho           mach_sonic = sqrt(v1^2 + v2^2 + v3^2) / sqrt(gamma * P / rho)
+ *   B_mag = sqrt(B^2)    mach_alfven = mach_sonic * c_s / sqrt(B^2 / rho)    plasma_beta = (B^2 != 0) ? P / (0.5 B^2) : NaN
+ * (the last three: GLM-MHD packs only). */
+enum apk_output_component {
+  APK_OUT_CONS = 0,
+  APK_OUT_PRIM = 64,
+  APK_OUT_TEMPERATURE = 128,
+  APK_OUT_MACH_SONIC = 129,
+  APK_OUT_B_MAG = 130,
+  APK_OUT_MACH_ALFVEN = 131,
+  APK_OUT_PLASMA_BETA = 132
+};
+#define APK_OUT_MAX_COMPONENTS 48
+typedef struct apk_output_desc {
+  int ncomp;                        /* 1 .. APK_OUT_MAX_COMPONENTS */
+  int single;                       /* 0 = double, 1 = float (round to nearest even) */
+  double gamma;                     /* of mach_sonic / mach_alfven */
+  double mbar_over_kb;              /* of temperature */
+  int comp[APK_OUT_MAX_COMPONENTS]; /* apk_output_component codes, in output order */
+} apk_output_desc;
+/* Blocks [first, first + n) of md: out[block - first][component][k][j][i] over INTERIOR cells only, C order, double or
+ * float; out is DEVICE memory of n * ncomp * nx3 * nx2 * nx1 items.  Every lane owns one interior cell, reads its
+ * nhydro + nscalars conserved values once, runs ConsToPrim on a register copy and stores the components asked for.  The
+ * pack is never written: a floor that fires changes the primitives that come out, not the state in memory, and no flag
+ * is latched.  Needs no ghost zone and no stored primitive (md's prim pointers are not read).  Honours
+ * apk_pack_desc.stride; 1-D, 2-D and 3-D blocks.  Does not synchronise. */
+int apk_output_pack(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_output_desc *desc, int first,
+                    int n, void *out, apk_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
  * they are launched on.  When enabled, every kernel launch of the listed groups is

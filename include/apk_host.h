@@ -469,8 +469,49 @@ int apk_sim_write_linear_wave_errors(apk_sim *sim, const char *path);
 /* main loop of a deck run (what `athenaPK -i deck` does for the scope here): initialize, step to
  * tlim / nlim, write every <parthenon/output*> block with file_type = hst to
  * <outdir>/<parthenon/job problem_id, default "parthenon">.out<N>.hst at its `dt` cadence (t = 0
- * and the final time included), and, for linear_wave with compute_error, the error file. */
+ * and the final time included), every block with file_type = npy as field snapshots (below) at the same
+ * cadence rule, and, for linear_wave with compute_error, the error file. */
 int apk_sim_execute(apk_sim *sim, const char *outdir, int *ncycles);
+
+/* ---- field snapshots (csrc/host/snapshot.cpp, csrc/host/snapshot_format.cpp, csrc/kernels_output.hip) -----------------
+ * A <parthenon/outputN> block with file_type = npy: dt (> 0), variables (comma separated, default cons),
+ * single_precision_output (default false), id (default out<N>).  Entries of `variables`: the groups cons and prim; single
+ * components cons.rho, cons.mom1..3, cons.etot, cons.B1..3, cons.psi, cons.s<n>, prim.rho, prim.vel1..3, prim.pressure,
+ * prim.B1..3, prim.psi, prim.r<n>; the derived fields temperature, mach_sonic, B_mag, mach_alfven, plasma_beta
+ * (apk_output_component in apk_amd.h; with every problem generator, where the reference has them for the cluster only).
+ * Duplicates collapse, order is kept.  Refused at creation with a message naming block and key: an unknown entry, an MHD
+ * component or MHD-only field with hydro/fluid = euler, temperature without <units> and hydro/He_mass_fraction, a scalar
+ * index >= nscalars, dt <= 0, an empty list.  hdf5 and rst blocks stay ignored; restart is not part of this.
+ * A dump is <prefix>.rank<r>.npy on every rank -- NumPy format 1.0, shape (nblocks_local, ncomp, nx3, nx2, nx1) of the
+ * meshblock, interior cells, '<f8' or '<f4', blocks in local order -- and <prefix>.json on rank 0: time, cycle, dt,
+ * components, dtype, fluid, gamma, nscalars, xmin, xmax, mesh_nx, block_nx, nghost, nranks and blocks (gid, level, lx1,
+ * lx2, lx3, rank, index = position in that rank's file), doubles as %.17g.  apk_sim_execute writes
+ * <outdir>/<problem_id as for hst>.<id>.<NNNNN> from 00000: after initialisation, then when time >= next or on the last
+ * cycle.  A dump packs the interior of the CURRENT conserved state on the sim's stream in chunks of whole blocks through a
+ * device and a pinned host staging buffer of at most apk_amd/snapshot_staging_mb MB each (default 256; never less than
+ * one block): no ghost zone is read, no stored primitive, nothing is exchanged and no driver state changes -- unlike
+ * read_block / gather these are local calls, and a run that dumps takes the stage forms and exchanges of one that does
+ * not.  `variables` below is such a comma-separated list. */
+typedef struct apk_snapshot_output_info {
+  int number;             /* N of <parthenon/outputN> */
+  int single, ncomp;
+  double dt;
+  char id[64];
+  char components[1024];  /* canonical names, comma separated */
+} apk_snapshot_output_info;
+/* the deck's snapshot outputs as parsed: copies min(n, size) entries, *size = their number.  Works on a host-only sim. */
+int apk_sim_snapshot_outputs(const apk_sim *sim, apk_snapshot_output_info *out, int n, int *size);
+/* what apk_sim_snapshot_read delivers for `variables`: local blocks, components, interior extents nx[3] = nx1, nx2, nx3 of
+ * a block, bytes per item, and (names may be NULL) the canonical component names, comma separated.  Works on a host-only
+ * sim. */
+int apk_sim_snapshot_shape(apk_sim *sim, const char *variables, int single, int *nblocks, int *ncomp, int nx[3], int *itemsize,
+                           char *names, size_t names_len);
+/* packs the current state into out[nblocks][ncomp][nx3][nx2][nx1] (double or float); out_bytes must be that size */
+int apk_sim_snapshot_read(apk_sim *sim, const char *variables, int single, void *out, size_t out_bytes);
+/* one dump to <prefix>.rank<r>.npy (+ <prefix>.json on rank 0).  Every rank calls it; no rank waits for another. */
+int apk_sim_write_snapshot(apk_sim *sim, const char *prefix, const char *variables, int single);
+/* the JSON index alone, to `path`, with the sim's time, cycle and dt (a host-only sim: time 0, cycle 0) */
+int apk_sim_write_snapshot_index(apk_sim *sim, const char *path, const char *variables, int single);
 /* wall seconds of the main loop of the last apk_sim_execute (initialisation excluded, device
  * synchronised): zones * cycles / this = Parthenon's "zone-cycles/wallsecond" */
 double apk_sim_loop_seconds(const apk_sim *sim);
