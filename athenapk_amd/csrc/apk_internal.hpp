@@ -60,6 +60,8 @@ enum : int {
   kWordStageDt = 4,   // the stage's time-step minimum (prepare_dt_word; apk_stage_dt_read / apk_stage_dt_flags_read)
   kWordFlags = 5,     // two 32-bit flag words, apk_ctx::d_flags: [0] latched, [1] trial stage
   kWordStageBad = 6,  // the fused stage's count of unphysical cells (apk_stage_unphysical_read)
+  kWordMarchTickets = 7,  // piece tickets of the finishing march's dynamic phase (zeroed in stream order by launch_m12f
+                          // before the launch that draws them; never read back)
   kWordPlusMax = 15,  // constant +max, the neutral element the time-step word is reset from
   kNumWords = 16
 };
@@ -76,6 +78,7 @@ enum : int {
   kPinnedBytes = 256
 };
 static_assert(kWordFlags == kWordStageDt + 1, "time-step word and flag words are read back with one 16-byte copy");
+static_assert(kWordStageBad < kWordMarchTickets && kWordMarchTickets < kWordPlusMax, "the march's ticket word is a spare one");
 static_assert(kPinSeed != kPinMin && kPinMin < kWordCounter && kWordStageBad < kPinU64Slots && kWordPlusMax < kNumWords,
               "u64 slots: seed, minimum and the mirrored words are distinct");
 static_assert(kPinU64Slots * 8 <= kPinHistory && kPinHistory + 8 * 8 <= kPinSums &&

@@ -82,6 +82,20 @@ __device__ unsigned long long g_m12f_phase[8];
 #define APK_TICK(slot) do { } while (0)
 #endif
 
+#ifndef APK_M12F_WAVE_ENDS
+// 1 (diagnostic variant build, `make variant VAR=we VARFLAGS=-DAPK_M12F_WAVE_ENDS=1`): every wave records three times of
+// the constant-rate wall clock (100 MHz) -- its start, the end of its whole columns, its end -- by vector stores of lane
+// 0, and launch_m12f writes the table of launch number APK_M12F_WAVE_ENDS_CALL to the file APK_M12F_WAVE_ENDS_OUT
+// (tools/m12f_wave_ends.py turns it into the distribution of end times).  In this build APK_M12F_STATIC=1 keeps the
+// static leftover split and APK_M12F_PIECE_ROWS sets the dynamic phase's piece length: the before / after pair and
+// the sweep behind the launcher's choice come from one library.
+#define APK_M12F_WAVE_ENDS 0
+#endif
+#if APK_M12F_WAVE_ENDS
+constexpr int kWaveEndsMax = 4096;
+__device__ unsigned long long g_m12f_wave_ends[3 * kWaveEndsMax];
+#endif
+
 // does the from-cons finishing march keep the loaded rows in a second LDS ring?  (two rings within the 20 KB a wave may
 // take with two waves per SIMD, with some room)
 template <int FLUID, int RECON>
@@ -97,7 +111,7 @@ constexpr bool m12f_keeps_raw_rows() {
 template <int FLUID, int RECON, int RS, int EXTRA, int LEAN, bool FC = false, bool X1H = false>
 __global__ void __launch_bounds__(64, 2)
 fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves, int per_xcd,
-                  long long total_rows) {
+                  long long total_rows, unsigned long long *tickets, int piece_rows) {
   static_assert(RECON != APK_RC_DC, "donor-cell stages have their own single-kernel form");
   static_assert(!FC || LEAN, "prim_from_cons: lean form only");
   static_assert(!X1H || LEAN == 1, "x1_halo: the lean forms");
@@ -146,13 +160,42 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
   const int full = ncol / nwaves, left_cols = ncol - full * nwaves;
   const int per_col = (left_cols > 0) ? nwaves / left_cols : 0;  // segments per leftover column (>= 1)
   const int seg = per_col > 0 ? (u0.nx2 + per_col - 1) / per_col : 0;
-  for (int piece = 0; piece <= full; ++piece) {  // wave-uniform
+  // The DYNAMIC leftover phase (tickets != nullptr; launch_m12f: packs with full >= 1 and columns left over): the
+  // left_cols x nx2 leftover rows are cut into pieces of piece_rows rows, and a wave that has finished its whole columns
+  // draws pieces from ONE ticket word until none are left.  Of the two waves of a SIMD the one dispatched first issues
+  // first and finishes its column in 2/3 of the other's time (profiles/m12f_wave_ends_before.json: 1.03 against 1.54 ms,
+  // in every SIMD), so under the static split half of the wave slots stood empty for the last third of the launch while
+  // the other half still had a fixed leftover piece to march; now the leftover rows go to whoever is free.  Tickets
+  // count segment-major -- ticket t is segment t / left_cols of leftover column t % left_cols -- so waves that draw at
+  // about the same time march neighbouring columns over the same rows, the property of the lockstep order above.  A
+  // ticket is one vector atomic of lane 0, made wave-uniform by v_readfirstlane (no scalar memory instruction).  Which
+  // wave marches a row does not enter its result.
+  const int left_segs = tickets ? (u0.nx2 + piece_rows - 1) / piece_rows : 0;
+#if APK_M12F_WAVE_ENDS
+  const unsigned long long we_start_ = wall_clock64();
+  unsigned long long we_cols_ = we_start_;
+#endif
+  for (int piece = 0;; ++piece) {  // wave-uniform
     // ---- this piece: rows s..e of column chunk `chunk` of block b
     int item, j0, nrows;
     if (piece < full) {
       item = piece * nwaves + w, j0 = 0, nrows = u0.nx2;
+    } else if (tickets) {
+#if APK_M12F_WAVE_ENDS
+      if (piece == full) we_cols_ = wall_clock64();
+#endif
+      unsigned long long t = 0;
+      if (lane == 0) t = atomicAdd(tickets, 1ull);
+      const int ti = __builtin_amdgcn_readfirstlane((int)(t < 0x7fffffffull ? t : 0x7fffffffull));
+      if (ti >= left_segs * left_cols) break;
+      const int sidx = ti / left_cols;
+      item = full * nwaves + (ti - sidx * left_cols), j0 = sidx * piece_rows;
+      nrows = (j0 + piece_rows <= u0.nx2) ? piece_rows : u0.nx2 - j0;
     } else {
-      if (left_cols <= 0) break;
+#if APK_M12F_WAVE_ENDS
+      if (piece == full) we_cols_ = wall_clock64();
+#endif
+      if (piece > full || left_cols <= 0) break;
       const int sidx = w / left_cols, lc = w - sidx * left_cols;
       if (sidx >= per_col || sidx * seg >= u0.nx2) break;
       item = full * nwaves + lc, j0 = sidx * seg;
@@ -566,6 +609,14 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
     for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_down(m, off, 64));
     if (lane == 0) atomicMin(sp.dt_bits, (unsigned long long)__double_as_longlong(m));
   }
+#if APK_M12F_WAVE_ENDS
+  if (lane == 0 && w < kWaveEndsMax) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the last row's stores have left the wave)
+    g_m12f_wave_ends[3 * w + 0] = we_start_;
+    g_m12f_wave_ends[3 * w + 1] = we_cols_;
+    g_m12f_wave_ends[3 * w + 2] = wall_clock64();
+  }
+#endif
 }
 
 // Round 3, measured and NOT kept (same box, general stage of 8 x 128^3, 3.39 ms with this kernel):
@@ -611,7 +662,11 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
 //    and global_ instead of flat_ accesses (as_global): both kept, both within 1 % (same-box bench A/B);
 //  * the nine per-variable offsets n * sn of d3 / u1 / u0 / prim' as ONE walking pointer (8 SGPR pairs fewer: scalar
 //    spills 87 -> 72, scratch 28 -> 20 B per lane): no change (2.60 against 2.58 ms for this kernel).
-// number of waves the device holds at once with two march waves per SIMD
+// number of waves the device holds at once with two march waves per SIMD.
+// Test hook: the environment variable APK_MARCH_WAVES (a positive integer, read once per process) LOWERS the count the
+// launches assume, so that a pack of a few small blocks has at least as many columns as "the device holds waves" and
+// takes the schedule of the large packs (whole columns in lockstep, then the dynamic leftover phase).  Results do not
+// depend on it (tests/test_gpu_m12f_dynamic_tail.py); production runs leave it unset.
 inline int resident_march_waves() {
   static const int n = [] {
     int dev = 0, cus = 256;
@@ -619,10 +674,36 @@ inline int resident_march_waves() {
       hipDeviceProp_t prop;
       if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
     }
-    return cus * 4 * 2;
+    int waves = cus * 4 * 2;
+    if (const char *e = std::getenv("APK_MARCH_WAVES")) {
+      const long v = std::strtol(e, nullptr, 10);
+      if (v > 0 && v < waves) waves = (int)v;
+    }
+    return waves;
   }();
   return n;
 }
+
+// Rows per piece of the dynamic leftover phase (fused_m12f_kernel).  A piece pays a stencil prologue of 1.5 - 2 rows, so
+// short pieces cost work and long ones leave the last waves marching alone.
+// Headline (GLM-MHD PPM+HLLD VL2, 8 x 128^3: 2368 columns on 2048 waves, 320 columns left over), one box, the wave-ends
+// variant build, span of the launch on the wall clock / HIP-event time of the march (profiles/m12f_piece_rows_sweep.txt):
+//   static split (22-row pieces)   1725 us / 1.746 ms
+//   8 rows    1656 us / 1.665 ms      11 rows   1639 us / 1.655 ms
+//   16 rows   1619 us / 1.643 ms      22 rows   1657 us / 1.646 ms
+// The choice is flat around 16 because the launch now ends with the slowest WHOLE column (it ends within 5 us of the
+// kernel in every dynamic run), which no piece length can move; 16 also divides the 128-row columns of the production
+// blocks, so no short piece is left.  Measured on the way (each against the kept schedule in one call on one box) and NOT
+// kept:
+//  * one ticket word per XCD (the leftover columns dealt to the XCDs in contiguous groups, a wave going on with the next
+//    XCD's word when its own is exhausted): 1.662 / 1.659 ms against 1.649 ms with the single word -- the same, so the
+//    single word it is;
+//  * the last 16 / 32 / 48 / 64 rows of every WHOLE column in the pool as well (the whole-column marches stop early, so
+//    that the pool lasts until the slower wave of every SIMD arrives): the average wave slot is occupied for 92.6 - 92.9 %
+//    of the span instead of 89.9 %, but the span does not move -- 1.632 - 1.640 / 1.650 - 1.666 / 1.656 / 1.666 ms
+//    against 1.634 - 1.646 ms.  A wave that has its SIMD to itself marches faster, and the extra prologues eat the rest:
+//    the slots left empty at the end are not lost work (profiles/m12f_piece_rows_sweep.txt).
+constexpr int kM12fPieceRows = 16;
 
 template <int FLUID, int RECON, int RS>
 inline bool launch_m12f(const PackView &u0, const PackView &u1, const StageParams &sp, const StagePlan &plan, hipStream_t s) {
@@ -642,12 +723,47 @@ inline bool launch_m12f(const PackView &u0, const PackView &u1, const StageParam
     const int nwaves = (int)nw;
     const int per_xcd = (nwaves + 7) / 8;
     const dim3 g((unsigned)(per_xcd * 8), 1, 1);
+    // Packs with at least as many columns as waves, and columns left over: the leftover rows are handed out piece by
+    // piece (the kernel's dynamic phase), from a ticket word zeroed here, in stream order.  Smaller packs keep the static
+    // split above.
+    const long long ncol = total_rows / u0.nx2;
+    unsigned long long *tickets = (ncol >= nwaves && ncol % nwaves != 0) ? sp.ctx->word(kWordMarchTickets) : nullptr;
+    int piece_rows = kM12fPieceRows;
+#if APK_M12F_WAVE_ENDS
+    if (const char *e = std::getenv("APK_M12F_STATIC")) {
+      if (std::atoi(e) != 0) tickets = nullptr;
+    }
+    if (const char *e = std::getenv("APK_M12F_PIECE_ROWS")) {
+      if (std::atoi(e) > 0) piece_rows = std::atoi(e);
+    }
+#endif
+    if (tickets && hipMemsetAsync(tickets, 0, sizeof(unsigned long long), s) != hipSuccess) return false;
     constexpr int lds_fc = m12f_keeps_raw_rows<FLUID, RECON>() ? 2 * lds : lds;  // (the rows as loaded, too)
     const bool ok = as_constants([&](auto X1H, auto FC, auto EX, auto LN) {
       if constexpr (m12f_compiled(RECON, EX, LN, FC, X1H))
-        hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EX, LN, (FC != 0), (X1H != 0)>), g, dim3(64), FC ? lds_fc : lds, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows);
+        hipLaunchKernelGGL((fused_m12f_kernel<FLUID, RECON, RS, EX, LN, (FC != 0), (X1H != 0)>), g, dim3(64), FC ? lds_fc : lds, s, u0, u1, sp, wpb, nwaves, per_xcd, total_rows, tickets, piece_rows);
       return m12f_compiled(RECON, EX, LN, FC, X1H);
     }, among<0, 1>{plan.x1_halo}, among<0, 1>{plan.from_cons != 0}, extra_among{plan.extra}, among<0, LEAN_PFLOOR, 1>{plan.lean});
+#if APK_M12F_WAVE_ENDS
+    {
+      static int calls = 0;
+      static const int want = std::getenv("APK_M12F_WAVE_ENDS_CALL") ? std::atoi(std::getenv("APK_M12F_WAVE_ENDS_CALL")) : 20;
+      const char *out = std::getenv("APK_M12F_WAVE_ENDS_OUT");
+      if (++calls == want && out) {
+        (void)hipStreamSynchronize(s);
+        std::vector<unsigned long long> h(3 * (size_t)kWaveEndsMax);
+        (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_m12f_wave_ends), h.size() * sizeof(unsigned long long));
+        if (FILE *f = std::fopen(out, "w")) {
+          std::fprintf(f, "# recon %d extra %d nwaves %d per_xcd %d columns %lld nx2 %d dynamic %d piece_rows %d\n", RECON, plan.extra,
+                       nwaves, per_xcd, ncol, u0.nx2, tickets ? 1 : 0, piece_rows);
+          std::fprintf(f, "# wave xcd start cols_end end (ticks of the 100 MHz wall clock)\n");
+          for (int w = 0; w < nwaves && w < kWaveEndsMax; ++w)
+            std::fprintf(f, "%d %d %llu %llu %llu\n", w, w / per_xcd, h[3 * w], h[3 * w + 1], h[3 * w + 2]);
+          std::fclose(f);
+        }
+      }
+    }
+#endif
 #if APK_M12F_TIMING
     {
       static int calls = 0;
