@@ -916,9 +916,7 @@ void apk_sim_destroy(apk_sim *s) {
     if (s->ev_fork) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(s->ev_fork));
     if (s->ev_join) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(s->ev_join));
     if (s->amr) amr_destroy_device_plans(s);
-    amr_free_buffers(s, s->amr_halo);
-    amr_free_buffers(s, s->amr_halo_faces);
-    amr_free_buffers(s, s->amr_halo_shell);
+    for (auto &m : s->amr_halo) amr_free_buffers(s, m);
     amr_free_buffers(s, s->amr_fluxmsg);
     amr_free_buffers(s, s->amr_move);
     dev_free(s, s->d_coarse);
@@ -1864,7 +1862,8 @@ long long apk_sim_message_generation(const apk_sim *s) { return s ? s->msg_gener
 // apk_sim_peer reports (0: back to the uniform mesh's)
 int apk_sim_select_messages(apk_sim *s, int which) {
   if (!s || which < 0 || which > 5 || (which > 0 && which < 5 && !s->amr) || (which == 5 && s->amr)) return APK_ERR_INVALID;
-  const apk_sim::MsgSet *sets[6] = {nullptr, &s->amr_halo, &s->amr_fluxmsg, &s->amr_halo_faces, &s->amr_halo_shell, nullptr};
+  const apk_sim::MsgSet *sets[6] = {nullptr, &s->amr_halo[AMR_FAMILY_FULL], &s->amr_fluxmsg, &s->amr_halo[AMR_FAMILY_FACES],
+                                    &s->amr_halo[AMR_FAMILY_SHELL], nullptr};
   s->active_msgs = sets[which];
   s->thin_msgs = which == 5;  // (the one-layer set of a uniform mesh; every exchange selects the set it moves anyway)
   s->msg_generation += 1;
@@ -1894,32 +1893,29 @@ int apk_sim_peer(const apk_sim *s, int p, apk_peer_info *o) {
 // x1..x3, 14..16: block boundaries x1..x3, 17..19: flux-correction copies x1..x3
 const std::vector<BoxRegion> *plan_of_phase(const apk_sim *s, int phase) {
   // (0..7: the uniform mesh's plans PH_LOCAL .. PH_UNPACK_THIN; 60..63: the same pack / unpack plans without the x1 faces,
-  // PH_PACK_NOX1 .. PH_UNPACK_THIN_NOX1 -- the numbers 10..49 below belong to refined meshes)
+  // PH_PACK_NOX1 .. PH_UNPACK_THIN_NOX1 -- the numbers 10..50 below belong to refined meshes)
   if (phase >= 0 && phase < PH_PACK_NOX1) return &s->mesh.plan[phase];
   if (phase >= 60 && phase < 60 + (PH_COUNT - PH_PACK_NOX1)) return &s->mesh.plan[PH_PACK_NOX1 + (phase - 60)];
   if (!s->amr) return nullptr;
   // this rank's share (local block numbers; kinds 1 / 2 = message buffers of the halo set for 20..24,
   // of the flux-correction set for 25..33)
   const auto &l = s->amr_local;
-  if (phase == 20) return &l.fill;
-  if (phase == 21) return &l.fill_pack;
-  if (phase == 22) return &l.fill_unpack;
   if (phase >= 25 && phase <= 27) return &l.flux_copy[phase - 25];
   if (phase >= 28 && phase <= 30) return &l.flux_pack[phase - 28];
   if (phase >= 31 && phase <= 33) return &l.flux_unpack[phase - 31];
   if (phase >= 34 && phase <= 36) return &l.coarse_bc[phase - 34];
-  if (phase >= 37 && phase <= 39) return &l.fine_bc[phase - 37];
-  // the exchanges of the stage loop: 40..42 faces only (fill copies, packs, unpacks), 43 the fill copies of 40 without
-  // the same-level same-rank ones (direct neighbour addressing), 44..46 the shell (fill copies, packs, unpacks),
-  // 47..49 its block boundaries
-  if (phase == 40) return &l.fill_faces;
-  if (phase == 41) return &l.fill_pack_faces;
-  if (phase == 42) return &l.fill_unpack_faces;
-  if (phase == 43) return &l.fill_direct;
-  if (phase == 44) return &l.fill_shell;
-  if (phase == 45) return &l.fill_pack_shell;
-  if (phase == 46) return &l.fill_unpack_shell;
-  if (phase >= 47 && phase <= 49) return &l.fine_bc_shell[phase - 47];
+  // the ghost exchange in its forms (amr_forms.hpp): a family's whole fill copies, packs and unpacks at 20..22 (full),
+  // 40..42 (faces: the stage loop's) and 44..46 (shell); the full and the shell family's block boundaries at 37..39 and
+  // 47..49; the fill copies of 40 and 44 without the same-level same-rank ones (direct neighbour addressing) at 43 and 50
+  const int first[AMR_FAMILIES] = {20, 40, 44}, bc[AMR_FAMILIES] = {37, -1, 47};
+  for (int fam = 0; fam < AMR_FAMILIES; ++fam) {
+    if (phase == first[fam]) return &l.fill[AMR_FAMILY[fam].whole];
+    if (phase == first[fam] + 1) return &l.family[fam].pack;
+    if (phase == first[fam] + 2) return &l.family[fam].unpack;
+    if (bc[fam] >= 0 && phase >= bc[fam] && phase < bc[fam] + 3) return &l.family[fam].fine_bc[phase - bc[fam]];
+  }
+  if (phase == 43) return &l.fill[AMR_XCHG_DIRECT];
+  if (phase == 50) return &l.fill[AMR_XCHG_SHELL_DIRECT];
   if (phase == 10) return &s->amr_plans.fill;
   if (phase >= 11 && phase <= 13) return &s->amr_plans.coarse_bc[phase - 11];
   if (phase >= 14 && phase <= 16) return &s->amr_plans.fine_bc[phase - 14];
@@ -1957,10 +1953,9 @@ const std::vector<AmrRefOp> *ops_of(const apk_sim *s, int which) {
   if (!s->amr) return nullptr;
   // 10..14: this rank's share of 0..4 (local block numbers)
   if (which == 10) return &s->amr_local.restrict_own;
-  if (which == 11) return &s->amr_local.prolongate;
+  if (which == 11) return &s->amr_local.family[AMR_FAMILY_FULL].prolongate;
   if (which >= 12 && which <= 14) return &s->amr_local.flux_restrict[which - 12];
-  if (which == 15) return &s->amr_local.prolongate_faces;  // (of the faces-only exchange / of the shell exchange)
-  if (which == 16) return &s->amr_local.prolongate_shell;
+  if (which == 15 || which == 16) return &s->amr_local.family[AMR_FAMILY_FACES + (which - 15)].prolongate;  // (faces, shell)
   if (which == 0) return &s->amr_plans.restrict_own;
   if (which == 1) return &s->amr_plans.prolongate;
   if (which >= 2 && which <= 4) return &s->amr_plans.flux_restrict[which - 2];

@@ -13,6 +13,7 @@
 #include "../../../include/apk_host.h"
 #include "../cooling_table.hpp"
 #include "amr.hpp"
+#include "amr_forms.hpp"
 #include "feedback.hpp"
 #include "mesh.hpp"
 #include "params.hpp"
@@ -353,77 +354,62 @@ struct apk_sim {
   // ranks turned into packs / unpacks of one message per peer
   apk::AmrPartition amr_part;
   struct AmrLocalPlans {
-    std::vector<apk::AmrRefOp> restrict_own, prolongate, flux_restrict[3];
-    std::vector<apk::BoxRegion> fill, fill_pack, fill_unpack, coarse_bc[3], fine_bc[3];
+    std::vector<apk::AmrRefOp> restrict_own, flux_restrict[3];
+    std::vector<apk::BoxRegion> coarse_bc[3];
+    // the ghost exchange in its forms (amr_forms.hpp): what a family shares, and every form's same-rank fill list
+    struct Family {
+      std::vector<apk::AmrRefOp> prolongate;
+      std::vector<apk::BoxRegion> pack, unpack;
+      std::vector<apk::BoxRegion> fine_bc[3];  // (empty where AMR_FAMILY[].bc names another family's)
+    } family[apk::AMR_FAMILIES];
+    std::vector<apk::BoxRegion> fill[apk::AMR_XCHG_FORMS];
     std::vector<apk::BoxRegion> flux_copy[3], flux_pack[3], flux_unpack[3];
     // the correction after a fused stage averages the fine fluxes of same-rank faces inside the fix kernel: the
     // restriction operators of flux_copy[d], entry for entry, and those whose coarse side lives on another rank (the
     // only ones that still run as operators there)
     std::vector<apk::AmrRefOp> flux_fused_ops[3], flux_restrict_remote[3];
-    // the exchange of the stage loop: without the boxes that fill ghost zones behind edges and corners
-    // (BoxRegion::corner); its messages are laid out by the same walk over the filtered global list
-    std::vector<apk::AmrRefOp> prolongate_faces;
-    std::vector<apk::BoxRegion> fill_faces, fill_pack_faces, fill_unpack_faces;
-    // ... and without the same-rank copies between blocks of one level either (BoxRegion::same_face): the exchange
-    // after a stage when the next one reads those neighbours through the face table (amr_direct)
-    std::vector<apk::BoxRegion> fill_direct;
-    // the exchange before a refinement check when the next cycle's first stage reads at most AMR_SHELL_DEPTH ghost
-    // layers: every ghost zone, edges and corners too, but only that deep (BuildAmrPlans(fill_depth))
-    std::vector<apk::AmrRefOp> prolongate_shell;
-    std::vector<apk::BoxRegion> fill_shell, fill_pack_shell, fill_unpack_shell, fine_bc_shell[3];
-    std::vector<apk::BoxRegion> fill_shell_direct;  // fill_shell without the same-level face copies
   } amr_local;
   struct MsgSet {
     apk::AmrMessages plan;
     std::vector<double *> send, recv;
     std::vector<int64_t> send_cap, recv_cap;
   };
-  MsgSet amr_halo, amr_fluxmsg, amr_move, amr_halo_faces, amr_halo_shell;
-  // refined meshes: the stage loop fills (and converts to primitives) only the ghost zones behind block FACES
-  // (AMR_GHOSTS_FACES), or all of them AMR_SHELL_DEPTH layers deep before a refinement check (AMR_GHOSTS_SHELL: what
-  // the tagging criteria and a donor-cell / PLM first stage read); accessors and regridding complete them first
-  // (sync_ghosts)
-  int amr_ghost_state = 0;  // AMR_GHOSTS_COMPLETE
+  MsgSet amr_halo[apk::AMR_FAMILIES], amr_fluxmsg, amr_move;
+  // refined meshes: the form of the exchange run last, that is, which ghost zones of cons are current (amr_forms.hpp);
+  // accessors and regridding complete them first (sync_ghosts)
+  int amr_ghost_state = apk::AMR_XCHG_FULL;
   bool amr_full_exchange = false;  // apk_sim_set_amr_full_exchange
   const MsgSet *active_msgs = nullptr;  // the message set apk_sim_peer reports (null: the uniform mesh's)
   long long msg_generation = 0;         // bumped whenever that set, its sizes or its buffers change
   struct AmrDevice {
-    std::vector<apk_refine_plan *> restrict_own[2], prolongate[2], flux_restrict[3], flux_restrict_remote[3];
-    apk_copy_plan *fill[2] = {nullptr, nullptr}, *fill_pack[2] = {nullptr, nullptr}, *fill_unpack[2] = {nullptr, nullptr};
+    std::vector<apk_refine_plan *> restrict_own[2], flux_restrict[3], flux_restrict_remote[3];
+    apk_copy_plan *coarse_bc[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    // The device forms of AmrLocalPlans::family and ::fill, per cons buffer.  The launches of the exchange before / after
+    // the message exchange take no per-cycle arguments: each half is captured once per mesh into a hipGraph and replayed
+    // as ONE launch (void* = hipGraphExec_t; null = not captured, the plans are launched one by one) -- `post` belongs
+    // to the family, `pre` to the form
+    struct Family {
+      std::vector<apk_refine_plan *> prolongate;
+      apk_copy_plan *pack = nullptr, *unpack = nullptr, *fine_bc[3] = {nullptr, nullptr, nullptr};
+      void *post = nullptr;
+    } family[2][apk::AMR_FAMILIES];
+    struct Form {
+      apk_copy_plan *fill = nullptr;
+      void *pre = nullptr;
+    } form[2][apk::AMR_XCHG_FORMS];
+    // no messages between the two halves (one rank): the `pre` graphs hold both halves -- one graph launch per exchange
+    bool xchg_whole = false;
+    apk_copy_plan *flux_copy[3] = {nullptr, nullptr, nullptr};
     apk_copy_plan *flux_pack[3] = {nullptr, nullptr, nullptr}, *flux_unpack[3] = {nullptr, nullptr, nullptr};
     // the correction applied after a fused stage instead (apk_flux_fix_plan): same-rank faces and
     // faces whose fine side arrived in a message, per cons buffer the stage wrote
-    // The launches of the multilevel exchange before / after the message exchange take no per-cycle
-    // arguments: each half is captured once per mesh into a hipGraph and replayed as ONE launch
-    // (void* = hipGraphExec_t; null = not captured, the plans are launched one by one)
-    void *xchg_pre[2] = {nullptr, nullptr}, *xchg_post[2] = {nullptr, nullptr};
-    // no messages between the two halves (one rank): the `pre` graphs hold both halves -- one graph launch per exchange
-    bool xchg_whole = false;
-    // the faces-only exchange of the stage loop (AmrLocalPlans::fill_faces ...)
-    std::vector<apk_refine_plan *> prolongate_faces[2];
-    apk_copy_plan *fill_faces[2] = {nullptr, nullptr}, *fill_pack_faces[2] = {nullptr, nullptr}, *fill_unpack_faces[2] = {nullptr, nullptr};
-    void *xchg_pre_faces[2] = {nullptr, nullptr}, *xchg_post_faces[2] = {nullptr, nullptr};
-    apk_copy_plan *fill_direct[2] = {nullptr, nullptr};  // (AmrLocalPlans::fill_direct; the other plans of the faces-only exchange)
-    void *xchg_pre_direct[2] = {nullptr, nullptr};
-    // the shell exchange (AmrLocalPlans::fill_shell ...)
-    std::vector<apk_refine_plan *> prolongate_shell[2];
-    apk_copy_plan *fill_shell[2] = {nullptr, nullptr}, *fill_pack_shell[2] = {nullptr, nullptr}, *fill_unpack_shell[2] = {nullptr, nullptr};
-    apk_copy_plan *fine_bc_shell[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    void *xchg_pre_shell[2] = {nullptr, nullptr}, *xchg_post_shell[2] = {nullptr, nullptr};
-    // the shell exchange without the same-rank same-level face copies (AMR_XCHG_SHELL_DIRECT: the tag kernel, ConsToPrim
-    // and the next predictor follow the face table there)
-    apk_copy_plan *fill_shell_direct[2] = {nullptr, nullptr};
-    void *xchg_pre_shell_direct[2] = {nullptr, nullptr};
     apk_flux_fix_plan *flux_fix[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    apk_flux_fix_plan *flux_fix_unpack[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     apk_flux_fix_plan *flux_fix_all[2] = {nullptr, nullptr}, *flux_fix_unpack_all[2] = {nullptr, nullptr};  // all directions in one launch
     // the faces (6 * local block + face) with a coarser or finer block behind them: the only boundary-plane
     // fluxes the correction after a fused stage reads (apk_calculate_fluxes_boundary_list)
     int *d_cf_faces = nullptr;
     int n_cf_faces = 0;
-    apk_flux_fix_plan *flux_fix_unpack[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    apk_copy_plan *coarse_bc[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    apk_copy_plan *fine_bc[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    apk_copy_plan *flux_copy[3] = {nullptr, nullptr, nullptr};
   } amr_dev;
   // RKL2 super-time-stepping (host/sts.cpp): the registers MY0 and Yjm2 (conserved-size buffers, allocated when rkl2 is
   // on) and the packs presenting them; Y0 is the u1 buffer.  sts_fused: apk_amd/sts_substage = fused | arrays (the default

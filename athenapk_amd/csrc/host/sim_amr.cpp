@@ -61,38 +61,39 @@ void amr_localize(apk_sim *s) {
     }
   };
   take_ops(g.restrict_own, l.restrict_own);
-  take_ops(g.prolongate, l.prolongate);
   for (int d = 0; d < 3; ++d) {
     take_ops(g.flux_restrict[d], l.flux_restrict[d]);
     take_bc(g.coarse_bc[d], l.coarse_bc[d]);
-    take_bc(g.fine_bc[d], l.fine_bc[d]);
   }
-  s->amr_halo.plan = AmrMessages();
+  // a family's share of the global fill list `fill`: its messages, packs and unpacks, and the same-rank copies as the
+  // fill list of its whole form; `direct` (a form or -1) takes that list without the copies between blocks of one level
+  auto take_family = [&](int fam, const std::vector<BoxRegion> &fill, int direct) {
+    const int whole = AMR_FAMILY[fam].whole;
+    AmrRegisterPeers(fill, part, part, rank, s->amr_halo[fam].plan);
+    AmrLocalize(fill, part, part, rank, s->amr_halo[fam].plan, l.fill[whole], l.family[fam].pack, l.family[fam].unpack);
+    for (const BoxRegion &r : l.fill[whole])
+      if (direct >= 0 && !r.same_face) l.fill[direct].push_back(r);
+  };
+  for (auto &m : s->amr_halo) m.plan = AmrMessages();
   s->amr_fluxmsg.plan = AmrMessages();
-  s->amr_halo_faces.plan = AmrMessages();
-  AmrRegisterPeers(g.fill, part, part, rank, s->amr_halo.plan);
-  AmrLocalize(g.fill, part, part, rank, s->amr_halo.plan, l.fill, l.fill_pack, l.fill_unpack);
-  {  // the stage loop's exchange: the same lists without the boxes behind edges and corners
+  take_family(AMR_FAMILY_FULL, g.fill, -1);
+  take_ops(g.prolongate, l.family[AMR_FAMILY_FULL].prolongate);
+  for (int d = 0; d < 3; ++d) take_bc(g.fine_bc[d], l.family[AMR_FAMILY_FULL].fine_bc[d]);
+  {  // the faces family: the same lists without the boxes behind edges and corners (BoxRegion::corner); its messages are
+     // laid out by the same walk over the filtered global list
     std::vector<BoxRegion> faces;
     for (const BoxRegion &r : g.fill)
       if (!r.corner) faces.push_back(r);
-    AmrRegisterPeers(faces, part, part, rank, s->amr_halo_faces.plan);
-    AmrLocalize(faces, part, part, rank, s->amr_halo_faces.plan, l.fill_faces, l.fill_pack_faces, l.fill_unpack_faces);
-    for (const AmrRefOp &o : l.prolongate)
-      if (!o.corner) l.prolongate_faces.push_back(o);
-    for (const BoxRegion &r : l.fill_faces)
-      if (!r.same_face) l.fill_direct.push_back(r);
+    take_family(AMR_FAMILY_FACES, faces, AMR_XCHG_DIRECT);
+    for (const AmrRefOp &o : l.family[AMR_FAMILY_FULL].prolongate)
+      if (!o.corner) l.family[AMR_FAMILY_FACES].prolongate.push_back(o);
   }
-  s->amr_halo_shell.plan = AmrMessages();
-  if (s->amr_geom.ng > AMR_SHELL_DEPTH) {  // the shell exchange: the same walk with shallower boxes
+  if (amr_has_shell(s)) {  // the shell family: the same walk with shallower boxes (BuildAmrPlans(fill_depth))
     AmrPlans shell;
     BuildAmrPlans(*s->amr, s->amr_geom, shell, AMR_SHELL_DEPTH);
-    AmrRegisterPeers(shell.fill, part, part, rank, s->amr_halo_shell.plan);
-    AmrLocalize(shell.fill, part, part, rank, s->amr_halo_shell.plan, l.fill_shell, l.fill_pack_shell, l.fill_unpack_shell);
-    for (const BoxRegion &r : l.fill_shell)
-      if (!r.same_face) l.fill_shell_direct.push_back(r);
-    take_ops(shell.prolongate, l.prolongate_shell);
-    for (int d = 0; d < 3; ++d) take_bc(shell.fine_bc[d], l.fine_bc_shell[d]);
+    take_family(AMR_FAMILY_SHELL, shell.fill, AMR_XCHG_SHELL_DIRECT);
+    take_ops(shell.prolongate, l.family[AMR_FAMILY_SHELL].prolongate);
+    for (int d = 0; d < 3; ++d) take_bc(shell.fine_bc[d], l.family[AMR_FAMILY_SHELL].fine_bc[d]);
   }
   for (int d = 0; d < 3; ++d) {  // (BuildAmrPlans appends a face's restriction and its copy together: same index)
     for (size_t n = 0; n < g.flux_copy[d].size(); ++n) {
@@ -263,37 +264,21 @@ void amr_destroy_device_plans(apk_sim *s) {
   a.d_cf_faces = nullptr;
   for (int par = 0; par < 2; ++par) {
     for (apk_refine_plan *p : a.restrict_own[par]) apk_refine_plan_destroy(p);
-    for (apk_refine_plan *p : a.prolongate[par]) apk_refine_plan_destroy(p);
     a.restrict_own[par].clear();
-    a.prolongate[par].clear();
-    apk_copy_plan_destroy(a.fill[par]);
-    apk_copy_plan_destroy(a.fill_pack[par]);
-    apk_copy_plan_destroy(a.fill_unpack[par]);
-    a.fill[par] = a.fill_pack[par] = a.fill_unpack[par] = nullptr;
-    for (apk_refine_plan *p : a.prolongate_faces[par]) apk_refine_plan_destroy(p);
-    a.prolongate_faces[par].clear();
-    apk_copy_plan_destroy(a.fill_faces[par]);
-    apk_copy_plan_destroy(a.fill_pack_faces[par]);
-    apk_copy_plan_destroy(a.fill_unpack_faces[par]);
-    a.fill_faces[par] = a.fill_pack_faces[par] = a.fill_unpack_faces[par] = nullptr;
-    apk_copy_plan_destroy(a.fill_direct[par]);
-    a.fill_direct[par] = nullptr;
-    for (apk_refine_plan *p : a.prolongate_shell[par]) apk_refine_plan_destroy(p);
-    a.prolongate_shell[par].clear();
-    apk_copy_plan_destroy(a.fill_shell[par]);
-    apk_copy_plan_destroy(a.fill_shell_direct[par]);
-    a.fill_shell_direct[par] = nullptr;
-    apk_copy_plan_destroy(a.fill_pack_shell[par]);
-    apk_copy_plan_destroy(a.fill_unpack_shell[par]);
-    a.fill_shell[par] = a.fill_pack_shell[par] = a.fill_unpack_shell[par] = nullptr;
-    for (int d = 0; d < 3; ++d) {
-      apk_copy_plan_destroy(a.fine_bc_shell[par][d]);
-      a.fine_bc_shell[par][d] = nullptr;
-    }
     for (int d = 0; d < 3; ++d) {
       apk_copy_plan_destroy(a.coarse_bc[par][d]);
-      apk_copy_plan_destroy(a.fine_bc[par][d]);
-      a.coarse_bc[par][d] = a.fine_bc[par][d] = nullptr;
+      a.coarse_bc[par][d] = nullptr;
+    }
+    for (auto &f : a.family[par]) {  // (a family owns the block-boundary plans it built: a borrower's are null)
+      for (apk_refine_plan *p : f.prolongate) apk_refine_plan_destroy(p);
+      apk_copy_plan_destroy(f.pack);
+      apk_copy_plan_destroy(f.unpack);
+      for (int d = 0; d < 3; ++d) apk_copy_plan_destroy(f.fine_bc[d]);
+      f = apk_sim::AmrDevice::Family();
+    }
+    for (auto &f : a.form[par]) {
+      apk_copy_plan_destroy(f.fill);
+      f = apk_sim::AmrDevice::Form();
     }
   }
   for (int d = 0; d < 3; ++d) {
@@ -464,36 +449,25 @@ int amr_rebuild(apk_sim *s) {
   } catch (const std::exception &e) {
     return fail(s, APK_ERR_INVALID, e.what());
   }
-  SIM_TRY(s, amr_ensure_buffers(s, s->amr_halo, "halo"));
-  SIM_TRY(s, amr_ensure_buffers(s, s->amr_halo_faces, "halo_faces"));
-  SIM_TRY(s, amr_ensure_buffers(s, s->amr_halo_shell, "halo_shell"));
+  for (int fam = 0; fam < AMR_FAMILIES; ++fam) SIM_TRY(s, amr_ensure_buffers(s, s->amr_halo[fam], AMR_FAMILY[fam].tag));
   SIM_TRY(s, amr_ensure_buffers(s, s->amr_fluxmsg, "fluxcorr"));
   amr_destroy_device_plans(s);
   auto &a = s->amr_dev;
   const auto &p = s->amr_local;
   for (int par = 0; par < 2; ++par) {
     SIM_TRY(s, amr_make_refine_plans(s, par, p.restrict_own, a.restrict_own[par]));
-    SIM_TRY(s, amr_make_refine_plans(s, par, p.prolongate, a.prolongate[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill, nullptr, &a.fill[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_pack, &s->amr_halo, &a.fill_pack[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_unpack, &s->amr_halo, &a.fill_unpack[par]));
-    SIM_TRY(s, amr_make_refine_plans(s, par, p.prolongate_faces, a.prolongate_faces[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_faces, nullptr, &a.fill_faces[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_pack_faces, &s->amr_halo_faces, &a.fill_pack_faces[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_unpack_faces, &s->amr_halo_faces, &a.fill_unpack_faces[par]));
-    SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_direct, nullptr, &a.fill_direct[par]));
-    if (amr_has_shell(s)) {
-      SIM_TRY(s, amr_make_refine_plans(s, par, p.prolongate_shell, a.prolongate_shell[par]));
-      SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_shell, nullptr, &a.fill_shell[par]));
-      SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_shell_direct, nullptr, &a.fill_shell_direct[par]));
-      SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_pack_shell, &s->amr_halo_shell, &a.fill_pack_shell[par]));
-      SIM_TRY(s, amr_make_copy_plan(s, par, p.fill_unpack_shell, &s->amr_halo_shell, &a.fill_unpack_shell[par]));
-      for (int d = 0; d < 3; ++d) SIM_TRY(s, amr_make_copy_plan(s, par, p.fine_bc_shell[d], nullptr, &a.fine_bc_shell[par][d]));
+    for (int d = 0; d < 3; ++d) SIM_TRY(s, amr_make_copy_plan(s, par, p.coarse_bc[d], nullptr, &a.coarse_bc[par][d]));
+    for (int fam = 0; fam < AMR_FAMILIES; ++fam) {
+      if (!amr_has_family(s, fam)) continue;
+      const auto &pf = p.family[fam];
+      auto &af = a.family[par][fam];
+      SIM_TRY(s, amr_make_refine_plans(s, par, pf.prolongate, af.prolongate));
+      SIM_TRY(s, amr_make_copy_plan(s, par, pf.pack, &s->amr_halo[fam], &af.pack));
+      SIM_TRY(s, amr_make_copy_plan(s, par, pf.unpack, &s->amr_halo[fam], &af.unpack));
+      for (int d = 0; d < 3 && AMR_FAMILY[fam].bc == fam; ++d) SIM_TRY(s, amr_make_copy_plan(s, par, pf.fine_bc[d], nullptr, &af.fine_bc[d]));
     }
-    for (int d = 0; d < 3; ++d) {
-      SIM_TRY(s, amr_make_copy_plan(s, par, p.coarse_bc[d], nullptr, &a.coarse_bc[par][d]));
-      SIM_TRY(s, amr_make_copy_plan(s, par, p.fine_bc[d], nullptr, &a.fine_bc[par][d]));
-    }
+    for (int form = 0; form < AMR_XCHG_FORMS; ++form)
+      if (amr_has_family(s, AMR_FORM_FAMILY[form])) SIM_TRY(s, amr_make_copy_plan(s, par, p.fill[form], nullptr, &a.form[par][form].fill));
   }
   for (int d = 0; d < s->mesh.ndim; ++d) {
     SIM_TRY(s, amr_make_refine_plans(s, 0, p.flux_restrict[d], a.flux_restrict[d]));
@@ -548,56 +522,38 @@ int amr_rebuild(apk_sim *s) {
   }
   // (a graph launch costs the host ~8 us and the stream a gap of that size: with no messages to wait for between the
   // halves -- one rank -- an exchange is ONE graph)
-  a.xchg_whole = s->amr_halo.plan.peers.empty() && s->amr_halo_faces.plan.peers.empty() && s->amr_halo_shell.plan.peers.empty();
-  const bool w = a.xchg_whole;
+  a.xchg_whole = true;
+  for (const auto &m : s->amr_halo) a.xchg_whole = a.xchg_whole && m.plan.peers.empty();
   for (int par = 0; par < 2; ++par) {
-    amr_capture_half(s, par, true, 0, &a.xchg_pre[par], w);
-    amr_capture_half(s, par, false, 0, &a.xchg_post[par]);
-    amr_capture_half(s, par, true, 1, &a.xchg_pre_faces[par], w);
-    amr_capture_half(s, par, false, 1, &a.xchg_post_faces[par]);
-    amr_capture_half(s, par, true, 2, &a.xchg_pre_direct[par], w);
-    if (amr_has_shell(s)) {
-      amr_capture_half(s, par, true, AMR_XCHG_SHELL, &a.xchg_pre_shell[par], w);
-      amr_capture_half(s, par, true, AMR_XCHG_SHELL_DIRECT, &a.xchg_pre_shell_direct[par], w);
-      amr_capture_half(s, par, false, AMR_XCHG_SHELL, &a.xchg_post_shell[par]);
-    }
+    for (int form = 0; form < AMR_XCHG_FORMS; ++form)
+      if (amr_has_family(s, AMR_FORM_FAMILY[form])) amr_capture_half(s, par, true, form, &a.form[par][form].pre, a.xchg_whole);
+    for (int fam = 0; fam < AMR_FAMILIES; ++fam)  // (the post half is the same for every form of a family)
+      if (amr_has_family(s, fam)) amr_capture_half(s, par, false, AMR_FAMILY[fam].whole, &a.family[par][fam].post);
   }
-  s->amr_ghost_state = AMR_GHOSTS_COMPLETE;  // (whoever rebuilt the plans fills the new mesh completely next)
+  s->amr_ghost_state = AMR_XCHG_FULL;  // (whoever rebuilt the plans fills the new mesh completely next)
   return build_packs(s);
 }
 
-// the multilevel ghost exchange of the state in cons buffer `buf` (see amr.hpp), in the two halves
-// either side of the message exchange
 // is there a shell exchange (more ghost layers than it fills)?
 bool amr_has_shell(const apk_sim *s) { return s->amr_geom.ng > AMR_SHELL_DEPTH; }
+// does this mesh build family `fam`'s plans?
+bool amr_has_family(const apk_sim *s, int fam) { return fam != AMR_FAMILY_SHELL || amr_has_shell(s); }
 
-// (mode: AMR_XCHG_FULL, AMR_XCHG_FACES, AMR_XCHG_DIRECT or AMR_XCHG_SHELL)
-int amr_exchange_pre(apk_sim *s, int buf, int mode) {
+// the multilevel ghost exchange of the state in cons buffer `buf` (see amr.hpp) in one of its forms (amr_forms.hpp:
+// AMR_XCHG_FULL, _FACES, _DIRECT, _SHELL or _SHELL_DIRECT), in the two halves either side of the message exchange
+int amr_exchange_pre(apk_sim *s, int buf, int form) {
   auto &a = s->amr_dev;
   for (apk_refine_plan *p : a.restrict_own[buf]) SIM_TRY(s, apk_refine_plan_run(s->ctx, p, s->stream));
-  if (mode == AMR_XCHG_SHELL || mode == AMR_XCHG_SHELL_DIRECT) {
-    SIM_TRY(s, apk_copy_plan_run(s->ctx, a.fill_pack_shell[buf], s->stream));
-    return apk_copy_plan_run(s->ctx, mode == AMR_XCHG_SHELL_DIRECT ? a.fill_shell_direct[buf] : a.fill_shell[buf], s->stream);
-  }
-  const bool faces = mode != AMR_XCHG_FULL;
-  SIM_TRY(s, apk_copy_plan_run(s->ctx, faces ? a.fill_pack_faces[buf] : a.fill_pack[buf], s->stream));
-  SIM_TRY(s, apk_copy_plan_run(s->ctx, mode == AMR_XCHG_DIRECT ? a.fill_direct[buf] : (faces ? a.fill_faces[buf] : a.fill[buf]), s->stream));
-  return APK_OK;
+  SIM_TRY(s, apk_copy_plan_run(s->ctx, a.family[buf][AMR_FORM_FAMILY[form]].pack, s->stream));
+  return apk_copy_plan_run(s->ctx, a.form[buf][form].fill, s->stream);
 }
-int amr_exchange_post(apk_sim *s, int buf, int mode) {
+int amr_exchange_post(apk_sim *s, int buf, int form) {
   auto &a = s->amr_dev;
-  if (mode == AMR_XCHG_SHELL || mode == AMR_XCHG_SHELL_DIRECT) {
-    SIM_TRY(s, apk_copy_plan_run(s->ctx, a.fill_unpack_shell[buf], s->stream));
-    for (int d = 0; d < 3; ++d) SIM_TRY(s, apk_copy_plan_run(s->ctx, a.coarse_bc[buf][d], s->stream));
-    for (apk_refine_plan *p : a.prolongate_shell[buf]) SIM_TRY(s, apk_refine_plan_run(s->ctx, p, s->stream));
-    for (int d = 0; d < 3; ++d) SIM_TRY(s, apk_copy_plan_run(s->ctx, a.fine_bc_shell[buf][d], s->stream));
-    return APK_OK;
-  }
-  const bool faces = mode != AMR_XCHG_FULL;
-  SIM_TRY(s, apk_copy_plan_run(s->ctx, faces ? a.fill_unpack_faces[buf] : a.fill_unpack[buf], s->stream));
+  const int fam = AMR_FORM_FAMILY[form];
+  SIM_TRY(s, apk_copy_plan_run(s->ctx, a.family[buf][fam].unpack, s->stream));
   for (int d = 0; d < 3; ++d) SIM_TRY(s, apk_copy_plan_run(s->ctx, a.coarse_bc[buf][d], s->stream));
-  for (apk_refine_plan *p : (faces ? a.prolongate_faces[buf] : a.prolongate[buf])) SIM_TRY(s, apk_refine_plan_run(s->ctx, p, s->stream));
-  for (int d = 0; d < 3; ++d) SIM_TRY(s, apk_copy_plan_run(s->ctx, a.fine_bc[buf][d], s->stream));
+  for (apk_refine_plan *p : a.family[buf][fam].prolongate) SIM_TRY(s, apk_refine_plan_run(s->ctx, p, s->stream));
+  for (int d = 0; d < 3; ++d) SIM_TRY(s, apk_copy_plan_run(s->ctx, a.family[buf][AMR_FAMILY[fam].bc].fine_bc[d], s->stream));
   return APK_OK;
 }
 
@@ -638,46 +594,33 @@ void amr_capture_half(apk_sim *s, int buf, bool pre, int mode, void **out, bool 
 
 void amr_destroy_graphs(apk_sim *s) {
   auto &a = s->amr_dev;
+  auto destroy = [](void *&g) {
+    if (g) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(g));
+    g = nullptr;
+  };
   for (int buf = 0; buf < 2; ++buf) {
-    if (a.xchg_pre[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_pre[buf]));
-    if (a.xchg_post[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_post[buf]));
-    if (a.xchg_pre_faces[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_pre_faces[buf]));
-    if (a.xchg_post_faces[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_post_faces[buf]));
-    if (a.xchg_pre_direct[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_pre_direct[buf]));
-    if (a.xchg_pre_shell[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_pre_shell[buf]));
-    if (a.xchg_pre_shell_direct[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_pre_shell_direct[buf]));
-    a.xchg_pre_shell_direct[buf] = nullptr;
-    if (a.xchg_post_shell[buf]) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(a.xchg_post_shell[buf]));
-    a.xchg_pre[buf] = a.xchg_post[buf] = a.xchg_pre_faces[buf] = a.xchg_post_faces[buf] = a.xchg_pre_direct[buf] = nullptr;
-    a.xchg_pre_shell[buf] = a.xchg_post_shell[buf] = nullptr;
+    for (auto &f : a.form[buf]) destroy(f.pre);
+    for (auto &f : a.family[buf]) destroy(f.post);
   }
 }
 
-// AMR_XCHG_FACES: the stage loop's exchange -- everything but the ghost zones behind edges and corners,
-// which no sweep or flux correction reads (sync_ghosts completes them for accessors, tagging and regridding;
-// the last stage of a cycle that checks the refinement criteria exchanges in full).  AMR_XCHG_DIRECT: nor the
-// ghost zones behind faces shared with a same-rank block of the same level, which the stages then read from
-// that block's interior (the face table built in amr_rebuild; same-level faces of OTHER ranks still arrive
-// in the messages).
-int amr_exchange(apk_sim *s, int buf, int mode) {
+// One exchange in form `form` (amr_forms.hpp).  What the cheaper forms leave out, sync_ghosts completes for accessors,
+// tagging and regridding; the last stage of a cycle that checks the refinement criteria exchanges in full or as a
+// shell.  The zones the direct forms leave out, the stages read from the neighbour's interior (the face table built in
+// amr_rebuild; same-level faces of OTHER ranks still arrive in the messages).
+int amr_exchange(apk_sim *s, int buf, int form) {
   auto &a = s->amr_dev;
-  if ((mode == AMR_XCHG_SHELL || mode == AMR_XCHG_SHELL_DIRECT) && !amr_has_shell(s)) mode = AMR_XCHG_FULL;
-  const bool faces = mode == AMR_XCHG_FACES || mode == AMR_XCHG_DIRECT;
-  const bool shell = mode == AMR_XCHG_SHELL || mode == AMR_XCHG_SHELL_DIRECT;
-  void *pre = mode == AMR_XCHG_SHELL_DIRECT ? a.xchg_pre_shell_direct[buf]
-              : mode == AMR_XCHG_SHELL ? a.xchg_pre_shell[buf]
-              : mode == AMR_XCHG_DIRECT ? a.xchg_pre_direct[buf] : (faces ? a.xchg_pre_faces[buf] : a.xchg_pre[buf]);
-  void *post = shell ? a.xchg_post_shell[buf] : (faces ? a.xchg_post_faces[buf] : a.xchg_post[buf]);
+  if (!amr_has_family(s, AMR_FORM_FAMILY[form])) form = AMR_XCHG_FULL;  // (a shell asked for on a mesh that has none)
+  const int fam = AMR_FORM_FAMILY[form];
+  void *pre = a.form[buf][form].pre, *post = a.family[buf][fam].post;
   if (pre) SIM_HIP(s, hipGraphLaunch(static_cast<hipGraphExec_t>(pre), hs(s)));
-  else SIM_TRY(s, amr_exchange_pre(s, buf, mode));
+  else SIM_TRY(s, amr_exchange_pre(s, buf, form));
   if (!(pre && a.xchg_whole)) {  // (else the graph held both halves)
-    SIM_TRY(s, amr_exchange_messages(s, shell ? s->amr_halo_shell : (faces ? s->amr_halo_faces : s->amr_halo)));
+    SIM_TRY(s, amr_exchange_messages(s, s->amr_halo[fam]));
     if (post) SIM_HIP(s, hipGraphLaunch(static_cast<hipGraphExec_t>(post), hs(s)));
-    else SIM_TRY(s, amr_exchange_post(s, buf, mode));
+    else SIM_TRY(s, amr_exchange_post(s, buf, form));
   }
-  // (of cons; the caller converts to primitives)
-  s->amr_ghost_state = mode == AMR_XCHG_FULL ? AMR_GHOSTS_COMPLETE
-                       : (mode == AMR_XCHG_SHELL ? AMR_GHOSTS_SHELL : (mode == AMR_XCHG_SHELL_DIRECT ? AMR_GHOSTS_SHELL_DIRECT : AMR_GHOSTS_FACES));
+  s->amr_ghost_state = form;  // (of cons; the caller converts to primitives)
   return APK_OK;
 }
 
@@ -1003,13 +946,13 @@ int amr_tags_begin(apk_sim *s, AmrTagRequest *req) {
   // behind edges and corners included, which the stage loop's faces-only exchange leaves stale.  The last
   // stage of a checking cycle exchanges in full or AMR_SHELL_DEPTH (= the criteria's reach) layers deep (do_stage),
   // so this is a no-op there; it is what covers apk_sim_regrid / apk_sim_check_refinement between cycles.
-  // (AMR_GHOSTS_SHELL_DIRECT: the shell without the zones behind same-level same-rank faces -- the tag kernel reads those
+  // (AMR_XCHG_SHELL_DIRECT: the shell without the zones behind same-level same-rank faces -- the tag kernel reads those
   // cells from the neighbours' interiors through the face table, as the stages do)
   // (amr_prim_free_cycle: ... and stores of the primitives only what the criterion reads, amr_tag_vars_stored; between
   // cycles, stale primitives are regenerated first)
-  if (s->amr_ghost_state == AMR_GHOSTS_FACES || (s->prim_stale && !s->amr_tag_vars_stored)) SIM_TRY(s, sync_ghosts(s));
+  if (AMR_FORM_FAMILY[s->amr_ghost_state] == AMR_FAMILY_FACES || (s->prim_stale && !s->amr_tag_vars_stored)) SIM_TRY(s, sync_ghosts(s));
   SIM_TRY(s, refinement_criterion(s, &req->criterion, &req->p0, &req->p1));
-  const int *table = s->amr_ghost_state == AMR_GHOSTS_SHELL_DIRECT ? s->d_face_nbr : nullptr;
+  const int *table = s->amr_ghost_state == AMR_XCHG_SHELL_DIRECT ? s->d_face_nbr : nullptr;
   SIM_TRY(s, apk_tag_blocks_begin_skip(s->ctx, s->mu0(), req->criterion, table, &req->pending, s->stream));
   return APK_OK;
 }

@@ -351,7 +351,7 @@ int sync_ghosts(apk_sim *s) {
     return materialize_prim(s);
   }
   if (s->amr) {
-    if (s->amr_ghost_state == AMR_GHOSTS_COMPLETE) return materialize_prim(s);  // (amr_prim_free_cycle may have left them stale)
+    if (s->amr_ghost_state == AMR_XCHG_FULL) return materialize_prim(s);  // (amr_prim_free_cycle may have left them stale)
     // the stage loop left the ghost zones behind edges and corners alone (or filled all of them a few layers deep):
     // complete exchange + ConsToPrim
     SIM_TRY(s, amr_exchange(s, s->cur, AMR_XCHG_FULL));

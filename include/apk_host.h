@@ -572,7 +572,7 @@ long long apk_sim_message_generation(const apk_sim *sim);
  * the copies of 40 without those between same-rank blocks of one level (the stages read these
  * neighbours through apk_stage_args.face_neighbor), 44..46 / 47..49 fill copies, packs, unpacks /
  * block boundaries of the exchange that fills every ghost zone two layers deep only (before a
- * refinement check) */
+ * refinement check), 50 the copies of 44 without those between same-rank blocks of one level */
 int apk_sim_plan_size(const apk_sim *sim, int phase);
 /* region r of a phase, with src/dst expressed as (kind, block, element offset):
  * kind 0 = local block cons, 1 = send buffer of peer `block`, 2 = recv buffer of peer `block`,

@@ -162,13 +162,15 @@ def exchange_on_ranks(ems):
 
 def stage_loop_exchange_on_ranks(ems, mode):
     """the exchanges of the stage loop (sim_amr.cpp amr_exchange): mode "faces" = without the boxes behind edges and
-    corners, "direct" = nor the copies between same-rank blocks of one level, "shell" = every ghost zone two layers deep"""
-    tag = "shell" if mode == "shell" else "faces"
+    corners, "direct" = nor the copies between same-rank blocks of one level, "shell" = every ghost zone two layers deep,
+    "shell_direct" = the shell without the copies between same-rank blocks of one level"""
+    tag = "shell" if mode in ("shell", "shell_direct") else "faces"
     for e in ems:
         e.use_messages("halo_" + tag)
         e._ops("my_restrict_own")
         e._copy("my_fill_pack_" + tag)
-        e._copy({"faces": "my_fill_faces", "direct": "my_fill_direct", "shell": "my_fill_shell"}[mode])
+        e._copy({"faces": "my_fill_faces", "direct": "my_fill_direct", "shell": "my_fill_shell",
+                 "shell_direct": "my_fill_shell_direct"}[mode])
     _wire(ems)
     for e in ems:
         e._copy("my_fill_unpack_" + tag)
@@ -176,7 +178,7 @@ def stage_loop_exchange_on_ranks(ems, mode):
             e._copy("my_coarse_bc%d" % d)
         e._ops("my_prolongate_" + tag)
         for d in (1, 2, 3):
-            e._copy(("my_bc_shell%d" if mode == "shell" else "my_bc%d") % d)
+            e._copy(("my_bc_shell%d" if tag == "shell" else "my_bc%d") % d)
 
 
 def flux_correction_on_ranks(ems):

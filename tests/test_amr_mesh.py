@@ -253,12 +253,14 @@ SMR2_NG4 = [o for o in SMR2] + ["parthenon/mesh/nghost=4", "hydro/reconstruction
 @pytest.mark.parametrize("bc", ["periodic", "reflecting"])
 @pytest.mark.parametrize("ov", [SMR3_NG4, SMR2_NG4], ids=["3d", "2d"])
 def test_stage_loop_exchanges_fill_what_they_promise(oracle, ov, bc, nranks):
-    """The three cheaper exchanges of the refined-mesh stage loop against the complete one on the same random state
+    """The four cheaper exchanges of the refined-mesh stage loop against the complete one on the same random state
     (four ghost layers, three / four levels, blocks over 1 and 3 ranks).  Faces only: every ghost cell straight behind a
     face as in the complete exchange, nothing else written.  Direct: the same, minus exactly the zones behind faces shared
     with a same-rank block of the same level.  Shell: every ghost cell at most two layers outside the interior --
     edges and corners included -- as in the complete exchange, nothing deeper written (on the periodic mesh; physical
-    boundaries copy whole transverse extents)."""
+    boundaries copy whole transverse extents).  Shell-direct: the shell, minus the cells straight behind faces shared with a
+    same-rank block of the same level; on the reflecting mesh its cells behind edges and corners are compared with the
+    shell's result put through the block boundaries again, because those boundaries mirror the cells left out."""
     from amr_emulator import stage_loop_exchange_on_ranks
     views = [_view(ov + _bc(bc), rank=r, nranks=nranks) for r in range(nranks)]
     info = views[0].refresh_info()
@@ -285,36 +287,56 @@ def test_stage_loop_exchanges_fill_what_they_promise(oracle, ov, bc, nranks):
     # the same-level same-rank neighbours, from the forest
     where = [{(v.block_level(lb), v.block_gid(lb)[1]): lb for lb in range(e.nb)} for v, e in zip(views, start)]
     nroot = [info.nx[d] // mb[d] for d in range(3)]
-    for mode in ("faces", "direct", "shell"):
-        ems = fresh()
+    done = {}
+    for mode in ("faces", "direct", "shell", "shell_direct"):
+        ems = done[mode] = fresh()
         stage_loop_exchange_on_ranks(ems, mode)
-        skipped = 0
+        skipped, left_out = 0, {}
         for r, (v, e) in enumerate(zip(views, ems)):
             for lb in range(e.nb):
-                if mode == "shell":
+                if mode in ("shell", "shell_direct"):
                     filled = (nghost > 0) & (np.maximum(np.maximum(depth[0], depth[1]), depth[2]) <= 2)
                 else:
                     filled = nghost == 1
-                    if mode == "direct":
-                        lev, loc = v.block_level(lb), v.block_gid(lb)[1]
-                        for f in range(6):
-                            if not act[f // 2]:
-                                continue
-                            nloc = list(loc)
-                            nloc[f // 2] += 1 if f % 2 else -1
-                            n = nroot[f // 2] << lev
-                            if bc == "periodic":
-                                nloc[f // 2] %= n
-                            if (lev, tuple(nloc)) in where[r]:
-                                filled = filled & ~zone[f]
-                                skipped += 1
+                if mode in ("direct", "shell_direct"):
+                    lev, loc = v.block_level(lb), v.block_gid(lb)[1]
+                    for f in range(6):
+                        if not act[f // 2]:
+                            continue
+                        nloc = list(loc)
+                        nloc[f // 2] += 1 if f % 2 else -1
+                        n = nroot[f // 2] << lev
+                        if bc == "periodic":
+                            nloc[f // 2] %= n
+                        if (lev, tuple(nloc)) in where[r]:
+                            filled = filled & ~(zone[f] & (nghost == 1))
+                            skipped += 1
                 got, want, was = e.cons[lb], ref[r].cons[lb], start[r].cons[lb]
+                if mode == "shell_direct":
+                    left_out[r, lb] = (nghost == 1) & (depth[0] + depth[1] + depth[2] <= 2) & ~filled
+                    if bc != "periodic":
+                        # Physical boundaries copy whole transverse extents, the rows left out included: behind edges
+                        # and corners they write what the complete exchange does not (which is why the driver runs this
+                        # form on periodic meshes only).  Measured: 3d 10560 of 138496 / 8608 of 156416 such cells on
+                        # 1 / 3 ranks, 2d 160 of 2496 / 136 of 3072, none of them straight behind a face -- those are
+                        # compared here, the others cell for cell below.
+                        filled = filled & (nghost == 1)
                 assert np.array_equal(got[:, filled], want[:, filled]), (mode, r, lb)
                 untouched = (nghost > 0) & ~filled
                 if bc == "periodic":  # (physical boundaries copy whole transverse extents, stale rows included)
                     assert np.array_equal(got[:, untouched], was[:, untouched]), (mode, r, lb)
                 assert np.array_equal(got[:, nghost == 0], was[:, nghost == 0])
-        assert mode != "direct" or skipped > 0
+        assert mode not in ("direct", "shell_direct") or skipped > 0
+        if mode == "shell_direct":
+            # every cell, on every mesh: the shell's result (compared with the complete exchange above) with the cells left
+            # out as they were at the start and the block boundaries, which mirror those cells too, applied once more
+            for r, (e, sh) in enumerate(zip(ems, done["shell"])):
+                for lb in range(e.nb):
+                    sh.cons[lb][:, left_out[r, lb]] = start[r].cons[lb][:, left_out[r, lb]]
+                for d in (1, 2, 3):
+                    sh._copy("my_bc_shell%d" % d)
+                for lb in range(e.nb):
+                    assert np.array_equal(e.cons[lb], sh.cons[lb]), (mode, r, lb)
     if nranks > 1:  # the shallow exchange sends less
         full = sum(sc for v in views for _, sc, _ in v.messages("halo"))
         faces = sum(sc for v in views for _, sc, _ in v.messages("halo_faces"))
