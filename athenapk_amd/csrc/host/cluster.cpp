@@ -11,6 +11,7 @@
 #include <limits>
 
 #include "cluster.hpp"
+#include "cluster_sources.hpp"
 #include "sim_internal.hpp"
 
 namespace apk {
@@ -47,6 +48,9 @@ const char *kAgn = "problem/cluster/agn_feedback";
 const char *kTower = "problem/cluster/magnetic_tower";
 const char *kJet = "problem/cluster/precessing_jet";
 const char *kTrig = "problem/cluster/agn_triggering";
+const char *kSnia = "problem/cluster/snia_feedback";
+const char *kStellar = "problem/cluster/stellar_feedback";
+const char *kClips = "problem/cluster/clips";
 
 [[noreturn]] void refuse(const std::string &key, const std::string &why) {
   throw std::runtime_error("problem_id = cluster: " + key + " " + why);
@@ -55,25 +59,12 @@ const char *kTrig = "problem/cluster/agn_triggering";
 // what the cluster generator would do and this path does not: refused, never ignored
 void refuse_unbuilt(apk_sim *s) {
   ParameterInput &pin = s->pin;
-  const double inf = std::numeric_limits<double>::infinity();
   if (pin.GetOrAddString("parthenon/mesh", "refinement", "none") != "none")
     refuse("parthenon/mesh/refinement", "must be none: the cluster problem runs on uniform meshes only (static refinement included)");
   if (s->mesh.nx[2] == 1) refuse("parthenon/mesh/nx3", "= 1: the cluster problem is three-dimensional");
   if (s->mesh.nx[1] == 1) refuse("parthenon/mesh/nx2", "= 1: the cluster problem is three-dimensional");
   if (pin.GetOrAddBoolean(kAgn, "enable_tracer", false))
     refuse("problem/cluster/agn_feedback/enable_tracer", "must be false: the AGN passive-scalar tag is not implemented");
-  if (pin.DoesBlockExist("problem/cluster/stellar_feedback"))
-    refuse("problem/cluster/stellar_feedback", "is not implemented: remove the block");
-  // (the reference's default is ENABLED: the deck has to say that it runs without)
-  if (!pin.GetOrAddBoolean("problem/cluster/snia_feedback", "disabled", false))
-    refuse("problem/cluster/snia_feedback/disabled", "must be true: SNIa feedback is not implemented, and the reference enables it by default");
-  const struct {
-    const char *key;
-    double def;
-  } clips[] = {{"clip_r", -1.0}, {"dfloor", -1.0}, {"vceil", inf}, {"vAceil", inf}, {"Tceil", inf}};
-  for (const auto &c : clips)
-    if (pin.GetOrAddReal("problem/cluster/clips", c.key, c.def) != c.def)
-      refuse(std::string("problem/cluster/clips/") + c.key, "must keep its default: the cluster clips are not implemented");
   if (pin.GetOrAddReal("problem/cluster/init_perturb", "sigma_v", 0.0) != 0.0)
     refuse("problem/cluster/init_perturb/sigma_v", "must be 0: initial velocity perturbations are not implemented");
   if (pin.GetOrAddReal("problem/cluster/init_perturb", "sigma_b", 0.0) != 0.0)
@@ -173,6 +164,81 @@ void triggering_initialize(apk_sim *s) {
            "input file.");
   if (s->pkg.diffint == APK_DIFFINT_RKL2) refuse(mode_key, "other than NONE is not supported with diffusion/integrator = rkl2");
   triggering_active_list(s);
+}
+
+// the interior index box, in the block's extended index space, of the cells of every local block that can lie within
+// `radius` of the origin: the active list of the split sources (include/apk_amd.h: apk_trig_box)
+void split_active_list(apk_sim *s, double radius) {
+  const Mesh &m = s->mesh;
+  s->split_boxes.clear();
+  s->split_box_cells = s->split_max_box_cells = 0;
+  const int first[3] = {m.is, m.js, m.ks}, nint[3] = {m.ie - m.is + 1, m.je - m.js + 1, m.ke - m.ks + 1};
+  for (int lb = 0; lb < (int)m.local_gids.size(); ++lb) {
+    double x0[3];
+    block_origin(s, lb, x0);
+    apk_trig_box box{};
+    box.block = lb;
+    long long cells = 1;
+    for (int d = 0; d < 3; ++d) {
+      std::vector<double> x((size_t)nint[d]);
+      for (int i = 0; i < nint[d]; ++i) x[(size_t)i] = xc(s, x0, d, first[d] + i);
+      split_index_range(x.data(), nint[d], first[d], radius, &box.lo[d], &box.hi[d]);
+      cells *= std::max(box.hi[d] - box.lo[d], 0);
+    }
+    if (cells == 0) continue;
+    s->split_boxes.push_back(box);
+    s->split_box_cells += cells;
+    s->split_max_box_cells = std::max(s->split_max_box_cells, cells);
+  }
+}
+
+// SNIAFeedback, StellarFeedback and the clips as the reference reads them (snia_feedback.cpp:31-48,
+// stellar_feedback.cpp:32-65, cluster.cpp:250-277); the derivations and refusals are host/cluster_sources_model.cpp's
+void sources_initialize(apk_sim *s) {
+  ParameterInput &pin = s->pin;
+  const UnitsState &u = s->pkg.units;
+  const double inf = std::numeric_limits<double>::infinity();
+  ClusterSourcesInput in;
+  in.power_per_bcg_mass = pin.GetOrAddReal(kSnia, "power_per_bcg_mass", 0.0);
+  in.mass_rate_per_bcg_mass = pin.GetOrAddReal(kSnia, "mass_rate_per_bcg_mass", 0.0);
+  in.snia_disabled = pin.GetOrAddBoolean(kSnia, "disabled", false);
+  in.stellar_radius = pin.GetOrAddReal(kStellar, "stellar_radius", 0.0);
+  in.exclusion_radius = pin.GetOrAddReal(kStellar, "exclusion_radius", 0.0);
+  in.efficiency = pin.GetOrAddReal(kStellar, "efficiency", 0.0);
+  in.number_density_threshold = pin.GetOrAddReal(kStellar, "number_density_threshold", 0.0);
+  in.temperature_threshold = pin.GetOrAddReal(kStellar, "temperature_threshold", 0.0);
+  in.accretion_radius = pin.GetOrAddReal(kTrig, "accretion_radius", 0);
+  in.clip_r = pin.GetOrAddReal(kClips, "clip_r", -1.0);
+  in.dfloor = pin.GetOrAddReal(kClips, "dfloor", -1.0);
+  in.vceil = pin.GetOrAddReal(kClips, "vceil", inf);
+  in.vAceil = pin.GetOrAddReal(kClips, "vAceil", inf);
+  in.Tceil = pin.GetOrAddReal(kClips, "Tceil", inf);
+  in.which_bcg_g = s->cluster.which_bcg_g, in.m_bcg_s = s->cluster.m_bcg_s, in.r_bcg_s = s->cluster.r_bcg_s;
+  in.mhd = s->pkg.fluid == APK_FLUID_GLMMHD, in.rkl2 = s->pkg.diffint == APK_DIFFINT_RKL2, in.has_composition = u.has_composition;
+  in.gamma = s->pkg.eos.gamma;
+  if (u.has_composition) in.mu = u.mu, in.mh = u.mh(), in.mbar_over_kb = u.mbar_over_kb, in.speed_of_light = u.speed_of_light();
+  s->snia = apk_snia_cfg{}, s->stellar = apk_stellar_cfg{}, s->clips = apk_clips_cfg{};
+  for (double &t : s->split_totals) t = 0.0;
+  apk_cluster_source_options &o = s->csrc;
+  o = cluster_source_options(in);  // (throws what is refused)
+  if (o.snia_active) {
+    s->snia.power_per_bcg_mass = o.power_per_bcg_mass, s->snia.mass_rate_per_bcg_mass = o.mass_rate_per_bcg_mass;
+    s->snia.rho_const_bcg = o.rho_const_bcg, s->snia.r_bcg_s = s->cluster.r_bcg_s, s->snia.smoothing_r = s->cluster.g_smoothing_radius;
+  }
+  if (o.stellar_active) {
+    s->stellar.stellar_radius = o.stellar_radius, s->stellar.exclusion_radius = o.exclusion_radius;
+    s->stellar.number_density_threshold = o.number_density_threshold, s->stellar.temperature_threshold = o.temperature_threshold;
+    s->stellar.mbar = o.mbar, s->stellar.mbar_over_kb = o.mbar_over_kb, s->stellar.mass_to_energy = o.mass_to_energy;
+  }
+  if (o.clips_active)
+    s->clips.clip_r = o.clip_r, s->clips.dfloor = o.dfloor, s->clips.vceil = o.vceil, s->clips.vAceil = o.vAceil, s->clips.eceil = o.eceil;
+  s->pkg.snia_srcterm = o.snia_active != 0;
+  s->pkg.cluster_split_srcterm = o.stellar_active || o.clips_active;
+  s->split_boxes.clear();
+  s->split_box_cells = s->split_max_box_cells = 0;
+  if (s->pkg.cluster_split_srcterm)
+    split_active_list(s, std::max(o.stellar_active ? o.stellar_radius : 0.0, o.clips_active ? o.clip_r : 0.0));
+  o.active_blocks = (int)s->split_boxes.size(), o.active_box_cells = s->split_box_cells;
 }
 
 // AGNFeedback, MagneticTower and JetCoordsFactory as the reference's constructors read them (agn_feedback.cpp:34-185,
@@ -361,6 +427,7 @@ void cluster_initialize(apk_sim *s) {
   s->pkg.gravity_srcterm = o.gravity_srcterm != 0;
   triggering_initialize(s);
   feedback_initialize(s, agn_block, tower_block);
+  sources_initialize(s);
 
   // ACCEPTEntropyProfile (entropy_profiles.hpp:25-34)
   o.k_0 = pin.GetOrAddReal("problem/cluster/entropy_profile", "k_0", 20 * u.kev() * u.cm() * u.cm());
@@ -473,7 +540,7 @@ void cluster_pgen_block(apk_sim *s, int lb, std::vector<double> &u) {
 }
 
 bool cluster_needs_block_origins(const apk_sim *s) {
-  return s->pkg.gravity_srcterm || s->pkg.agn_triggering ||
+  return s->pkg.gravity_srcterm || s->pkg.agn_triggering || s->pkg.snia_srcterm || s->pkg.cluster_split_srcterm ||
          (s->cluster.enabled && (s->agn_opt.configured || s->tower.potential != APK_TOWER_UNDEFINED));
 }
 
@@ -545,6 +612,33 @@ int cluster_feedback_sources(apk_sim *s, double beta_dt) {
     return fail(s, APK_ERR_INVALID, e.what());
   }
   return APK_OK;
+}
+
+// SNIAFeedback::FeedbackSrcTerm, the third term of ClusterUnsplitSrcTerm (cluster.cpp:82-83)
+int cluster_snia_source(apk_sim *s, double beta_dt) {
+  return apk_snia_feedback_src(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, &s->snia, s->d_block_xmin, beta_dt, s->stream);
+}
+
+// ClusterSplitSrcTerm (cluster.cpp:85-93) over this rank's active list, the five sums over blocks and ranks
+// (sum_blocks_in_global_order) added to the running totals; out[5]: this call's sums (may be null)
+static int split_sources(apk_sim *s, bool stellar, bool clips, double *out) {
+  const bool listed = !s->split_boxes.empty();  // (a rank with no block in the list launches nothing and contributes zeros)
+  if (listed)
+    SIM_TRY(s, apk_cluster_split_src(s->ctx, s->mu0(), s->pkg.fluid, &s->pkg.eos, stellar ? &s->stellar : nullptr, clips ? &s->clips : nullptr,
+                                     s->d_split_boxes, (int)s->split_boxes.size(), s->split_max_box_cells, s->d_block_xmin,
+                                     s->d_split_sums, s->stream));
+  double sum[8];
+  SIM_TRY(s, sum_blocks_in_global_order(s, listed ? s->d_split_sums : nullptr, 8, sum));
+  for (int q = 0; q < 5; ++q) {
+    s->split_totals[q] += sum[q];
+    if (out) out[q] = sum[q];
+  }
+  return APK_OK;
+}
+
+int cluster_split_sources(apk_sim *s, double dt) {
+  (void)dt;  // (the reference passes it; neither stellar feedback nor the clips reads it)
+  return split_sources(s, s->csrc.stellar_active != 0, s->csrc.clips_active != 0, nullptr);
 }
 
 // AGN triggering of one cycle (hydro_driver.cpp:360-394): AGNTriggeringResetTriggering, ReduceTriggering over this rank's
@@ -638,6 +732,11 @@ int cluster_device_setup(apk_sim *s) {
     SIM_TRY(s, dev_alloc(s, "trig_boxes", s->trig_boxes.size() * sizeof(apk_trig_box), reinterpret_cast<double **>(&s->d_trig_boxes)));
     SIM_HIP(s, hipMemcpy(s->d_trig_boxes, s->trig_boxes.data(), s->trig_boxes.size() * sizeof(apk_trig_box), hipMemcpyHostToDevice));
     SIM_TRY(s, dev_alloc(s, "trig_sums", sizeof(double) * 4 * (size_t)std::max(nlb, 1), &s->d_trig_sums));
+  }
+  if (s->pkg.cluster_split_srcterm && !s->split_boxes.empty()) {
+    SIM_TRY(s, dev_alloc(s, "split_boxes", s->split_boxes.size() * sizeof(apk_trig_box), reinterpret_cast<double **>(&s->d_split_boxes)));
+    SIM_HIP(s, hipMemcpy(s->d_split_boxes, s->split_boxes.data(), s->split_boxes.size() * sizeof(apk_trig_box), hipMemcpyHostToDevice));
+    SIM_TRY(s, dev_alloc(s, "split_sums", sizeof(double) * 8 * (size_t)std::max(nlb, 1), &s->d_split_sums));
   }
   return APK_OK;
 }
@@ -843,6 +942,51 @@ int apk_sim_agn_triggering_active_list(const apk_sim *s, int *out, int n, int *s
     out[7 * e] = b.block;
     for (int d = 0; d < 3; ++d) out[7 * e + 1 + d] = b.lo[d], out[7 * e + 4 + d] = b.hi[d];
   }
+  return APK_OK;
+}
+
+int apk_sim_cluster_source_options(const apk_sim *s, apk_cluster_source_options *o) {
+  if (!s || !o || !s->cluster.enabled) return APK_ERR_INVALID;
+  *o = s->csrc;
+  o->flux_path_sources = s->pkg.flux_path_sources() ? 1 : 0;
+  return APK_OK;
+}
+
+int apk_sim_cluster_split_active_list(const apk_sim *s, int *out, int n, int *size) {
+  if (!s || !size || !s->cluster.enabled) return APK_ERR_INVALID;
+  *size = (int)s->split_boxes.size();
+  for (int e = 0; out && e < n && e < *size; ++e) {
+    const apk_trig_box &b = s->split_boxes[(size_t)e];
+    out[7 * e] = b.block;
+    for (int d = 0; d < 3; ++d) out[7 * e + 1 + d] = b.lo[d], out[7 * e + 4 + d] = b.hi[d];
+  }
+  return APK_OK;
+}
+
+int apk_sim_snia_feedback_src(apk_sim *s, double beta_dt) {
+  if (!s || s->host_only) return APK_ERR_INVALID;
+  if (!s->cluster.enabled || !s->pkg.snia_srcterm || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "snia_feedback_src needs problem_id = cluster with problem/cluster/snia_feedback/disabled = false");
+  SIM_TRY(s, sync_ghosts(s));  // (materialises the stored primitives when the cycle kept them out of memory)
+  SIM_TRY(s, cluster_snia_source(s, beta_dt));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+int apk_sim_cluster_split_src(apk_sim *s, double dt, int stellar, int clips, double out[5]) {
+  if (!s || s->host_only || !out) return APK_ERR_INVALID;
+  (void)dt;
+  if (!s->cluster.enabled || !s->pkg.cluster_split_srcterm || !s->d_block_xmin)
+    return fail(s, APK_ERR_INVALID, "cluster_split_src needs problem_id = cluster with problem/cluster/stellar_feedback or problem/cluster/clips");
+  SIM_TRY(s, sync_ghosts(s));
+  SIM_TRY(s, split_sources(s, stellar && s->csrc.stellar_active, clips && s->csrc.clips_active, out));
+  SIM_HIP(s, hipStreamSynchronize(hs(s)));
+  return APK_OK;
+}
+
+int apk_sim_cluster_source_totals(const apk_sim *s, double out[5]) {
+  if (!s || !out || !s->cluster.enabled) return APK_ERR_INVALID;
+  for (int q = 0; q < 5; ++q) out[q] = s->split_totals[q];
   return APK_OK;
 }
 

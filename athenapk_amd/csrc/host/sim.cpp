@@ -489,9 +489,10 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
   const bool cool = s->pkg.cooling;
   const double h = s->pkg.cool_table_hash;
   // With rkl2 one more, last: the diffusive limit itself, which sizes the next cycle's super-time-steps.
-  // (the AGN feedback source's own pressure check shares the pressure slot: -2 below -1, so that every rank sees which)
+  // (the AGN feedback source's own pressure check and stellar feedback's energy check share the pressure slot: -3 and -2
+  // below -1, so that every rank sees which; the reference meets the AGN one first)
   double mins[8] = {dt, e.dt_hyp_local, (e.flags & APK_FLAG_NEG_DENSITY) ? -1.0 : 0.0,
-                    (e.flags & APK_FLAG_AGN_NEG_PRESSURE) ? -2.0 : ((e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0),
+                    (e.flags & APK_FLAG_AGN_NEG_PRESSURE) ? -3.0 : ((e.flags & APK_FLAG_STELLAR_ENERGY) ? -2.0 : ((e.flags & APK_FLAG_NEG_PRESSURE) ? -1.0 : 0.0)),
                     (e.flags & (APK_FLAG_COOL_MAX_ITER | APK_FLAG_COOL_TABLE)) ? -1.0 : 0.0, h, -h, e.dt_diff_local};
   if (s->have_comm && s->nranks > 1) {
     if (s->comm.allreduce_min(s->comm.user, mins, sts ? 8 : (cool ? 7 : 4)) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_min failed");
@@ -504,7 +505,9 @@ int estimate_timestep_commit(apk_sim *s, const DtEstimate &e, double *dt_out) {
     return fail(s, APK_ERR_INVALID, "cooling failed on another rank");
   }
   // agn_feedback.cpp:407-408: the reference aborts inside the source's loop, before any later ConsToPrim can complain
-  if (mins[3] <= -2.0) return fail(s, APK_ERR_INVALID, "Kinetic injection leads to negative pressure");
+  if (mins[3] <= -3.0) return fail(s, APK_ERR_INVALID, "Kinetic injection leads to negative pressure");
+  // stellar_feedback.cpp:163-165
+  if (mins[3] <= -2.0) return fail(s, APK_ERR_INVALID, "Sanity check failed. Added thermal energy should be positive.");
   if (mins[2] < 0.0)
     return fail(s, APK_ERR_INVALID, "Got negative density. Consider enabling first-order flux correction or setting a reasonble density floor.");
   if (mins[3] < 0.0)
@@ -934,6 +937,8 @@ void apk_sim_destroy(apk_sim *s) {
     dev_free(s, s->d_tower_contribs);
     dev_free(s, reinterpret_cast<double *>(s->d_trig_boxes));
     dev_free(s, s->d_trig_sums);
+    dev_free(s, reinterpret_cast<double *>(s->d_split_boxes));
+    dev_free(s, s->d_split_sums);
     dev_free(s, s->d_cons2[0]);
     dev_free(s, s->d_prim2[0]);
     dev_free(s, s->d_prim2[1]);
@@ -1036,6 +1041,7 @@ int apk_sim_initialize(apk_sim *s) {
   s->pkg.mindx = kHuge;
   s->pkg.dt_hyp = kHuge;
   if (s->cluster.enabled) cluster_triggering_reset(s);
+  for (double &t : s->split_totals) t = 0.0;
   SIM_TRY(s, exchange_ghosts(s));
   SIM_TRY(s, fill_derived(s));
   // adaptive meshes: tag the initial condition, refine, and evaluate the problem generator again on
@@ -1455,6 +1461,8 @@ int apk_sim_history_labels(const apk_sim *s, char *buf, size_t len) {
   // (agn_feedback.cpp:162-177 adds the column whenever feedback is enabled; here only runs with triggering have it, so
   // that the others keep their columns)
   if (s->pkg.agn_triggering) l += " agn_feedback_power";
+  // (cluster.cpp:292-313 adds these to every cluster run; here only runs with stellar feedback or clips have them)
+  if (s->pkg.cluster_split_srcterm) l += " stellar_mass added_dfloor_mass removed_eceil_energy removed_vceil_energy added_vAceil_mass";
   std::snprintf(buf, len, "%s", l.c_str());
   return APK_OK;
 }
@@ -1493,19 +1501,23 @@ int apk_sim_write_history(apk_sim *s, const char *path) {
   const bool maxv2 = s->problem_id == "linear_wave_mhd" && s->lwm.dump_max_v2;
   double mv2 = 0.0;
   if (maxv2 && (rc = max_abs_v2(s, &mv2)) != APK_OK) return rc;
+  // the running totals of the split cluster sources: reported, then reset on every rank (cluster.cpp:300-313)
+  double totals[5];
+  for (int q = 0; q < 5; ++q) totals[q] = s->split_totals[q], s->split_totals[q] = 0.0;
   if (s->rank != 0) return APK_OK;
   std::vector<double> row(h, h + (mhd ? 8 : 6));
   if (s->fmft) row.insert(row.end(), t3, t3 + (mhd ? 3 : 1));
   if (floop) row.push_back(urdb);
   if (maxv2) row.push_back(mv2);
   if (s->pkg.agn_triggering) row.push_back(s->agn_opt.configured ? s->agn.power() : 0.0);
+  if (s->pkg.cluster_split_srcterm) row.insert(row.end(), totals, totals + 5);
   FILE *f = std::fopen(path, "r");
   const bool fresh = (f == nullptr);
   if (f) std::fclose(f);
   f = std::fopen(path, "a");
   if (!f) return fail(s, APK_ERR_INVALID, std::string("history file could not be opened: ") + path);
   if (fresh) {
-    char labels[256];
+    char labels[512];
     apk_sim_history_labels(s, labels, sizeof(labels));
     int col = 1;
     std::fprintf(f, "#  History data\n");

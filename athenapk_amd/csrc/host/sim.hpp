@@ -94,7 +94,14 @@ struct HydroPackage {
   // problem/cluster/agn_triggering/triggering_mode != NONE: the cycle's reduction and removal update cons and prim in
   // place before stage 1 (hydro_driver.cpp:360-394)
   bool agn_triggering = false;
-  bool flux_path_sources() const { return diffusion_configured() || cooling || gravity_srcterm || feedback_srcterm || agn_triggering; }
+  // problem/cluster/snia_feedback with a rate (the third term of ClusterUnsplitSrcTerm, cluster.cpp:82-83), and
+  // problem/cluster/stellar_feedback or problem/cluster/clips (ClusterSplitSrcTerm, cluster.cpp:85-93: once per cycle,
+  // after the last stage's unsplit sources)
+  bool snia_srcterm = false;
+  bool cluster_split_srcterm = false;
+  bool flux_path_sources() const {
+    return diffusion_configured() || cooling || gravity_srcterm || feedback_srcterm || agn_triggering || snia_srcterm || cluster_split_srcterm;
+  }
 };
 
 struct LinearWaveState {  // globals of src/pgen/linear_wave.cpp
@@ -209,6 +216,17 @@ struct apk_sim {
   long long trig_box_cells = 0, trig_max_box_cells = 0;
   apk_trig_box *d_trig_boxes = nullptr;
   double *d_trig_sums = nullptr;  // [nblocks][4]
+  // SNIa feedback, stellar feedback and the clips (host/cluster.cpp): the options as parsed and derived, the split
+  // sources' own active list with its device copy, and the five running totals since the last history row
+  apk_cluster_source_options csrc{};
+  apk_snia_cfg snia{};
+  apk_stellar_cfg stellar{};
+  apk_clips_cfg clips{};
+  std::vector<apk_trig_box> split_boxes;
+  long long split_box_cells = 0, split_max_box_cells = 0;
+  apk_trig_box *d_split_boxes = nullptr;
+  double *d_split_sums = nullptr;  // [nblocks][8]
+  double split_totals[5] = {0, 0, 0, 0, 0};
   bool host_only = false;
   bool fused = true;
   int rank = 0, nranks = 1;

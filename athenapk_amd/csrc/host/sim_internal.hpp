@@ -59,6 +59,8 @@ int cluster_tower_contribs(apk_sim *s, double time, double out[2]);  // the towe
 int cluster_agn_triggering(apk_sim *s, double dt);  // AGN triggering of one cycle: reduce, sum over ranks, remove
 void cluster_triggering_reset(apk_sim *s);          // the reduced quantities back to zero (initialisation)
 int cluster_feedback_sources(apk_sim *s, double beta_dt);  // AGN feedback, tower power, tower fixed rate: one stage
+int cluster_snia_source(apk_sim *s, double beta_dt);       // SNIa feedback: one stage
+int cluster_split_sources(apk_sim *s, double dt);          // stellar feedback and the clips: once per cycle, sums into the totals
 int cluster_write_test_profile(apk_sim *s, const std::string &path);  // test_he_sphere.dat
 int dev_alloc(apk_sim *s, const char *tag, size_t bytes, double **out);
 void dev_free(apk_sim *s, double *p);

@@ -808,6 +808,11 @@ static int run_flux_array_stage(apk_sim *s, const Stage &st) {
     SIM_TRY(s, apk_gravity_src(s->ctx, s->mu0(), &s->cluster.gravity, s->d_block_xmin, st.beta_dt, s->stream));
   // ... then AGN feedback with the tower's power-scaled field, then the tower's fixed field rate (cluster.cpp:76-80)
   if (pkg.feedback_srcterm) SIM_TRY(s, cluster_feedback_sources(s, st.beta_dt));
+  // ... then SNIa feedback (cluster.cpp:82-83)
+  if (pkg.snia_srcterm) SIM_TRY(s, cluster_snia_source(s, st.beta_dt));
+  // the first-order split sources after the unsplit ones of the last stage, with the full dt and the primitives the pack
+  // then holds (hydro_driver.cpp:548-560): stellar feedback, then the clips (cluster.cpp:85-93)
+  if (st.last && pkg.cluster_split_srcterm) SIM_TRY(s, cluster_split_sources(s, s->dt));
   return APK_OK;
 }
 

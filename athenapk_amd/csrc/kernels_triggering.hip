@@ -9,7 +9,7 @@
 // the host hands over an active list (apk_trig_box: a block and an index box in its extended index space, ghost cells
 // included, that holds every cell whose centre can lie inside the sphere) and the grid is (P, entries of the list).
 // Each workgroup of 256 takes a fixed contiguous share of its box's cells, i fastest so that loads coalesce along a row
-// of the box; a box is clipped to the block's arrays before it is used.  The cell centre is cell_centre of
+// of the box; a box is clipped to the block's arrays before it is used (active_box.hpp, shared with kernels_cluster_sources.hip).  The cell centre is cell_centre of
 // cell_centre.hpp with the index counted from the first interior cell (negative in the lower ghost zone), the number the
 // host's generators and a neighbouring block form for that cell; r2 = x * x + y * y + z * z and the test is the strict
 // r2 < R^2.
@@ -42,6 +42,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "active_box.hpp"
 #include "apk_internal.hpp"
 #include "block_sum.hpp"
 #include "cell_centre.hpp"
@@ -50,76 +51,6 @@
 namespace apk {
 
 namespace {
-
-// the box of entry `e`, clipped to the block's arrays, and this workgroup's share [first, last) of its cells
-struct BoxShare {
-  int b, lo[3], n[3];
-  int64_t first, last;
-};
-APK_DEV bool box_share(const PackView &pv, const apk_trig_box *__restrict__ boxes, int e, int p, int P, BoxShare &s) {
-  const apk_trig_box bx = boxes[e];
-  s.b = bx.block;
-  if (s.b < 0 || s.b >= pv.nblocks) return false;
-  const int ext[3] = {pv.ni, pv.nj, pv.nk};
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const int lo = bx.lo[d] < 0 ? 0 : bx.lo[d];
-    const int hi = bx.hi[d] > ext[d] ? ext[d] : bx.hi[d];
-    s.lo[d] = lo;
-    s.n[d] = hi > lo ? hi - lo : 0;
-  }
-  block_sum_share((int64_t)s.n[0] * s.n[1] * s.n[2], p, P, s.first, s.last);
-  return true;
-}
-
-// cell q of the share: its extended indices, offset, centre and whether it is an interior cell
-struct TrigCell {
-  int64_t off;
-  double r2;
-  bool interior;
-};
-APK_DEV TrigCell trig_cell(const PackView &pv, const BoxShare &s, const apk_block_desc &bd, const double *__restrict__ block_xmin,
-                           int64_t q) {
-  const int64_t nrow = s.n[0];
-  int ii, jj, kk;
-  box_ijk(q, nrow, nrow * s.n[1], ii, jj, kk);
-  const int i = s.lo[0] + ii, j = s.lo[1] + jj, k = s.lo[2] + kk;
-  double x, y, z;
-  cell_xyz(bd, block_xmin, s.b, pv.nblocks, i - pv.is, j - pv.js, k - pv.ks, x, y, z);
-  TrigCell c;
-  c.off = (int64_t)k * pv.sk + (int64_t)j * pv.sj + i;
-  c.r2 = x * x + y * y + z * z;
-  c.interior = i >= pv.is && i <= pv.ie && j >= pv.js && j <= pv.je && k >= pv.ks && k <= pv.ke;
-  return c;
-}
-
-// AddDensityToConsAtFixedVelTemp (cluster_utils.hpp:40-52) on the stored primitives, then ConsToPrim, for one cell;
-// density_of(rho): the density to add, from the stored density
-template <int FLUID, typename F>
-APK_DEV unsigned add_density_fixed_vel_temp(const apk_eos &eos, const apk_block_desc &bd, int64_t off, int64_t sn, F density_of) {
-  constexpr int NV = nvars<FLUID>();
-  double *__restrict__ up = bd.cons + off;
-  double *__restrict__ wp = bd.prim + off;
-  double u[NV], w[NV], di;
-#pragma unroll
-  for (int n = 0; n < NV; ++n) {
-    u[n] = up[n * sn];
-    w[n] = wp[n * sn];
-  }
-  const double density = density_of(w[IDN]);
-  u[IDN] += density;
-  u[IM1] += density * w[IV1];
-  u[IM2] += density * w[IV2];
-  u[IM3] += density * w[IV3];
-  u[IEN] += density * (0.5 * (sqr(w[IV1]) + sqr(w[IV2]) + sqr(w[IV3])) + 1 / (eos.gamma - 1.0) * w[IPR] / w[IDN]);
-  const unsigned flags = cons_to_prim_cell<FLUID>(eos, u, w, di);
-#pragma unroll
-  for (int n = 0; n < NV; ++n) {
-    up[n * sn] = u[n];
-    wp[n * sn] = w[n];
-  }
-  return flags;
-}
 
 // ReduceBondiTriggeringQuantities (agn_triggering.cpp:234-256): grid (P, entries)
 __global__ void __launch_bounds__(256) trig_reduce_bondi_kernel(PackView pv, double gamma, double accretion_radius,

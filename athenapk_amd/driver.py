@@ -211,6 +211,23 @@ class _ClusterHost:
         self._cluster_check(self.lib.apk_sim_agn_triggering_active_list(self.h, out, size.value, C.byref(size)))
         return [(out[7 * e], tuple(out[7 * e + 1:7 * e + 4]), tuple(out[7 * e + 4:7 * e + 7])) for e in range(size.value)]
 
+    def cluster_source_options(self):
+        """lib.ClusterSourceOptions: <problem/cluster/snia_feedback>, <problem/cluster/stellar_feedback> and
+        <problem/cluster/clips> as parsed, which of the three sources are active, the derived rho_const_bcg, mbar,
+        mass_to_energy and eceil, and the number of active blocks and box cells of the split sources on this rank"""
+        o = L.ClusterSourceOptions()
+        self._cluster_check(self.lib.apk_sim_cluster_source_options(self.h, C.byref(o)))
+        return o
+
+    def cluster_split_active_list(self):
+        """this rank's active list of stellar feedback and the clips: [(local block, (lo_i, lo_j, lo_k), (hi_i, hi_j,
+        hi_k))], interior boxes in the extended index space, hi exclusive"""
+        size = C.c_int(0)
+        self._cluster_check(self.lib.apk_sim_cluster_split_active_list(self.h, None, 0, C.byref(size)))
+        out = (C.c_int * (7 * max(size.value, 1)))()
+        self._cluster_check(self.lib.apk_sim_cluster_split_active_list(self.h, out, size.value, C.byref(size)))
+        return [(out[7 * e], tuple(out[7 * e + 1:7 * e + 4]), tuple(out[7 * e + 4:7 * e + 7])) for e in range(size.value)]
+
     def pgen_block(self, lb):
         """the problem generator's conserved state of local block lb, interior cells: [nvar][nx3][nx2][nx1] of the block"""
         nf = self.info
@@ -800,6 +817,26 @@ class Simulation(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
         mass_to_add): conserved B, E and rho of the interior cells change"""
         self._check(self.lib.apk_sim_magnetic_tower_src(self.h, float(field), float(mass),
                                                         float(self.time if time is None else time)))
+
+    CLUSTER_SOURCE_TOTALS = ("stellar_mass", "added_dfloor_mass", "removed_eceil_energy", "removed_vceil_energy", "added_vAceil_mass")
+
+    def snia_feedback_src(self, beta_dt):
+        """SNIa feedback (apk_snia_feedback_src) once on the current state: conserved state and stored primitives of the
+        interior cells change"""
+        self._check(self.lib.apk_sim_snia_feedback_src(self.h, float(beta_dt)))
+
+    def cluster_split_src(self, dt, stellar=True, clips=True):
+        """stellar feedback and / or the clips (apk_cluster_split_src) once on the current state; returns the five global
+        sums in the order of CLUSTER_SOURCE_TOTALS, which also join the running totals.  A collective"""
+        out = (C.c_double * 5)()
+        self._check(self.lib.apk_sim_cluster_split_src(self.h, float(dt), int(bool(stellar)), int(bool(clips)), out))
+        return np.array(out[:])
+
+    def cluster_source_totals(self):
+        """the five running totals since the last history row, in the order of CLUSTER_SOURCE_TOTALS"""
+        out = (C.c_double * 5)()
+        self._check(self.lib.apk_sim_cluster_source_totals(self.h, out))
+        return np.array(out[:])
 
     def agn_triggering_reduce(self, dt):
         """one reduction of AGN triggering (COLD_GAS: with its removal) on the current state with this dt, summed over

@@ -26,10 +26,11 @@ COOL_INTEGRATOR = {"rk12": 1, "rk45": 2, "townsend": 3}
 APK_FLAG_COOL_MAX_ITER = 4
 APK_FLAG_COOL_TABLE = 8
 APK_FLAG_AGN_NEG_PRESSURE = 16
+APK_FLAG_STELLAR_ENERGY = 32  # stellar feedback's "Added thermal energy should be positive"
 
 TIMING_SLOTS = ("fused_x1", "fused_x2", "fused_x3", "fluxes", "update", "dedner", "cons_to_prim",
                 "min_dt", "copy_regions", "fused_dc_x1", "fused_dc_x2", "fused_dc_x3", "tracers", "tracer_sort", "gravity",
-                "agn_feedback", "tower", "tower_contribs", "triggering")
+                "agn_feedback", "tower", "tower_contribs", "triggering", "cluster_sources")
 
 APK_OK = 0
 APK_RCCL_ID_BYTES = 128
@@ -177,6 +178,33 @@ class AgnTriggeringCfg(C.Structure):
     """apk_agn_triggering_cfg: what apk_agn_triggering_reduce takes by value"""
     _fields_ = ([("mode", C.c_int), ("remove_accreted_mass", C.c_int)] +
                 [(n, C.c_double) for n in ("accretion_radius", "cold_temp_thresh", "cold_t_acc", "mean_molecular_mass_by_kb")])
+
+
+class SniaCfg(C.Structure):
+    """apk_snia_cfg: what apk_snia_feedback_src takes by value"""
+    _fields_ = [(n, C.c_double) for n in ("power_per_bcg_mass", "mass_rate_per_bcg_mass", "rho_const_bcg", "r_bcg_s", "smoothing_r")]
+
+
+class StellarCfg(C.Structure):
+    """apk_stellar_cfg: stellar feedback's numbers as apk_cluster_split_src takes them"""
+    _fields_ = [(n, C.c_double) for n in ("stellar_radius", "exclusion_radius", "number_density_threshold", "temperature_threshold",
+                                          "mbar", "mbar_over_kb", "mass_to_energy")]
+
+
+class ClipsCfg(C.Structure):
+    """apk_clips_cfg: the clips as apk_cluster_split_src takes them (a clip at its disabled value is skipped)"""
+    _fields_ = [(n, C.c_double) for n in ("clip_r", "dfloor", "vceil", "vAceil", "eceil")]
+
+
+class ClusterSourceOptions(C.Structure):
+    """apk_cluster_source_options: <problem/cluster/snia_feedback>, <problem/cluster/stellar_feedback> and
+    <problem/cluster/clips> as parsed and derived, and the size of this rank's active list (include/apk_host.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("snia_active", "stellar_active", "clips_active", "flux_path_sources", "active_blocks")] +
+                [("active_box_cells", C.c_longlong)] +
+                [(n, C.c_double) for n in ("power_per_bcg_mass", "mass_rate_per_bcg_mass", "rho_const_bcg", "stellar_radius",
+                                           "exclusion_radius", "efficiency", "number_density_threshold", "temperature_threshold",
+                                           "mbar", "mbar_over_kb", "mass_to_energy", "clip_r", "dfloor", "vceil", "vAceil", "Tceil",
+                                           "eceil")])
 
 
 class AgnTriggeringOptions(C.Structure):
@@ -431,6 +459,8 @@ def _signatures():
         "apk_magnetic_tower_power_contribs": (i, [vp, vp, C.POINTER(MagneticTowerCfg), C.POINTER(JetCoords), vp, vp, vp]),
         "apk_agn_triggering_reduce": (i, [vp, vp, i, C.POINTER(Eos), C.POINTER(AgnTriggeringCfg), vp, i, C.c_int64, vp, d, vp, vp]),
         "apk_agn_triggering_remove_bondi": (i, [vp, vp, i, C.POINTER(Eos), d, vp, i, C.c_int64, vp, d, d, d, vp]),
+        "apk_snia_feedback_src": (i, [vp, vp, i, C.POINTER(Eos), C.POINTER(SniaCfg), vp, d, vp]),
+        "apk_cluster_split_src": (i, [vp, vp, i, C.POINTER(Eos), C.POINTER(StellarCfg), C.POINTER(ClipsCfg), vp, i, C.c_int64, vp, vp, vp]),
         "apk_first_order_flux_correct": (i, [vp, vp, vp, i, E, d, d, d, d, C.POINTER(ll), vp]),
         "apk_count_unphysical": (i, [vp, vp, i, C.POINTER(ll), vp]),
         "apk_history": (i, [vp, vp, i, c_dp, vp]),
@@ -531,6 +561,11 @@ def _signatures():
         "apk_sim_agn_triggering_timestep": (i, [vp, c_dp, c_dp]),
         "apk_sim_agn_feedback_power_of": (i, [vp, d, c_dp, c_dp]),
         "apk_sim_agn_triggering_active_list": (i, [vp, C.POINTER(C.c_int), i, C.POINTER(C.c_int)]),
+        "apk_sim_cluster_source_options": (i, [vp, C.POINTER(ClusterSourceOptions)]),
+        "apk_sim_cluster_split_active_list": (i, [vp, C.POINTER(C.c_int), i, C.POINTER(C.c_int)]),
+        "apk_sim_snia_feedback_src": (i, [vp, d]),
+        "apk_sim_cluster_split_src": (i, [vp, d, i, i, c_dp]),
+        "apk_sim_cluster_source_totals": (i, [vp, c_dp]),
         "apk_sim_agn_triggering_reduce": (i, [vp, d]),
         "apk_sim_agn_triggering_remove_bondi": (i, [vp, d]),
         "apk_sim_tracers_options": (i, [vp, C.POINTER(TracersOptions)]),

@@ -1021,6 +1021,51 @@ int apk_agn_triggering_remove_bondi(apk_ctx *ctx, const apk_pack *md, int fluid,
                                     const apk_trig_box *boxes, int nboxes, int64_t max_box_cells, const double *block_xmin,
                                     double total_mass, double accretion_rate, double dt, apk_stream_t stream);
 
+/* ---- SNIa feedback, stellar feedback and the clips of the cluster problem (src/pgen/cluster/snia_feedback.cpp,
+ * stellar_feedback.cpp, cluster_clips.cpp, cluster_utils.hpp; csrc/kernels_cluster_sources.hip) ------------------------
+ * SNIAFeedback's numbers and the Hernquist BCG's density (ClusterGravity::rho_from_r with NFW and SMBH off,
+ * cluster_gravity.hpp:203-230).  rho_const_bcg = m_bcg_s * r_bcg_s / (2 pi) for HERNQUIST and 0 for NONE: what the
+ * reference's calc_rho_const_bcg returns.  The reference never calls that function and reads its member uninitialised
+ * (cluster_gravity.hpp:46, 220): this is the evident intent, not the behaviour. */
+typedef struct apk_snia_cfg {
+  double power_per_bcg_mass, mass_rate_per_bcg_mass;
+  double rho_const_bcg, r_bcg_s, smoothing_r;
+} apk_snia_cfg;
+/* Replaces the loop of SNIAFeedback::FeedbackSrcTerm (snia_feedback.cpp:87-118) on the interior cells of every block:
+ *   r = sqrt(x * x + y * y + z * z), r' = max(r, smoothing_r), rho_bcg = rho_const_bcg / (r' * ((r' + a) * (r' + a) * (r' + a)))
+ *   cons.E += power_per_bcg_mass * beta_dt * rho_bcg; AddDensityToConsAtFixedVel(mass_rate_per_bcg_mass * beta_dt * rho_bcg)
+ * on the stored primitives (cluster_utils.hpp:24-34), then ConsToPrim, whose flags go into the flag word; cons and prim
+ * are stored.  The cube is a product where the reference writes pow(r + a, 3).  block_xmin as for apk_gravity_src. */
+int apk_snia_feedback_src(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_snia_cfg *cfg,
+                          const double *block_xmin, double beta_dt, apk_stream_t stream);
+/* StellarFeedback's numbers (stellar_feedback.cpp:105-114): mass_to_energy = efficiency * c * c */
+typedef struct apk_stellar_cfg {
+  double stellar_radius, exclusion_radius;
+  double number_density_threshold, temperature_threshold;
+  double mbar, mbar_over_kb, mass_to_energy;
+} apk_stellar_cfg;
+/* the "cluster_*" params of cluster.cpp:250-277; a clip at its disabled value (dfloor <= 0, a ceiling +inf) is skipped */
+typedef struct apk_clips_cfg {
+  double clip_r, dfloor, vceil, vAceil, eceil;
+} apk_clips_cfg;
+/* Replaces ClusterSplitSrcTerm (cluster.cpp:85-93) in ONE launch over an active list (apk_trig_box, clipped to the
+ * blocks' interior: both reference loops run over IndexDomain::interior).  A lane owns its cell and applies in order
+ *   1. stellar != NULL: StellarFeedback::FeedbackSrcTerm's lambda (stellar_feedback.cpp:135-169) -- out when
+ *      r > stellar_radius || r <= exclusion_radius (r = sqrt(r2)), when rho / mbar < number_density_threshold, when
+ *      mbar_over_kb * p / rho > temperature_threshold (stored primitives); delta = threshold * mbar - rho;
+ *      AddDensityToConsAtFixedVelTemp(delta), E += -mass_to_energy * delta, ConsToPrim.  Where the reference aborts
+ *      ("Added thermal energy should be positive") APK_FLAG_STELLAR_ENERGY is latched and the kernel goes on.
+ *   2. clips != NULL and r2 < clip_r * clip_r: ApplyClusterClips' lambda (cluster_clips.cpp:93-155) statement for
+ *      statement -- ConsToPrim first, dfloor, vceil, vAceil (GLM-MHD only), eceil -- and NO ConsToPrim afterwards: the
+ *      primitives are stored as the reference leaves them (a stale velocity after dfloor included).
+ * sums: device, [nblocks][8], cleared first: stellar_mass (the sum of -(delta * dV)), added_dfloor_mass,
+ * removed_eceil_energy, removed_vceil_energy, added_vAceil_mass, three zeros; the deterministic block sum of
+ * apk_agn_triggering_reduce.  One call with both configurations equals stellar alone followed by clips alone. */
+#define APK_FLAG_STELLAR_ENERGY 32u
+int apk_cluster_split_src(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_stellar_cfg *stellar,
+                          const apk_clips_cfg *clips, const apk_trig_box *boxes, int nboxes, int64_t max_box_cells,
+                          const double *block_xmin, double *sums, apk_stream_t stream);
+
 /* ---- field snapshots: one fused pass from the conserved state to a dense staging buffer (csrc/kernels_output.hip) ----
  * Component codes.  APK_OUT_CONS + n: conserved variable n as stored (n < nhydro + nscalars); APK_OUT_PRIM + n: primitive
  * n as ConsToPrim would give it (passive scalars: r_n = s_n / rho); the derived fields of the reference's
@@ -1079,7 +1124,8 @@ enum apk_timing_slot {
   APK_T_TOWER = 16,          /* apk_magnetic_tower_src */
   APK_T_TOWER_CONTRIBS = 17, /* apk_magnetic_tower_power_contribs */
   APK_T_TRIGGERING = 18,     /* apk_agn_triggering_reduce, apk_agn_triggering_remove_bondi */
-  APK_T_COUNT = 19
+  APK_T_CLUSTER_SOURCES = 19, /* apk_snia_feedback_src, apk_cluster_split_src */
+  APK_T_COUNT = 20
 };
 int apk_kernel_timing_enable(apk_ctx *ctx, int on);
 /* total_ms / launches may be NULL */

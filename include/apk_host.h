@@ -212,9 +212,9 @@ int apk_sim_cooling_table(const apk_sim *sim, int which, double *out, int n, int
  * The slice built here: static gravity (NFW + Hernquist BCG + SMBH) as an unsplit source, the ACCEPT-like entropy
  * profile and the hydrostatic-equilibrium sphere, or uniform gas; a uniform field with GLM-MHD.  Keys and defaults are
  * the reference's (<problem/cluster>, .../gravity, .../entropy_profile, .../hydrostatic_equilibrium, .../uniform_gas,
- * .../uniform_b_field; AGN feedback and the magnetic tower: below).  Refused at creation, each with a message naming the
- * key: refined meshes, nx2 = 1 or nx3 = 1, stellar_feedback, snia_feedback unless
- * disabled = true, any clips key off its default, init_perturb/sigma_v or sigma_b != 0, dipole_b_field, reductions, the
+ * .../uniform_b_field; AGN feedback, the magnetic tower, AGN triggering, SNIa feedback, stellar feedback and the clips:
+ * below).  Refused at creation, each with a message naming the
+ * key: refined meshes, nx2 = 1 or nx3 = 1, init_perturb/sigma_v or sigma_b != 0, dipole_b_field, reductions, the
  * sphere without <units> and hydro/He_mass_fraction, uniform_b_field without GLM-MHD, gravity_srcterm with
  * diffusion/integrator = rkl2.  All entries below work on a host-only sim. */
 typedef struct apk_cluster_options {
@@ -350,6 +350,47 @@ int apk_sim_agn_triggering_active_list(const apk_sim *sim, int *out, int n, int 
 int apk_sim_agn_triggering_reduce(apk_sim *sim, double dt);
 /* RemoveBondiAccretedGas on the current state with the stored total_mass and accretion rate.  For tests. */
 int apk_sim_agn_triggering_remove_bondi(apk_sim *sim, double dt);
+
+/* ---- SNIa feedback, stellar feedback and the clips of the cluster problem (src/pgen/cluster/snia_feedback.cpp,
+ * stellar_feedback.cpp, cluster_clips.cpp, cluster.cpp:240-313; csrc/host/cluster.cpp, csrc/kernels_cluster_sources.hip)
+ * Keys and defaults are the reference's: <problem/cluster/snia_feedback> power_per_bcg_mass, mass_rate_per_bcg_mass,
+ * disabled (false); <problem/cluster/stellar_feedback> stellar_radius, exclusion_radius (0: agn_triggering/
+ * accretion_radius), efficiency, number_density_threshold, temperature_threshold (all zero: disabled);
+ * <problem/cluster/clips> clip_r (-1), dfloor (-1), vceil, vAceil, Tceil (infinity), eceil = Tceil / mbar_over_kb /
+ * (gamma - 1).  Refused at creation, naming the key ("refused, never ignored" extends to blocks that would be inert):
+ * snia_feedback not disabled with both rates zero (the reference runs it as a no-op) or without a BCG; a partly set
+ * stellar block; stellar feedback without <units> and hydro/He_mass_fraction; clip_r > 0 with no limit set; a limit off
+ * its default with clip_r <= 0; vAceil without GLM-MHD; Tceil without units; any of the three with
+ * diffusion/integrator = rkl2.
+ * SNIa runs in every flux-array stage after the feedback sources, with the stage's beta_dt (cluster.cpp:82-83).  The
+ * split sources run once per cycle after the unsplit sources of the last stage and before its exchange, with the full
+ * dt (hydro_driver.cpp:548-560), over an active list of their own: per local block the interior index box of the cells
+ * that can lie within max(stellar_radius, clip_r).  Their five sums go through the rank-order sum into running totals
+ * that accumulate per cycle and are reset when a history row is written (cluster.cpp:300-313); runs with stellar
+ * feedback or clips, and only those, carry them as five more history columns under the reference's names.  Not
+ * restarted; uniform meshes; the reductions cold_mass and agn_extent are not built. */
+typedef struct apk_cluster_source_options {
+  int snia_active, stellar_active, clips_active;
+  int flux_path_sources;      /* some source of this run (these three or any other) keeps its stages on the flux-array path */
+  int active_blocks;          /* this rank's entries of the split sources' active list ... */
+  long long active_box_cells; /* ... and the cells of their boxes */
+  double power_per_bcg_mass, mass_rate_per_bcg_mass, rho_const_bcg; /* SNIa; rho_const_bcg as apk_snia_cfg's */
+  double stellar_radius, exclusion_radius, efficiency, number_density_threshold, temperature_threshold;
+  double mbar, mbar_over_kb, mass_to_energy; /* mu * mh, the package's mbar_over_kb, efficiency * c * c (0 without units) */
+  double clip_r, dfloor, vceil, vAceil, Tceil, eceil;
+} apk_cluster_source_options;
+int apk_sim_cluster_source_options(const apk_sim *sim, apk_cluster_source_options *opt);
+/* the split sources' active list, as apk_sim_agn_triggering_active_list.  Works on a host-only sim. */
+int apk_sim_cluster_split_active_list(const apk_sim *sim, int *out, int n, int *size);
+/* apk_snia_feedback_src once on the current state with the given beta_dt.  For tests. */
+int apk_sim_snia_feedback_src(apk_sim *sim, double beta_dt);
+/* apk_cluster_split_src once on the current state (stellar / clips: which of the configured steps run), the sum over
+ * ranks into out[5] (stellar_mass, added_dfloor_mass, removed_eceil_energy, removed_vceil_energy, added_vAceil_mass) and
+ * into the running totals.  dt is taken for symmetry with the reference's call; neither step depends on it.  A
+ * collective.  For tests. */
+int apk_sim_cluster_split_src(apk_sim *sim, double dt, int stellar, int clips, double out[5]);
+/* the running totals since the last history row, in the order above */
+int apk_sim_cluster_source_totals(const apk_sim *sim, double out[5]);
 
 /* ---- tracer particles (<tracers>, src/tracers/tracers.cpp; csrc/host/tracers.cpp) ---------------------------------
  * Keys (tracers.cpp:43-93, 102-118): enabled (default false), initial_seed_method = none | random_per_block | user,
