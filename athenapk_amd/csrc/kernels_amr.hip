@@ -10,6 +10,7 @@
 
 #include "apk_internal.hpp"
 #include "hydro_math.hpp"
+#include "wg_reduce.hpp"
 
 // (merged plans, apk_flux_fix_plan_create_merged: the regions of all directions in ONE launch)
 struct FixRegionBox {
@@ -422,16 +423,7 @@ __global__ void __launch_bounds__(256) tag_kernel(PackView pv, unsigned long lon
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
-  __shared__ double part[4];
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  if ((tid & 63) == 0) part[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    const double mm = fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
-    atomicMax(block_max + b, (unsigned long long)__double_as_longlong(mm));
-  }
+  wg_max_to_word(m, block_max + b, true);
 }
 
 }  // namespace

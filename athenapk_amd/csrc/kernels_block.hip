@@ -6,6 +6,7 @@
 #include "apk_internal.hpp"
 #include "flux_div.hpp"
 #include "hydro_math.hpp"
+#include "wg_reduce.hpp"
 
 namespace apk {
 
@@ -76,18 +77,6 @@ dedner_kernel(PackView pv, double coeff, double beta_dt) {
   u[IPS * pv.sn] *= coeff;
 }
 
-// ---- wave/workgroup reductions -------------------------------------------------------------
-APK_DEV double wave_min(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-  return v;
-}
-APK_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // ---- ConservedToPrimitive over the ENTIRE block (src/eos/adiabatic_hydro.cpp:33-55) -----
 // store_vars: bit n set = primitive n is stored (all ones: FillDerived; apk_cons_to_prim_dt_select stores a subset)
 template <int FLUID>
@@ -138,20 +127,6 @@ APK_DEV double cell_dt_hyp(const PackView &pv, const apk_block_desc &blk, double
   if (pv.ndim > 2) m = fmin(m, blk.dx[2] / (fabs(w[IV3]) + lz));
   return m;
 }
-// (64, 4) workgroups: one candidate per workgroup, and an atomic only if it beats the word's current value (a plain
-// read: a stale, larger value merely costs an atomic that changes nothing).  Every thread of the workgroup calls it.
-APK_DEV void block_min_to_word(double lane_min, unsigned long long *word) {
-  __shared__ double wmin[4];
-  const double m = wave_min(lane_min);
-  if (threadIdx.x == 0) wmin[threadIdx.y] = m;
-  __syncthreads();
-  if (threadIdx.x == 0 && threadIdx.y == 0) {
-    const double g = fmin(fmin(wmin[0], wmin[1]), fmin(wmin[2], wmin[3]));
-    // (blockDim must be (64, 4, 1): wmin[4] / threadIdx.y above)
-    const double cur = __longlong_as_double((long long)__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    if (g < cur) atomicMin(word, (unsigned long long)__double_as_longlong(g));
-  }
-}
 
 // WITH_DT: EstimateHyperbolicTimestep (hydro.cpp:845-895) of the interior cells on the way, from the primitives in
 // registers -- the values min_dt_kernel would read back -- reduced into *dt_bits (apk_cons_to_prim_dt).
@@ -198,7 +173,7 @@ cons_to_prim_kernel(PackView pv, apk_eos eos, unsigned *flags, unsigned long lon
       if (i >= pv.is && i <= pv.ie && j >= pv.js && j <= pv.je && k >= pv.ks && k <= pv.ke) lane_min = cell_dt_hyp<FLUID>(pv, blk, eos.gamma, w);
     }
   }
-  if constexpr (WITH_DT) block_min_to_word(lane_min, dt_bits);
+  if constexpr (WITH_DT) wg_min_to_word(lane_min, dt_bits);
 }
 
 // Interior cells and the ghost cells straight behind a FACE of the block (at most one ghost coordinate):
@@ -228,7 +203,7 @@ cons_to_prim_faces_kernel(PackView pv, apk_eos eos, unsigned *flags, const int *
       if (ghost == 0) lane_min = cell_dt_hyp<FLUID>(pv, blk, eos.gamma, w);
     }
   }
-  if constexpr (WITH_DT) block_min_to_word(lane_min, dt_bits);
+  if constexpr (WITH_DT) wg_min_to_word(lane_min, dt_bits);
 }
 
 // The end of a cycle of a refined mesh whose stage loop stores no primitives (apk_tag_blocks_begin_from_cons): the
@@ -297,16 +272,8 @@ tag_pgrad_from_cons_kernel(PackView pv, apk_eos eos, unsigned *flags, unsigned l
       m = fmax(m, eps);
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
-  __shared__ double part[4];
-  if ((tid & 63) == 0) part[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0 && k0 <= ku) {
-    const double mm = fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
-    atomicMax(block_max + b, (unsigned long long)__double_as_longlong(mm));
-  }
-  block_min_to_word(lane_min, dt_bits);
+  wg_max_to_word(m, block_max + b, k0 <= ku);
+  wg_min_to_word(lane_min, dt_bits);
 }
 
 // Ghost zones only (the interior was converted by the finishing sweep of the fused stage).  The
@@ -399,15 +366,7 @@ min_dt_kernel(PackView pv, double gamma, unsigned long long *min_bits, int kchun
     if (pv.ndim > 1) min_dt = fmin(min_dt, blk.dx[1] / (fabs(v2) + ly));
     if (pv.ndim > 2) min_dt = fmin(min_dt, blk.dx[2] / (fabs(v3) + lz));
   }
-  min_dt = wave_min(min_dt);
-  __shared__ double part[4];
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  if ((tid & 63) == 0) part[tid >> 6] = min_dt;
-  __syncthreads();
-  if (tid == 0) {
-    const double m = fmin(fmin(part[0], part[1]), fmin(part[2], part[3]));
-    atomicMin(min_bits, (unsigned long long)__double_as_longlong(m));
-  }
+  wg_min_to_word(min_dt, min_bits);
 }
 
 // ---- HydroHst (src/hydro/hydro.cpp:145-208): per-workgroup partials, fixed-order final ----
@@ -440,29 +399,7 @@ __global__ void __launch_bounds__(256) history_kernel(PackView pv, double *parti
                  : 0;
     }
   }
-  __shared__ double part[4][8];
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const double s = wave_sum(h[q]);
-    if ((tid & 63) == 0) part[tid >> 6][q] = s;
-  }
-  __syncthreads();
-  if (tid < 8) {
-    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partial[(int64_t)wg * 8 + tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
-  }
-}
-
-__global__ void __launch_bounds__(256) history_final_kernel(const double *partial, int nwg,
-                                                            double *out8) {
-  // 8 quantities x 32 lanes each; fixed summation order => run-to-run deterministic
-  const int q = threadIdx.x / 32, lane = threadIdx.x % 32;
-  double s = 0.0;
-  for (int w = lane; w < nwg; w += 32) s += partial[(int64_t)w * 8 + q];
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) s += __shfl_down(s, off, 32);
-  if (lane == 0) out8[q] = s;
+  wg_sums_to_row(h, partial + wg_index() * 8);
 }
 
 // ---- FirstOrderFluxCorrect (src/hydro/hydro.cpp:1223-1342), two-phase schedule -------------
@@ -780,7 +717,7 @@ int launch_history(const PackView &pv, int fluid, double *d_partial, int *nwg_ou
   else
     hipLaunchKernelGGL(history_kernel<APK_FLUID_GLMMHD>, grid, dim3(64, 4, 1), 0, s, pv,
                        d_partial);
-  hipLaunchKernelGGL(history_final_kernel, dim3(1), dim3(256), 0, s, d_partial, nwg, d_out8);
+  hipLaunchKernelGGL(final_sum_kernel<8>, dim3(1), dim3(256), 0, s, d_partial, nwg, d_out8);
   return hipGetLastError() == hipSuccess ? APK_OK : APK_ERR_DEVICE;
 }
 

@@ -39,6 +39,7 @@
 #include "apk_internal.hpp"
 #include "cooling_table.hpp"
 #include "hydro_math.hpp"
+#include "wg_reduce.hpp"
 
 namespace apk {
 
@@ -327,12 +328,6 @@ __global__ void __launch_bounds__(256) cool_townsend_kernel(PackView pv, CoolDev
   u[IEN * sn] += rho * (internal_e_new - internal_e);
 }
 
-APK_DEV double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-
 // EstimateTimeStep (tabular_cooling.cpp:606-665): min over interior cells of the cooling time into min_bits (positive
 // doubles and +inf order like their bit patterns)
 __global__ void __launch_bounds__(256) cool_dt_kernel(PackView pv, CoolDev c, double gm1, unsigned long long *min_bits,
@@ -354,15 +349,7 @@ __global__ void __launch_bounds__(256) cool_dt_kernel(PackView pv, CoolDev c, do
     m = cooling_time < m ? cooling_time : m;  // std::min(cooling_time, m)
   }
   latch(d_flags, flags);
-  m = wave_min(m);
-  __shared__ double part[4];
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) part[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    const double r = fmin(fmin(part[0], part[1]), fmin(part[2], part[3]));
-    atomicMin(min_bits, (unsigned long long)__double_as_longlong(r));
-  }
+  wg_min_to_word(m, min_bits);
 }
 
 __global__ void __launch_bounds__(256) cool_dedt_kernel(CoolDev c, const double *e, const double *rho, double *out,

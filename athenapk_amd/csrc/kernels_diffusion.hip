@@ -27,6 +27,7 @@
 #include "apk_internal.hpp"
 #include "diff_flux_face.hpp"
 #include "hydro_math.hpp"
+#include "wg_reduce.hpp"
 
 namespace apk {
 
@@ -89,12 +90,6 @@ __global__ void __launch_bounds__(256) diff_flux_kernel(PackView pv, DiffCoeffs 
   if constexpr (COND != COND_NONE || VISC || RES) fl[IEN * sn] = f.e;
 }
 
-APK_DEV double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-
 // EstimateConductionTimestep, general branch (conduction.cpp:96-180), with chi = ThermalDiffusivity::Get of the cell:
 // the minimum over interior cells of dx_d^2 / chi (COND_ISO_GEN: isotropic Spitzer, no TINY) or of
 // dx_d^2 / (chi |B_d| / |B| cos(theta) + TINY) (COND_ANISO) into min_bits (positive doubles order like their bit
@@ -138,15 +133,7 @@ __global__ void __launch_bounds__(256) cond_dt_kernel(PackView pv, DiffCoeffs c,
       }
     }
   }
-  m = wave_min_d(m);
-  __shared__ double part[4];
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  if ((tid & 63) == 0) part[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    const double r = fmin(fmin(part[0], part[1]), fmin(part[2], part[3]));
-    atomicMin(min_bits, (unsigned long long)__double_as_longlong(r));
-  }
+  wg_min_to_word(m, min_bits);
 }
 
 using DiffKernel = void (*)(PackView, DiffCoeffs, int);

@@ -36,8 +36,8 @@
 // so about 250 B on top of the step; the standalone kernel (the passes, and the seed-time call) reads rho and active
 // again, + 12 B.  The counting sort carries all 24 values: + 192 B read and 192 B written per sort.
 // The sums use no atomic: every lane forms a term (exact zeros for inactive and out-of-range lanes), the wave adds it
-// with the shuffle pattern of kernels_block.hip (wave_sum), lane 0 of the four waves leaves it in LDS, and 26 lanes add
-// the four in wave order and store the workgroup's row of partials[nworkgroups][26] with ordinary vector stores;
+// with wave_sum (wg_reduce.hpp), lane 0 of the four waves leaves it in LDS, and 26 lanes add the four in wave order
+// and store the workgroup's row of partials[nworkgroups][26] with ordinary vector stores;
 // tracers_lookback_sum_kernel (26 workgroups, one per sum, a stride loop over the rows) adds the rows.
 //
 // Locality: apk_tracers_sort is a counting sort by (block, interior k-plane) -- histogram, one-workgroup scan, scatter
@@ -45,6 +45,7 @@
 // sort by id).  Inactive particles go to a bucket of their own at the end.
 #include "apk_internal.hpp"
 #include "hydro_math.hpp"
+#include "wg_reduce.hpp"
 
 namespace apk {
 
@@ -162,14 +163,13 @@ APK_DEV void tracer_lookback_partials(const double (&s)[NLB], const double (&sd)
 #pragma unroll
   for (int q = 0; q < NSUMS; ++q) {
     const double term = q < NLB ? s[0] * s[q] : q < 2 * NLB ? sd[0] * sd[q - NLB] : q == 2 * NLB ? s[0] : sd[0];
-    double v = term;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const double v = wave_sum(term);
     if (lane == 0) part[wave][q] = v;
   }
   __syncthreads();
   if (threadIdx.x < NSUMS) {
     const int q = threadIdx.x;
+    // (wave order, here and in tracers_lookback_sum_kernel: not wg_sums_to_row's pairs -- the correlations keep their bits)
     row[q] = ((part[0][q] + part[1][q]) + part[2][q]) + part[3][q];
   }
 }
@@ -275,8 +275,7 @@ __global__ void __launch_bounds__(256) tracers_lookback_sum_kernel(const double 
   const int q = blockIdx.x;
   double v = 0.0;
   for (int64_t r = threadIdx.x; r < nrows; r += 256) v += partials[r * NSUMS + q];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) sums26[q] = ((part[0] + part[1]) + part[2]) + part[3];

@@ -9,6 +9,7 @@
 
 #include "apk_internal.hpp"
 #include "hydro_math.hpp"
+#include "wg_reduce.hpp"
 
 struct apk_fmft {
   int nblocks = 0, num_modes = 0;
@@ -169,43 +170,8 @@ fmft_inverse_kernel(PackView pv, const apk_fmft_block *blocks, const double *var
   blk.acc[2 * pv.sn + cell] = s2;
 }
 
-APK_DEV double wsum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// generic "NQ sums per workgroup" epilogue: partial[wg][NQ]
-template <int NQ>
-APK_DEV void store_partials(const double (&h)[NQ], double *partial) {
-  __shared__ double part[4][NQ];
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const double s = wsum(h[q]);
-    if ((tid & 63) == 0) part[tid >> 6][q] = s;
-  }
-  __syncthreads();
-  if (tid < NQ) {
-    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partial[(int64_t)wg * NQ + tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
-  }
-}
-
-template <int NQ>
-__global__ void __launch_bounds__(256) final_sum_kernel(const double *partial, int nwg, double *out) {
-  // NQ <= 8 quantities x 32 lanes each, fixed order => deterministic
-  const int q = threadIdx.x / 32, lane = threadIdx.x % 32;
-  if (q >= NQ) return;
-  double s = 0.0;
-  for (int w = lane; w < nwg; w += 32) s += partial[(int64_t)w * NQ + q];
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) s += __shfl_down(s, off, 32);
-  if (lane == 0) out[q] = s;
-}
-
 // first level of the final sum when there are many partials (one per 256 cells: 65536 on 256^3, which
-// the single workgroup above walks in 2048 dependent steps = 0.6 ms): kMidGroups workgroups each sum a
+// final_sum_kernel's single workgroup walks in 2048 dependent steps = 0.6 ms): kMidGroups workgroups each sum a
 // contiguous share in a fixed order; the single workgroup then adds kMidGroups values per quantity
 constexpr int kMidGroups = 256;
 template <int NQ>
@@ -219,16 +185,7 @@ __global__ void __launch_bounds__(256) mid_sum_kernel(const double *partial, int
 #pragma unroll
     for (int q = 0; q < NQ; ++q) h[q] += partial[(int64_t)w * NQ + q];
   }
-  __shared__ double part[4][NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const double v = wsum(h[q]);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][q] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NQ)
-    out[(int64_t)blockIdx.x * NQ + threadIdx.x] =
-        (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+  wg_sums_to_row(h, out + (int64_t)blockIdx.x * NQ);
 }
 
 // turbulence.cpp:395-413
@@ -247,7 +204,7 @@ turb_mean_momentum_kernel(PackView pv, const apk_fmft_block *blocks, double *par
     h[2] = den * acc[1 * pv.sn] * vol;
     h[3] = den * acc[2 * pv.sn] * vol;
   }
-  store_partials<4>(h, partial);
+  wg_sums_to_row(h, partial + wg_index() * 4);
 }
 
 // turbulence.cpp:421-430
@@ -267,7 +224,7 @@ turb_remove_mean_kernel(PackView pv, const apk_fmft_block *blocks, double m1, do
     acc[2 * pv.sn] = a2;
     h[0] = sqr(a0) * vol + sqr(a1) * vol + sqr(a2) * vol;
   }
-  store_partials<1>(h, partial);
+  wg_sums_to_row(h, partial + wg_index());
 }
 
 // turbulence.cpp:446-469
@@ -316,7 +273,7 @@ __global__ void __launch_bounds__(256) turb_history_kernel(PackView pv, double g
       h[2] = p / e_mag * vol;
     }
   }
-  store_partials<3>(h, partial);
+  wg_sums_to_row(h, partial + wg_index() * 3);
 }
 
 // field_loop::RelDivBHst (src/pgen/field_loop.cpp:60-95): sum of 0.5 |dx| |div B| / B0 * volume with
@@ -333,7 +290,7 @@ __global__ void __launch_bounds__(256) user_reldivb_kernel(PackView pv, double B
     if (pv.ndim == 3) divb += (b3[pv.sk] - b3[-pv.sk]) / blk.dx[2];
     h[0] = 0.5 * (sqrt(sqr(blk.dx[0]) + sqr(blk.dx[1]) + sqr(blk.dx[2]))) * fabs(divb) / B0 * vol;
   }
-  store_partials<1>(h, partial);
+  wg_sums_to_row(h, partial + wg_index());
 }
 
 // run a partial-sum kernel result through the final reduction and bring NQ doubles to the host
@@ -396,22 +353,7 @@ turb_apply_fill_kernel(PackView pv, const apk_fmft_block *blocks, double norm, d
       if (pv.ndim > 2) lane_min = fmin(lane_min, blk.dx[2] / (fabs(w[IV3]) + lz));
     }
   }
-  if constexpr (WITH_DT) {
-    // one candidate per workgroup, and an atomic only if it beats the word's current value (a plain read: a
-    // stale, larger value merely costs an atomic that changes nothing) -- 65536 workgroups on 256^3 would
-    // otherwise queue on one address for milliseconds
-    __shared__ double wmin[4];
-    double m = lane_min;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_down(m, off, 64));
-    if (threadIdx.x == 0) wmin[threadIdx.y] = m;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-      m = fmin(fmin(wmin[0], wmin[1]), fmin(wmin[2], wmin[3]));
-      const double cur = __longlong_as_double((long long)*reinterpret_cast<volatile unsigned long long *>(dt_bits));
-      if (m < cur) atomicMin(dt_bits, (unsigned long long)__double_as_longlong(m));
-    }
-  }
+  if constexpr (WITH_DT) wg_min_to_word(lane_min, dt_bits);
 }
 
 template <int NQ>

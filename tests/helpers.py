@@ -223,6 +223,32 @@ def orc_stage(fluid, recon, riemann, g, u0, u1, prim, gamma, c_h, gam0, gam1, be
     return out
 
 
+# ---- the device's order of additions in a workgroup sum (csrc/wg_reduce.hpp), restated ------------
+def wave_tree_sum(v):
+    """[..., 64] lane values -> lane 0 of the shuffle tree: v[l] += v[l + off] for off = 32, 16, ..., 1."""
+    v = np.array(v, dtype=np.float64, copy=True)
+    off = v.shape[-1] // 2
+    while off > 0:
+        v[..., :off] += v[..., off:2 * off]
+        off //= 2
+    return v[..., 0]
+
+
+def wg_pair_sum(w):
+    """[..., 4] wave results -> the workgroup's sum, (w0 + w1) + (w2 + w3)."""
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def final_sum32(partial):
+    """[nwg, nq] rows of partials -> [nq]: lane l of 32 adds the rows l, l + 32, ... in turn, from 0.0; then a
+    width-32 tree."""
+    nwg, nq = partial.shape
+    s = np.zeros((nq, 32))
+    for w in range(nwg):
+        s[:, w % 32] += partial[w]
+    return wave_tree_sum(s)
+
+
 def interior(a, nx, ng):
     """Slice the interior cells of [..., nvar, Nk, Nj, Ni]."""
     sk = slice(ng, ng + nx[2]) if nx[2] > 1 else slice(0, 1)

@@ -454,6 +454,68 @@ def test_history(request, fluid):
     np.testing.assert_allclose(got, want, rtol=1e-13, atol=1e-15)
 
 
+def _history_lane_terms(fluid, nx, ng, dx, cons):
+    """history_kernel's eight terms of every cell, operation for operation (the parity build contracts nothing and
+    rounds its divide and sqrt correctly), in the lanes interior_cell / rect_ij give them: [nwg, 4 waves, 64 lanes, 8],
+    zeros in the lanes without a cell."""
+    sqr = lambda x: x * x
+    nb = cons.shape[0]
+    n1, n2, n3 = nx
+    at = lambda n, dk=0, dj=0, di=0: cons[:, n, ng + dk:ng + dk + n3, ng + dj:ng + dj + n2, ng + di:ng + di + n1]
+    vol = dx[0] * dx[1] * dx[2]
+    d, m1, m2, m3, en = (at(n) for n in range(5))
+    h = np.zeros((8, nb, n3, n2, n1))
+    h[0], h[1], h[2], h[3] = d * vol, m1 * vol, m2 * vol, m3 * vol
+    h[4] = 0.5 / d * (sqr(m1) + sqr(m2) + sqr(m3)) * vol
+    h[5] = en * vol
+    if fluid == "glmmhd":
+        b1, b2, b3 = at(5), at(6), at(7)
+        h[6] = 0.5 * (sqr(b1) + sqr(b2) + sqr(b3)) * vol
+        divb = (at(5, di=1) - at(5, di=-1)) / dx[0] + (at(6, dj=1) - at(6, dj=-1)) / dx[1]
+        divb = divb + (at(7, dk=1) - at(7, dk=-1)) / dx[2]
+        abs_b = np.sqrt(sqr(b1) + sqr(b2) + sqr(b3))
+        assert np.all(abs_b != 0)
+        h[7] = 0.5 * np.sqrt(sqr(dx[0]) + sqr(dx[1]) + sqr(dx[2])) * np.abs(divb) / abs_b * vol
+    # lanes: (64, 4) tiles of a plane where nx1 >= 48, else the plane's rows flattened over 256 lanes
+    B, K, J, I = np.meshgrid(np.arange(nb), np.arange(n3), np.arange(n2), np.arange(n1), indexing="ij")
+    if n1 >= 48:
+        gx, gy = (n1 + 63) // 64, (n2 + 3) // 4
+        bx, by, tid = I // 64, J // 4, (J % 4) * 64 + I % 64
+    else:
+        gx, gy = 1, (n1 * n2 + 255) // 256
+        f = J * n1 + I
+        bx, by, tid = 0 * f, f // 256, f % 256
+    wg = ((B * n3 + K) * gy + by) * gx + bx
+    lanes = np.zeros((nb * n3 * gy * gx, 256, 8))
+    lanes[wg, tid] = np.moveaxis(h, 0, -1)
+    return lanes.reshape(-1, 4, 64, 8)
+
+
+@pytest.mark.parametrize("fluid", ["euler", "glmmhd"])
+@pytest.mark.parametrize("nx", [(16, 8, 8), (64, 6, 5)], ids=["flat_rows", "tiles"])
+def test_history_sums_in_the_stated_order(request, fluid, nx):
+    """The history sums, bit for bit: the order of additions csrc/wg_reduce.hpp states -- a shuffle tree per wave,
+    (w0 + w1) + (w2 + w3) over the four waves, then final_sum_kernel<8>'s 32 striding lanes and their tree -- on the
+    kernel's own per-cell terms.  (16,8,8) flattens rows and leaves every workgroup half empty; (64,6,5) has (64,4)
+    tiles whose second one has two waves of zeros.  The data tell orders apart: the exactly rounded sum of the same
+    terms differs in at least one column."""
+    import math
+    from athenapk_amd import hydro
+    ctx = _ctx(request, True)
+    ng, dx = 2, (0.1, 0.07, 0.13)
+    g = H.geom(fluid, nx, ng, 0, dx)
+    cons = H.prim_to_cons(fluid, H.random_prim(fluid, nx, ng, seed=21, kind="rough", nblocks=3), GAMMA)
+    lanes = _history_lane_terms(fluid, nx, ng, tuple(g.dx), cons)
+    want = H.final_sum32(H.wg_pair_sum(np.moveaxis(H.wave_tree_sum(np.moveaxis(lanes, 2, -1)), 1, -1)))
+    exact = np.array([math.fsum(lanes[..., q].ravel()) for q in range(8)])
+    assert np.any(want != exact), "this data does not tell one order of additions from another"
+    assert np.all(want[:6] != 0) and (fluid == "euler" or np.all(want[6:] != 0))
+    md = hydro.MeshData(ctx, nx, ng, NHYDRO[fluid], dx=tuple(g.dx), nblocks=3, cons=cons, with_flux=False)
+    got = np.asarray(hydro.HydroHst(md, fluid))
+    print("history sums", fluid, nx, "got", got.tolist(), "want", want.tolist(), "exact", exact.tolist())
+    assert np.array_equal(got, want)
+
+
 # ---- FirstOrderFluxCorrect ------------------------------------------------------------------------
 @pytest.mark.parametrize("fluid", ["euler", "glmmhd"])
 def test_first_order_flux_correct(request, fluid):
