@@ -82,19 +82,10 @@ __device__ unsigned long long g_m12f_phase[8];
 #define APK_TICK(slot) do { } while (0)
 #endif
 
-#ifndef APK_M12F_WAVE_ENDS
-// 1 (diagnostic variant build, `make variant VAR=we VARFLAGS=-DAPK_M12F_WAVE_ENDS=1`): every wave records three times of
-// the constant-rate wall clock (100 MHz) -- its start, the end of its whole columns, its end -- by vector stores of lane
-// 0, and launch_m12f writes the table of launch number APK_M12F_WAVE_ENDS_CALL to the file APK_M12F_WAVE_ENDS_OUT
-// (tools/m12f_wave_ends.py turns it into the distribution of end times).  In this build APK_M12F_STATIC=1 keeps the
-// static leftover split and APK_M12F_PIECE_ROWS sets the dynamic phase's piece length: the before / after pair and
-// the sweep behind the launcher's choice come from one library.
-#define APK_M12F_WAVE_ENDS 0
-#endif
-#if APK_M12F_WAVE_ENDS
-constexpr int kWaveEndsMax = 4096;
-__device__ unsigned long long g_m12f_wave_ends[3 * kWaveEndsMax];
-#endif
+// APK_M12F_WAVE_ENDS = 1 (diagnostic variant build, `make variant VAR=we VARFLAGS=-DAPK_M12F_WAVE_ENDS=1`): every wave
+// records its start, the end of its whole columns and its end, and launch_m12f writes the table of one launch to the
+// file APK_M12F_WAVE_ENDS_OUT -- wave_ends.hpp, with the switches of that build (static leftover split, piece length,
+// priority off: the before / after pairs and the sweep behind the launcher's choice come from one library).
 
 // does the from-cons finishing march keep the loaded rows in a second LDS ring?  (two rings within the 20 KB a wave may
 // take with two waves per SIMD, with some room)
@@ -171,9 +162,13 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
   // ticket is one vector atomic of lane 0, made wave-uniform by v_readfirstlane (no scalar memory instruction).  Which
   // wave marches a row does not enter its result.
   const int left_segs = tickets ? (u0.nx2 + piece_rows - 1) / piece_rows : 0;
+  // The wave's priority follows the share of the piece it is marching that it has left (wave_priority.hpp), whole
+  // columns and ticket pieces alike: of the two waves of a SIMD the one that is behind issues first, so the partners of a
+  // pair reach the end of their columns together instead of 0.5 ms apart.
+  WavePriority prio;
 #if APK_M12F_WAVE_ENDS
-  const unsigned long long we_start_ = wall_clock64();
-  unsigned long long we_cols_ = we_start_;
+  prio.off = (sp.prio_off & 1) != 0;
+  WaveEndsMark we_ = wave_ends_begin();
 #endif
   for (int piece = 0;; ++piece) {  // wave-uniform
     // ---- this piece: rows s..e of column chunk `chunk` of block b
@@ -182,7 +177,7 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
       item = piece * nwaves + w, j0 = 0, nrows = u0.nx2;
     } else if (tickets) {
 #if APK_M12F_WAVE_ENDS
-      if (piece == full) we_cols_ = wall_clock64();
+      if (piece == full) we_.mid = wall_clock64();
 #endif
       unsigned long long t = 0;
       if (lane == 0) t = atomicAdd(tickets, 1ull);
@@ -193,7 +188,7 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
       nrows = (j0 + piece_rows <= u0.nx2) ? piece_rows : u0.nx2 - j0;
     } else {
 #if APK_M12F_WAVE_ENDS
-      if (piece == full) we_cols_ = wall_clock64();
+      if (piece == full) we_.mid = wall_clock64();
 #endif
       if (piece > full || left_cols <= 0) break;
       const int sidx = w / left_cols, lc = w - sidx * left_cols;
@@ -370,6 +365,7 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
 
     int slot0 = 0;  // slot holding row c-H
     for (; c <= e + 1; ++c) {
+      prio.step(e + 1 - c, nrows + 2);
       const int64_t done = base + (int64_t)(c - 1) * st;  // the cell this iteration retires
       // (its place in d3; lanes that retire nothing get a valid column)
       const int64_t d3done = d3base + (int64_t)(c - 1) * d3st;
@@ -595,6 +591,7 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
 #pragma unroll
       for (int q = 0; q < NV; ++q) wl_prev[q] = qln[perm<2>(q)];
     }
+    prio.done();
   }
 #if APK_M12F_TIMING
   if (lane == 0) {
@@ -610,12 +607,7 @@ fused_m12f_kernel(PackView u0, PackView u1, StageParams sp, int wpb, int nwaves,
     if (lane == 0) atomicMin(sp.dt_bits, (unsigned long long)__double_as_longlong(m));
   }
 #if APK_M12F_WAVE_ENDS
-  if (lane == 0 && w < kWaveEndsMax) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the last row's stores have left the wave)
-    g_m12f_wave_ends[3 * w + 0] = we_start_;
-    g_m12f_wave_ends[3 * w + 1] = we_cols_;
-    g_m12f_wave_ends[3 * w + 2] = wall_clock64();
-  }
+  wave_ends_finish(WE_M12F, w, we_);
 #endif
 }
 
@@ -747,21 +739,10 @@ inline bool launch_m12f(const PackView &u0, const PackView &u1, const StageParam
 #if APK_M12F_WAVE_ENDS
     {
       static int calls = 0;
-      static const int want = std::getenv("APK_M12F_WAVE_ENDS_CALL") ? std::atoi(std::getenv("APK_M12F_WAVE_ENDS_CALL")) : 20;
-      const char *out = std::getenv("APK_M12F_WAVE_ENDS_OUT");
-      if (++calls == want && out) {
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h(3 * (size_t)kWaveEndsMax);
-        (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_m12f_wave_ends), h.size() * sizeof(unsigned long long));
-        if (FILE *f = std::fopen(out, "w")) {
-          std::fprintf(f, "# recon %d extra %d nwaves %d per_xcd %d columns %lld nx2 %d dynamic %d piece_rows %d\n", RECON, plan.extra,
-                       nwaves, per_xcd, ncol, u0.nx2, tickets ? 1 : 0, piece_rows);
-          std::fprintf(f, "# wave xcd start cols_end end (ticks of the 100 MHz wall clock)\n");
-          for (int w = 0; w < nwaves && w < kWaveEndsMax; ++w)
-            std::fprintf(f, "%d %d %llu %llu %llu\n", w, w / per_xcd, h[3 * w], h[3 * w + 1], h[3 * w + 2]);
-          std::fclose(f);
-        }
-      }
+      char head[200];
+      std::snprintf(head, sizeof head, "kernel m12f recon %d extra %d nwaves %d per_xcd %d columns %lld nx2 %d dynamic %d piece_rows %d",
+                    RECON, plan.extra, nwaves, per_xcd, ncol, u0.nx2, tickets ? 1 : 0, piece_rows);
+      wave_ends_dump(WE_M12F, "APK_M12F_WAVE_ENDS_OUT", calls, nwaves, per_xcd, head, s);
     }
 #endif
 #if APK_M12F_TIMING

@@ -69,6 +69,9 @@ int launch_stage_fused(apk_ctx *ctx, const PackView &u0, const PackView &u1,
   sp.du_first = 0;
   sp.du_pitch = 0;
   sp.ctx = ctx;
+#if APK_M12F_WAVE_ENDS
+  sp.prio_off = wave_ends_env("APK_WAVE_PRIORITY_OFF", 0);
+#endif
   sp.eos = a.eos;
   sp.flags = ctx->d_flags + (a.trial ? 1 : 0);
   sp.dt_bits = ctx->dt_word();  // min of the finishing sweep (apk_stage_dt_read)

@@ -24,6 +24,8 @@
 #include "apk_internal.hpp"
 #include "hydro_math.hpp"
 #include "stage_form.hpp"
+#include "wave_ends.hpp"
+#include "wave_priority.hpp"
 
 namespace apk {
 
@@ -65,6 +67,9 @@ struct StageParams {
   const apk_x1_halo_block *x1_blocks;
   int x1_recv_depth, x1_send_depth, x1_send_field;
   apk_ctx *ctx;  // host side only (kernel timing); never dereferenced on the device
+#if APK_M12F_WAVE_ENDS
+  int prio_off;  // (variant build, wave_ends.hpp: APK_WAVE_PRIORITY_OFF)
+#endif
 };
 
 // A lane's share of apk_stage_args.x1_halo on the sending side: where the cells it retires along its march go in the
@@ -649,8 +654,17 @@ fused_march_kernel(PackView u0, PackView u1, StageParams sp, int nseg, int rpw) 
                                     ring[(2 * NV + n) * 64 + lane], ring[(3 * NV + n) * 64 + lane]);
   }
 
+  // (the x3 sweep of the two-kernel stage: the wave's priority follows the share of its march it has left, so that
+  // of the two waves of a SIMD the one that is behind issues first and both end together -- wave_priority.hpp)
+  constexpr bool PRIO = ROWADDR;
+  [[maybe_unused]] WavePriority prio;
+#if APK_M12F_WAVE_ENDS
+  prio.off = (sp.prio_off & 2) != 0;
+  [[maybe_unused]] const WaveEndsMark we_ = wave_ends_begin();
+#endif
   int slot0 = 0;  // slot holding row c-H
   for (; c <= e + 1; ++c) {
+    if constexpr (PRIO) prio.step(e + 1 - c, e + 3 - s);
     // the streaming operands of the cell that completes in this iteration (c-1) are requested
     // first, so they are in flight during the reconstruction and the Riemann solve
     const int64_t done = base + (int64_t)(c - 1) * st;
@@ -765,6 +779,10 @@ fused_march_kernel(PackView u0, PackView u1, StageParams sp, int nseg, int rpw) 
 #pragma unroll
     for (int q = 0; q < NV; ++q) wl_prev[q] = qln[perm<DIR>(q)];
   }
+  if constexpr (PRIO) prio.done();
+#if APK_M12F_WAVE_ENDS
+  if constexpr (ROWADDR) wave_ends_finish(WE_X3, (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x), we_);
+#endif
   if constexpr (EXTRA == EXTRA_C2P_DT) {
     // one atomic per wave for the whole march (positive doubles order like their bit patterns)
     double m = lane_min_dt;
@@ -1100,6 +1118,9 @@ fused_dc3_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, in
 #pragma unroll
     for (int n = 0; n < NV; ++n) wnext[n] = ((s > u0.ke) ? prim_khi : prim)[n * u0.sn + (int64_t)s * u0.sk];
   }
+#if APK_M12F_WAVE_ENDS
+  const WaveEndsMark we_ = wave_ends_begin();
+#endif
   for (int c = s; c <= e + 1; ++c) {
     const int64_t off = (int64_t)c * u0.sk;
     double wc[NV];
@@ -1219,6 +1240,9 @@ fused_dc3_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, in
       }
     }
   }
+#if APK_M12F_WAVE_ENDS
+  wave_ends_finish(WE_DC, vid, we_);
+#endif
   if constexpr (EXTRA == EXTRA_C2P_DT) {
     double m = lane_min_dt;
 #pragma unroll
@@ -1389,6 +1413,12 @@ fused_dc3r2_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, 
   // plane on top of it -- 256 VGPRs + 20 B of scratch -- measured 1.15 -> 1.17 ms in round 4 and is gone.)
   constexpr int HOLD = (FROM_CONS && EXTRA != EXTRA_NONE) ? 2 : 0;
   double held[HOLD > 0 ? HOLD : 1][NV];
+  // (No wave priority here, unlike the marches of the two-kernel stage -- wave_priority.hpp: measured, DESIGN 7.R8.  With
+  // 8.4 short waves per SIMD the partners of a pair are of different ages all the time, and a priority from the share of
+  // the planes left moved neither the occupied share of the wave slots, 87 %, nor the kernel's time.)
+#if APK_M12F_WAVE_ENDS
+  const WaveEndsMark we_ = wave_ends_begin();
+#endif
   for (int c = s; c <= e + 1; ++c) {
     const int64_t off = (int64_t)plane(c) * lsk;
     double wc[2][NV];
@@ -1495,6 +1525,9 @@ fused_dc3r2_kernel(PackView u0, PackView u1, StageParams sp, int kseg, int wpb, 
       }
     }
   }
+#if APK_M12F_WAVE_ENDS
+  wave_ends_finish(WE_DC, vid, we_);
+#endif
   if constexpr (EXTRA == EXTRA_C2P_DT) {
     double m = lane_min_dt;
 #pragma unroll
@@ -1743,6 +1776,20 @@ inline bool launch_dc_march(const PackView &u0, const PackView &u1, const StageP
         if (cost < best) best = cost, kseg = cand;
       }
     }
+#if APK_M12F_WAVE_ENDS
+    kseg = wave_ends_env("APK_DC_KSEG", kseg);
+    if (kseg > u0.nx3) kseg = u0.nx3;
+    struct DumpAtExit {  // (after the launch, on every way out)
+      int nwaves, kseg, extra;
+      hipStream_t s;
+      ~DumpAtExit() {
+        static int calls = 0;
+        char head[160];
+        std::snprintf(head, sizeof head, "kernel dc extra %d nwaves %d kseg %d", extra, nwaves, kseg);
+        wave_ends_dump(WE_DC, "APK_DC_WAVE_ENDS_OUT", calls, nwaves, (nwaves + 7) / 8, head, s);
+      }
+    } dump_at_exit{(int)((int64_t)wpb_run * ((u0.nx3 + kseg - 1) / kseg) * u0.nblocks), kseg, plan.extra, s};
+#endif
     const int nseg = (u0.nx3 + kseg - 1) / kseg;
     ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 0, s);
     if (two_rows) {
@@ -1787,7 +1834,11 @@ inline bool launch_two_kernel(const PackView &u0, const PackView &u1, const Stag
       sp1.du_pitch = du_pitch;
       const int rpw = march_rows_per_wave(u0.nx1, u0.nx2);
       dim3 g3((u0.nx1 + 64 / rpw - 1) / (64 / rpw), (u0.nx2 + rpw - 1) / rpw, u0.nblocks);
-      const int nseg = march_segments((int64_t)g3.x * g3.y * g3.z, u0.nx3);
+      int nseg = march_segments((int64_t)g3.x * g3.y * g3.z, u0.nx3);
+#if APK_M12F_WAVE_ENDS
+      nseg = wave_ends_env("APK_X3_NSEG", nseg);
+      if (nseg > u0.nx3) nseg = u0.nx3;
+#endif
       g3.z *= nseg;
       ScopedTiming t(sp.ctx, stage_timing_slot(RECON) + 2, s);
       ok = as_constants([&](auto FC) {
@@ -1795,6 +1846,14 @@ inline bool launch_two_kernel(const PackView &u0, const PackView &u1, const Stag
           hipLaunchKernelGGL((fused_march_kernel<FLUID, RECON, RS, 3, false, EXTRA_NONE, (FC != 0)>), g3, dim3(64), lds, s, u0, u1, sp1, nseg, rpw);
         return x3_sweep_compiled(RECON, FC);
       }, among<0, 1>{plan.from_cons != 0});
+#if APK_M12F_WAVE_ENDS
+      {
+        static int calls = 0;
+        char head[160];
+        std::snprintf(head, sizeof head, "kernel x3 recon %d nwaves %d nseg %d", RECON, (int)(g3.x * g3.y * g3.z), nseg);
+        wave_ends_dump(WE_X3, "APK_X3_WAVE_ENDS_OUT", calls, (int)(g3.x * g3.y * g3.z), 0, head, s);
+      }
+#endif
     }
     if (sp.phase != 1) {
       StageParams sp2 = sp;
