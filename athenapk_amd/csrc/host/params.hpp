@@ -45,6 +45,7 @@ class ParameterInput {
     const std::string path = Trim(arg.substr(0, eq));
     if (path.find('/') == std::string::npos) throw std::runtime_error("override must be block/key=value: " + arg);
     values_[path] = Trim(arg.substr(eq + 1));
+    defaults_.erase(path);
   }
   // names of the blocks that start with `prefix` (e.g. "parthenon/output"), in deck order of
   // their names
@@ -65,6 +66,42 @@ class ParameterInput {
         return true;
     return false;
   }
+  // the deck as parsed with the overrides applied, every block and key, as deck text that LoadFromString reads back
+  // (blocks in the order of their names; a block without keys keeps its header).  What GetOrAdd* added as a default is
+  // left out: the reader adds it again, and a block that exists only through its defaults would read back as one the
+  // deck has -- which some options ask about (DoesBlockExist).
+  std::string Dump() const {
+    std::map<std::string, std::vector<std::pair<std::string, std::string>>> by_block;
+    for (const std::string &b : blocks_) by_block[b];
+    for (const auto &kv : values_) {
+      if (defaults_.count(kv.first)) continue;
+      const auto slash = kv.first.rfind('/');
+      by_block[kv.first.substr(0, slash)].emplace_back(kv.first.substr(slash + 1), kv.second);
+    }
+    std::string out;
+    for (const auto &b : by_block) {
+      out += "<" + b.first + ">\n";
+      for (const auto &kv : b.second) out += kv.first + " = " + kv.second + "\n";
+      out += "\n";
+    }
+    return out;
+  }
+  // the keys of one block, in the order of their names
+  std::vector<std::string> KeysOf(const std::string &block) const {
+    std::vector<std::string> out;
+    const std::string pre = block + "/";
+    for (auto it = values_.lower_bound(pre); it != values_.end() && it->first.compare(0, pre.size(), pre) == 0; ++it)
+      if (it->first.find('/', pre.size()) == std::string::npos) out.push_back(it->first.substr(pre.size()));
+    return out;
+  }
+  void Set(const std::string &block, const std::string &key, const std::string &value) {
+    values_[block + "/" + key] = value;
+    defaults_.erase(block + "/" + key);
+  }
+  void Erase(const std::string &block, const std::string &key) {
+    values_.erase(block + "/" + key);
+    defaults_.erase(block + "/" + key);
+  }
   bool DoesParameterExist(const std::string &block, const std::string &key) const {
     return values_.count(block + "/" + key) > 0;
   }
@@ -77,7 +114,10 @@ class ParameterInput {
   int GetInteger(const std::string &b, const std::string &k) const { return (int)ToInt(GetString(b, k), b, k); }
   bool GetBoolean(const std::string &b, const std::string &k) const { return ToBool(GetString(b, k), b, k); }
   std::string GetOrAddString(const std::string &b, const std::string &k, const std::string &def) {
-    if (!DoesParameterExist(b, k)) values_[b + "/" + k] = def;
+    if (!DoesParameterExist(b, k)) {
+      values_[b + "/" + k] = def;
+      defaults_.insert(b + "/" + k);
+    }
     return GetString(b, k);
   }
   double GetOrAddReal(const std::string &b, const std::string &k, double def) {
@@ -86,6 +126,7 @@ class ParameterInput {
       os.precision(17);
       os << def;
       values_[b + "/" + k] = os.str();
+      defaults_.insert(b + "/" + k);
       return def;
     }
     return GetReal(b, k);
@@ -93,6 +134,7 @@ class ParameterInput {
   int GetOrAddInteger(const std::string &b, const std::string &k, int def) {
     if (!DoesParameterExist(b, k)) {
       values_[b + "/" + k] = std::to_string(def);
+      defaults_.insert(b + "/" + k);
       return def;
     }
     return GetInteger(b, k);
@@ -100,6 +142,7 @@ class ParameterInput {
   bool GetOrAddBoolean(const std::string &b, const std::string &k, bool def) {
     if (!DoesParameterExist(b, k)) {
       values_[b + "/" + k] = def ? "true" : "false";
+      defaults_.insert(b + "/" + k);
       return def;
     }
     return GetBoolean(b, k);
@@ -132,6 +175,7 @@ class ParameterInput {
   }
   std::map<std::string, std::string> values_;
   std::set<std::string> blocks_;  // block headers seen in the deck
+  std::set<std::string> defaults_;  // block/key of the values GetOrAdd* added (not the deck's, not an override's)
 };
 
 }  // namespace apk

@@ -780,6 +780,7 @@ int create_common(const char *deck, const char *const *overrides, int noverrides
         throw std::runtime_error("Reflecting boundary conditions for MHD need special treatment.");
     tracers_initialize(s);  // <tracers> (after the hydro package, as the reference's Initialize order)
     snapshot_initialize(s);  // the npy output blocks (host/snapshot.cpp)
+    restart_initialize(s);   // the rst output blocks and what a restart refuses (host/restart.cpp)
   } catch (const std::exception &e) {
     if (errbuf && errlen) std::snprintf(errbuf, errlen, "%s", e.what());
     delete s;
@@ -1070,12 +1071,15 @@ int apk_sim_initialize(apk_sim *s) {
   SIM_TRY(s, estimate_timestep(s, &est));
   set_global_dt(s, est);
   SIM_TRY(s, tracers_seed_initial(s));  // SeedInitialTracers (UserWorkBeforeLoopMesh, tracers.cpp:87, 95-186)
+  s->initialized = true;
+  s->restored = false;
   return APK_OK;
 }
 
 int apk_sim_step(apk_sim *s) {
   if (!s || s->host_only) return APK_ERR_INVALID;
   s->err.clear();
+  s->initialized = true;
   if (s->time < s->tlim && (s->tlim - s->time) < s->dt) s->dt = s->tlim - s->time;
   SIM_TRY(s, pre_step(s));
   // diffusion/integrator = rkl2: a parabolic half step before and after the hyperbolic stages (hydro_driver.cpp:455-458,
@@ -1376,6 +1380,10 @@ int apk_sim_gather(apk_sim *s, int field, double *out) {
 
 int apk_sim_history(apk_sim *s, double *out8) {
   if (!s || s->host_only || !out8) return APK_ERR_INVALID;
+  // (relDivB differences B across the faces of a block: the ghost zones behind them must be those of the current state,
+  // which the stage loop does not keep where it reads neighbours directly -- else the column depends on when they were
+  // last filled, and a resumed run, whose ghost zones were filled at the dump, would not repeat it)
+  if (s->pkg.fluid == APK_FLUID_GLMMHD) SIM_TRY(s, sync_ghosts(s));
   SIM_TRY(s, apk_history(s->ctx, s->mu0(), s->pkg.fluid, out8, s->stream));
   if (s->have_comm && s->nranks > 1) {
     if (s->comm.allreduce_sum(s->comm.user, out8, 8) != 0) return fail(s, APK_ERR_DEVICE, "allreduce_sum failed");
@@ -1585,18 +1593,30 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     std::string path;
     double dt, next;
     int rows = 0;  // history rows written so far
+    std::string number;  // N of <parthenon/outputN>
   };
+  // a restored sim (apk_sim_restore) goes on where the dump was written: no initialisation, no row or dump for the restored
+  // time, files appended to, every output's next time and counter as the state file has them
+  const bool resumed = s->restored;
+  auto stored = [&](const std::string &number) -> const apk::OutputSchedule * {
+    for (const auto &o : s->restored_sched)
+      if (o.number == number) return &o;
+    return nullptr;
+  };
+  // (an output block the state file does not know, e.g. one an override added: from the next multiple of its dt on)
+  auto next_after = [&](double dt) { return dt * (std::floor(s->time / dt) + 1.0); };
   std::vector<HstOut> outs;
   try {
     const std::string base = s->pin.GetOrAddString("parthenon/job", "problem_id", "parthenon");
     for (const std::string &blk : s->pin.BlocksWithPrefix("parthenon/output")) {
       if (blk == "parthenon/output_defaults" || !s->pin.DoesParameterExist(blk, "file_type")) continue;
-      // npy: field snapshots, parsed at creation (host/snapshot.cpp: s->snap_outs); hdf5 / rst outputs are out of scope
+      // npy: field snapshots, rst: restart dumps, both parsed at creation (host/snapshot.cpp: s->snap_outs, host/restart.cpp:
+      // s->rst_outs); hdf5 outputs are out of scope
       if (s->pin.GetString(blk, "file_type") != "hst") continue;
       const std::string num = blk.substr(std::string("parthenon/output").size());
       const double out_dt = s->pin.GetReal(blk, "dt");
       if (!(out_dt > 0.0)) throw std::runtime_error("<" + blk + ">: dt must be positive for hst outputs");
-      outs.push_back({std::string(outdir) + "/" + base + ".out" + num + ".hst", out_dt, 0.0});
+      outs.push_back({std::string(outdir) + "/" + base + ".out" + num + ".hst", out_dt, 0.0, 0, num});
       if (s->pin.DoesParameterExist(blk, "data_format"))
         s->pin.ApplyOverride("parthenon/output_defaults/data_format=" + s->pin.GetString(blk, "data_format"));
     }
@@ -1620,14 +1640,14 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
   if (s->pkg.agn_triggering && s->trig_write_to_file) {
     s->trig_path = std::string(outdir) + "/" + s->trig_filename;
     if (s->rank == 0) {
-      FILE *f = std::fopen(s->trig_path.c_str(), "w");
+      FILE *f = std::fopen(s->trig_path.c_str(), resumed ? "a" : "w");
       if (!f) return fail(s, APK_ERR_INVALID, "cannot open " + s->trig_path);
       std::fclose(f);
     }
   }
-  SIM_TRY(s, apk_sim_initialize(s));
+  if (!resumed) SIM_TRY(s, apk_sim_initialize(s));
   // problem/cluster/hydrostatic_equilibrium/test_he_sphere: the reference writes the file when it builds the package
-  SIM_TRY(s, cluster_write_test_profile(s, std::string(outdir) + "/test_he_sphere.dat"));
+  if (!resumed) SIM_TRY(s, cluster_write_test_profile(s, std::string(outdir) + "/test_he_sphere.dat"));
   // the tracers next to every history row: <history file without .hst>.<row, 5 digits>.tracers.<field>.npy
   auto write_tracers = [&](HstOut &o) -> int {
     if (!s->tracers) return APK_OK;
@@ -1636,9 +1656,16 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     return tracers_write_outputs(s, o.path.substr(0, o.path.size() - 4) + "." + num + ".tracers");
   };
   for (auto &o : outs) {
+    if (resumed) {
+      const apk::OutputSchedule *st = stored(o.number);
+      o.next = st ? st->next : next_after(o.dt);
+      o.rows = st ? (int)st->counter : 0;
+      continue;
+    }
     if (s->rank == 0) std::remove(o.path.c_str());
     SIM_TRY(s, apk_sim_write_history(s, o.path.c_str()));
     SIM_TRY(s, write_tracers(o));
+    if (!s->tracers) o.rows += 1;  // (write_tracers counts them otherwise)
     o.next = o.dt;
   }
   // the field snapshots: <outdir>/<problem_id>.<id>.<NNNNN>, the cadence rule of the history outputs
@@ -1648,14 +1675,40 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     int dumps;
   };
   std::vector<SnapOut> snaps;
-  for (const auto &o : s->snap_outs) snaps.push_back({&o, o.dt, 0});
+  for (const auto &o : s->snap_outs) {
+    const apk::OutputSchedule *st = resumed ? stored(o.block.substr(std::string("parthenon/output").size())) : nullptr;
+    snaps.push_back({&o, st ? st->next : (resumed ? next_after(o.dt) : o.dt), st ? (int)st->counter : 0});
+  }
   auto write_snapshot = [&](SnapOut &so) -> int {
     char num[16];
     std::snprintf(num, sizeof num, "%05d", so.dumps++);
     const std::string base = s->pin.GetOrAddString("parthenon/job", "problem_id", "parthenon");
     return snapshot_write(s, std::string(outdir) + "/" + base + "." + so.o->id + "." + num, so.o->codes, so.o->names, so.o->single);
   };
-  for (auto &so : snaps) SIM_TRY(s, write_snapshot(so));
+  if (!resumed)
+    for (auto &so : snaps) SIM_TRY(s, write_snapshot(so));
+  // the restart dumps: <outdir>/<problem_id>.<id>.<NNNNN>.{rank<r>.npy, json, rst}, the same cadence rule; none at t = 0
+  struct RstOut {
+    const apk::RestartOutputBlock *o;
+    double next;
+    int dumps;
+  };
+  std::vector<RstOut> rsts;
+  for (const auto &o : s->rst_outs) {
+    const apk::OutputSchedule *st = resumed ? stored(o.number) : nullptr;
+    rsts.push_back({&o, st ? st->next : (resumed ? next_after(o.dt) : o.dt), st ? (int)st->counter : 0});
+  }
+  // what a dump stores of the outputs: where each of them stands once the cycle's outputs are written
+  struct SchedScope {
+    apk_sim *s;
+    ~SchedScope() { s->out_sched.clear(); }
+  } sched_scope{s};
+  auto publish_schedules = [&]() {
+    s->out_sched.clear();
+    for (const auto &o : outs) s->out_sched.push_back({o.number, o.next, (long long)o.rows});
+    for (const auto &so : snaps) s->out_sched.push_back({so.o->block.substr(std::string("parthenon/output").size()), so.next, (long long)so.dumps});
+    for (const auto &ro : rsts) s->out_sched.push_back({ro.o->number, ro.next, (long long)ro.dumps});
+  };
   int n = 0;
   // parthenon/time/perf_cycle_offset: cycles left out of the performance figure (first-touch
   // allocations, e.g. the flux-difference workspace and the spare prim buffer, happen there)
@@ -1664,7 +1717,8 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
   auto t0 = std::chrono::steady_clock::now();
   s->perf_cycles = 0;
   s->perf_zone_mark = s->zone_cycles;
-  while (s->time < s->tlim && (s->nlim < 0 || n < s->nlim)) {
+  const int done_before = resumed ? s->ncycle : 0;  // (nlim bounds the run's cycle number, as Parthenon's does)
+  while (s->time < s->tlim && (s->nlim < 0 || done_before + n < s->nlim)) {
     if (n == perf_offset && n > 0) {
       SIM_HIP(s, hipStreamSynchronize(hs(s)));
       t0 = std::chrono::steady_clock::now();
@@ -1673,11 +1727,12 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
     SIM_TRY(s, apk_sim_step(s));
     ++n;
     if (n > perf_offset) s->perf_cycles += 1;
-    const bool last = !(s->time < s->tlim && (s->nlim < 0 || n < s->nlim));
+    const bool last = !(s->time < s->tlim && (s->nlim < 0 || done_before + n < s->nlim));
     for (auto &o : outs)
       if (s->time >= o.next || last) {
         SIM_TRY(s, apk_sim_write_history(s, o.path.c_str()));
         SIM_TRY(s, write_tracers(o));
+        if (!s->tracers) o.rows += 1;
         while (o.next <= s->time) o.next += o.dt;
       }
     for (auto &so : snaps)
@@ -1685,6 +1740,21 @@ int apk_sim_execute(apk_sim *s, const char *outdir, int *ncycles) {
         SIM_TRY(s, write_snapshot(so));
         while (so.next <= s->time) so.next += so.o->dt;
       }
+    // every rst output that fires this cycle is counted and advanced before any of them is written: each dump then says
+    // where ALL outputs stand after this cycle, and a run resumed from either numbers the next dumps as this one does
+    std::vector<std::pair<const RstOut *, int>> firing;
+    for (auto &ro : rsts)
+      if (s->time >= ro.next || last) {
+        firing.emplace_back(&ro, ro.dumps++);
+        while (ro.next <= s->time) ro.next += ro.o->dt;
+      }
+    if (!firing.empty()) publish_schedules();
+    for (const auto &fr : firing) {
+      char num[16];
+      std::snprintf(num, sizeof num, "%05d", fr.second);
+      const std::string base = s->pin.GetOrAddString("parthenon/job", "problem_id", "parthenon");
+      SIM_TRY(s, restart_write(s, std::string(outdir) + "/" + base + "." + fr.first->o->id + "." + num));
+    }
   }
   SIM_TRY(s, sync_ghosts(s));
   SIM_HIP(s, hipStreamSynchronize(hs(s)));

@@ -173,6 +173,19 @@ struct SnapshotOutput {
   std::vector<std::string> names;  // their canonical names
 };
 
+// one <parthenon/outputN> block with file_type = rst (host/restart.cpp): a restart output
+struct RestartOutputBlock {
+  std::string block, number, id;  // the deck block, its N and the id of the file names (default out<N>)
+  double dt = 0.0;
+};
+
+// where one output of apk_sim_execute stands: the block's N, the next output time and the files (rows, for hst) so far
+struct OutputSchedule {
+  std::string number;
+  double next = 0.0;
+  long long counter = 0;
+};
+
 }  // namespace apk
 
 namespace apk {
@@ -444,6 +457,11 @@ struct apk_sim {
   double *d_snap = nullptr;
   void *h_snap = nullptr;  // pinned (hipHostMalloc)
   size_t snap_dev_cap = 0, snap_host_cap = 0;
+  // restart (host/restart.cpp): the deck's rst outputs; the schedules of apk_sim_execute's outputs while it runs (what a
+  // dump stores) and those a state file brought; whether the state was set by apk_sim_initialize or apk_sim_restore
+  std::vector<apk::RestartOutputBlock> rst_outs;
+  std::vector<apk::OutputSchedule> out_sched, restored_sched;
+  bool initialized = false, restored = false;
   int sts_last_s = 0;           // sub-stages of the last half step taken
   double sts_last_ratio = 0.0;  // its 2 tau / dt_diff
   long long overlapped = 0;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "sim.hpp"
+#include "snapshot_format.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -129,6 +130,10 @@ void snapshot_initialize(apk_sim *s);  // the npy output blocks and apk_amd/snap
 int snapshot_write(apk_sim *s, const std::string &prefix, const std::vector<int> &codes, const std::vector<std::string> &names,
                    bool single);       // one dump: <prefix>.rank<r>.npy on every rank, <prefix>.json on rank 0
 void snapshot_free(apk_sim *s);
+void snapshot_block_table(const apk_sim *s, std::vector<SnapshotBlock> &blocks);  // rank and position in its file of every global block
+int snapshot_staging(apk_sim *s, size_t bytes);  // the two staging buffers, at least `bytes` each
+void restart_initialize(apk_sim *s);  // the rst output blocks, the refusals and a state block's own checks (host/restart.cpp), at creation
+int restart_write(apk_sim *s, const std::string &prefix);  // one dump: the cons snapshot, then <prefix>.rst on rank 0
 double xc(const apk_sim *s, const double x0[3], int d, int idx);
 void block_origin(const apk_sim *s, int lb, double x0[3]);
 void lw_eigensystem(double gm1, double v1, double v2, double v3, double h, double ev[5], double rem[5][5]);

@@ -778,8 +778,6 @@ void turbulence_setup(apk_sim *s) {
   if (!(m.nx[0] == m.nx[1] && m.nx[1] == m.nx[2] && L[0] == L[1] && L[1] == L[2]))
     throw std::runtime_error("FMFT has only been tested with cubic meshes and constant dx/dy/dz. "
                              "Remove this warning at your own risk.");
-  if (pin.DoesParameterExist("problem/turbulence", "accel_hat_0_0_r"))
-    throw std::runtime_error("restarting the turbulence driver state is not supported");
   if (s->pkg.fluid == APK_FLUID_GLMMHD) {
     const int b_config = pin.GetInteger("problem/turbulence", "b_config");
     if (b_config == 3) throw std::runtime_error("Random B fields not implemented yet.");
@@ -788,6 +786,18 @@ void turbulence_setup(apk_sim *s) {
   }
   const int gnx[3] = {m.nx[0], m.nx[1], m.nx[2]};
   s->fmft = std::make_unique<FewModesFT>(num_modes, std::move(k_vec), k_peak, sol_weight, t_corr, rseed, gnx);
+  // the restart parameters (turbulence.cpp:166-197): a deck that is a state file carries the spectral state and the RNG
+  if (pin.DoesParameterExist("problem/turbulence", "state_rng")) {
+    std::vector<double> hat(6 * (size_t)num_modes);
+    for (int i = 0; i < 3; ++i)
+      for (int m = 0; m < num_modes; ++m) {
+        const std::string key = "accel_hat_" + std::to_string(i) + "_" + std::to_string(m);
+        hat[((size_t)i * num_modes + m) * 2] = pin.GetReal("problem/turbulence", key + "_r");
+        hat[((size_t)i * num_modes + m) * 2 + 1] = pin.GetReal("problem/turbulence", key + "_i");
+      }
+    if (!s->fmft->RestoreState(hat, pin.GetString("problem/turbulence", "state_rng"), pin.GetString("problem/turbulence", "state_dist")))
+      throw std::runtime_error("problem/turbulence/state_rng or state_dist does not parse");
+  }
 }
 
 // turbulence::ProblemGenerator (src/pgen/turbulence.cpp:217-370): a MeshData-wide generator --

@@ -13,6 +13,40 @@
 namespace apk {
 namespace host {
 
+// position of every global block in its rank's file: Morton order within a rank on uniform meshes (mesh.hpp: Build), the
+// Z-ordered leaf list itself on refined ones
+void snapshot_block_table(const apk_sim *s, std::vector<SnapshotBlock> &blocks) {
+  const Mesh &m = s->mesh;
+  const int nb = m.nblocks_total;
+  blocks.assign(nb, SnapshotBlock());
+  std::vector<int> order(nb);
+  for (int g = 0; g < nb; ++g) order[g] = g;
+  if (!s->amr) {
+    std::vector<uint64_t> key(nb);
+    for (int g = 0; g < nb; ++g) {
+      int bc[3];
+      m.Loc(g, bc);
+      key[g] = Mesh::Morton(bc[0], bc[1], bc[2]);
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
+  }
+  std::vector<int> count(s->nranks, 0);
+  for (int p = 0; p < nb; ++p) {
+    const int g = order[p];
+    SnapshotBlock &b = blocks[g];
+    b.gid = g;
+    b.rank = m.gid_rank[g];
+    b.index = count[b.rank]++;
+    if (s->amr) {
+      const AmrLeaf &leaf = s->amr->leaves[g];
+      b.level = leaf.level;
+      for (int d = 0; d < 3; ++d) b.lx[d] = leaf.lx[d];
+    } else {
+      m.Loc(g, b.lx);
+    }
+  }
+}
+
 namespace {
 
 const char *kConsNames[9] = {"rho", "mom1", "mom2", "mom3", "etot", "B1", "B2", "B3", "psi"};
@@ -163,8 +197,6 @@ int snapshot_chunks(apk_sim *s, const std::vector<int> &codes, bool single, Sink
   return APK_OK;
 }
 
-// position of every global block in its rank's file: Morton order within a rank on uniform meshes (mesh.hpp: Build), the
-// Z-ordered leaf list itself on refined ones
 void build_index(const apk_sim *s, const std::vector<std::string> &names, bool single, SnapshotIndex &ix) {
   const Mesh &m = s->mesh;
   ix.time = s->host_only ? 0.0 : s->time;
@@ -183,37 +215,12 @@ void build_index(const apk_sim *s, const std::vector<std::string> &names, bool s
   }
   ix.nghost = m.ng;
   ix.nranks = s->nranks;
-  const int nb = m.nblocks_total;
-  ix.blocks.resize(nb);
-  std::vector<int> order(nb);
-  for (int g = 0; g < nb; ++g) order[g] = g;
-  if (!s->amr) {
-    std::vector<uint64_t> key(nb);
-    for (int g = 0; g < nb; ++g) {
-      int bc[3];
-      m.Loc(g, bc);
-      key[g] = Mesh::Morton(bc[0], bc[1], bc[2]);
-    }
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-  }
-  std::vector<int> count(s->nranks, 0);
-  for (int p = 0; p < nb; ++p) {
-    const int g = order[p];
-    SnapshotBlock &b = ix.blocks[g];
-    b.gid = g;
-    b.rank = m.gid_rank[g];
-    b.index = count[b.rank]++;
-    if (s->amr) {
-      const AmrLeaf &leaf = s->amr->leaves[g];
-      b.level = leaf.level;
-      for (int d = 0; d < 3; ++d) b.lx[d] = leaf.lx[d];
-    } else {
-      m.Loc(g, b.lx);
-    }
-  }
+  snapshot_block_table(s, ix.blocks);
 }
 
 }  // namespace
+
+int snapshot_staging(apk_sim *s, size_t bytes) { return ensure_staging(s, bytes); }
 
 void snapshot_initialize(apk_sim *s) {
   ParameterInput &pin = s->pin;
@@ -223,7 +230,7 @@ void snapshot_initialize(apk_sim *s) {
   s->snap_outs.clear();
   for (const std::string &blk : pin.BlocksWithPrefix("parthenon/output")) {
     if (blk == "parthenon/output_defaults" || !pin.DoesParameterExist(blk, "file_type")) continue;
-    if (pin.GetString(blk, "file_type") != "npy") continue;  // hst: apk_sim_execute; hdf5 / rst: ignored
+    if (pin.GetString(blk, "file_type") != "npy") continue;  // hst: apk_sim_execute; rst: host/restart.cpp; hdf5: ignored
     SnapshotOutput o;
     o.block = blk;
     const std::string num = blk.substr(std::string("parthenon/output").size());

@@ -12,7 +12,9 @@
 #include <complex>
 #include <cstdint>
 #include <random>
+#include <sstream>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 namespace apk {
@@ -41,6 +43,33 @@ class FewModesFT {
   std::vector<Complex> &var_hat() { return hat_; }
   std::mt19937 &rng() { return rng_; }
   std::uniform_real_distribution<> &dist() { return dist_; }
+
+  // What a restart keeps (src/pgen/turbulence.cpp:166-197: the restart parameters accel_hat_<i>_<m>_r / _i, state_rng and
+  // state_dist): the spectral state as [3][M][re, im] and the operator<< text of the generator and of the distribution.
+  void SaveState(std::vector<double> &hat, std::string &state_rng, std::string &state_dist) const {
+    hat.resize(hat_.size() * 2);
+    for (size_t q = 0; q < hat_.size(); ++q) hat[2 * q] = hat_[q].real(), hat[2 * q + 1] = hat_[q].imag();
+    std::ostringstream r, d;
+    r << rng_;
+    d.precision(17);
+    d << dist_;
+    state_rng = r.str();
+    state_dist = d.str();
+  }
+  // false (and nothing changed) if a text does not parse or the spectral state has another size
+  bool RestoreState(const std::vector<double> &hat, const std::string &state_rng, const std::string &state_dist) {
+    if (hat.size() != hat_.size() * 2) return false;
+    std::mt19937 rng;
+    std::uniform_real_distribution<> dist;
+    std::istringstream r(state_rng), d(state_dist);
+    r >> rng;
+    d >> dist;
+    if (r.fail() || d.fail()) return false;
+    rng_ = rng;
+    dist_ = dist;
+    for (size_t q = 0; q < hat_.size(); ++q) hat_[q] = Complex(hat[2 * q], hat[2 * q + 1]);
+    return true;
+  }
 
   // phase table of one axis for n interior cells starting at global index g0 on a gn-cell axis:
   // out(re|im, m, idx) = exp(i * 2 pi k_axis(m) / gn * ((idx + g0) mod gn)), the k_x = 0 modes

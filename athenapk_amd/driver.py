@@ -271,6 +271,23 @@ class _SnapshotHost:
                                                                    int(bool(single))))
 
 
+class _RestartHost:
+    """Restart (include/apk_host.h): what needs no device state; works on host-only sims too."""
+
+    def restart_outputs(self):
+        """the deck's rst output blocks as parsed: [{"number", "id", "dt"}]"""
+        size = C.c_int(0)
+        self._snapshot_check(self.lib.apk_sim_restart_outputs(self.h, None, 0, C.byref(size)))
+        out = (L.RestartOutputInfo * max(size.value, 1))()
+        self._snapshot_check(self.lib.apk_sim_restart_outputs(self.h, out, size.value, C.byref(size)))
+        return [{"number": o.number, "id": o.id.decode(), "dt": o.dt} for o in out[:size.value]]
+
+    def write_restart(self, prefix):
+        """one restart dump: <prefix>.rank<r>.npy on every rank, <prefix>.json and, last, <prefix>.rst on rank 0 (a
+        host-only sim: the state file alone).  Leaves the run alone bit for bit.  Call it on every rank."""
+        self._snapshot_check(self.lib.apk_sim_write_restart(self.h, str(prefix).encode()))
+
+
 class _MeshView:
     """Block placement and ghost-exchange plans of a sim handle (valid without a GPU)."""
 
@@ -354,7 +371,7 @@ class _MeshView:
         return self.info
 
 
-class Simulation(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
+class Simulation(_FmftHost, _ClusterHost, _SnapshotHost, _RestartHost, _MeshView):
     """apk_sim: deck + overrides -> mesh partition, packs, ghost plans, stage loop (C++).
 
     COLLECTIVE accessors on N > 1 ranks: read_block / write_block / gather / history / turbulence_history / reldivb and
@@ -631,6 +648,14 @@ class Simulation(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
         self._check(self.lib.apk_sim_initialize(self.h))
         return self
 
+    def restore(self, path):
+        """in place of initialize(), on a Simulation built from restart.deck(path): the state of the dump behind the state
+        file `path` (<prefix>.rst).  Collective on N > 1 ranks.  On refined meshes the block list may change: info is
+        refreshed."""
+        self._check(self.lib.apk_sim_restore(self.h, str(path).encode()))
+        self.refresh_info()
+        return self
+
     def step(self):
         self._check(self.lib.apk_sim_step(self.h))
 
@@ -733,7 +758,8 @@ class Simulation(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
         self._check(self.lib.apk_sim_write_linear_wave_errors(self.h, str(path).encode()))
 
     def execute(self, outdir):
-        """initialize + main loop + the deck's hst and npy (field snapshot) outputs + the linear-wave error file"""
+        """initialize + main loop + the deck's hst, npy (field snapshot) and rst (restart) outputs + the linear-wave error
+        file; after restore(): no initialisation, the outputs go on where the state file says they stood"""
         n = C.c_int(0)
         self._check(self.lib.apk_sim_execute(self.h, str(outdir).encode(), C.byref(n)))
         return n.value
@@ -1021,7 +1047,7 @@ def _tracers_read(lib, h, names):
     return {name: raw[name][order] for name in raw}
 
 
-class HostPlan(_FmftHost, _ClusterHost, _SnapshotHost, _MeshView):
+class HostPlan(_FmftHost, _ClusterHost, _SnapshotHost, _RestartHost, _MeshView):
     """Host-only view of a rank's mesh partition and ghost-exchange plan (no GPU needed)."""
 
     def __init__(self, deck, overrides=(), rank=0, nranks=1, strict=False):

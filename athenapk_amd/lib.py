@@ -390,6 +390,11 @@ class SnapshotOutputInfo(C.Structure):
                 ("components", C.c_char * 1024)]
 
 
+class RestartOutputInfo(C.Structure):
+    """apk_restart_output_info: one rst output block of the deck as parsed"""
+    _fields_ = [("number", C.c_int), ("dt", C.c_double), ("id", C.c_char * 64)]
+
+
 class AmrOpInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("level", C.c_int), ("src_kind", C.c_int), ("src_block", C.c_int),
                 ("dst_kind", C.c_int), ("dst_block", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3),
@@ -503,6 +508,7 @@ def _signatures():
         "apk_tracers_lookback": (i, [vp, C.POINTER(TracerArrays), ll, d, vp, ll, vp, vp]),
         "apk_tracers_step_fused_lookback": (i, [vp, vp, C.POINTER(TracerArrays), C.POINTER(TracerGeom), d, vp, ll, vp, ll, vp, vp]),
         "apk_output_pack": (i, [vp, vp, i, E, C.POINTER(OutputDesc), i, i, vp, vp]),
+        "apk_restart_unpack": (i, [vp, vp, i, i, vp, vp]),
         "apk_kernel_timing_enable": (i, [vp, i]),
         "apk_kernel_timing_read": (i, [vp, i, c_dp, C.POINTER(ll)]),
         # apk_host.h
@@ -630,6 +636,9 @@ def _signatures():
         "apk_sim_snapshot_read": (i, [vp, C.c_char_p, i, vp, C.c_size_t]),
         "apk_sim_write_snapshot": (i, [vp, C.c_char_p, C.c_char_p, i]),
         "apk_sim_write_snapshot_index": (i, [vp, C.c_char_p, C.c_char_p, i]),
+        "apk_sim_restart_outputs": (i, [vp, C.POINTER(RestartOutputInfo), i, C.POINTER(i)]),
+        "apk_sim_write_restart": (i, [vp, C.c_char_p]),
+        "apk_sim_restore": (i, [vp, C.c_char_p]),
     }
 
 

@@ -1099,6 +1099,12 @@ typedef struct apk_output_desc {
 int apk_output_pack(apk_ctx *ctx, const apk_pack *md, int fluid, const apk_eos *eos, const apk_output_desc *desc, int first,
                     int n, void *out, apk_stream_t stream);
 
+/* The inverse of apk_output_pack for the conserved variables (restart files, csrc/host/restart.cpp).  `in`: DEVICE memory
+ * [n][nhydro + nscalars][nx3][nx2][nx1], dense, interior cells, double; it goes into the interior of `cons` of blocks
+ * [first, first + n).  One lane per interior cell, the variable loop inside the lane.  Ghost zones, row padding and prim
+ * are never written.  Honours apk_pack_desc.stride; 1-D, 2-D and 3-D blocks.  Does not synchronise. */
+int apk_restart_unpack(apk_ctx *ctx, const apk_pack *md, int first, int n, const double *in, apk_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the caller's stream) ------------------------
  * bench.py needs the average duration of individual kernels measured live on the stream
  * they are launched on.  When enabled, every kernel launch of the listed groups is

@@ -471,7 +471,10 @@ int apk_sim_gather(apk_sim *sim, int field, double *host_out);
  * outputs of apk_sim_execute are).  On uniform meshes it is local. */
 int apk_sim_read_block(apk_sim *sim, int lb, int field, double *host_out);
 int apk_sim_write_block(apk_sim *sim, int lb, int field, const double *host_in);
-/* history sums over the whole mesh (allreduce'd): mass,1-mom,2-mom,3-mom,KE,tot-E,ME,relDivB */
+/* history sums over the whole mesh (allreduce'd): mass,1-mom,2-mom,3-mom,KE,tot-E,ME,relDivB.  GLM-MHD: relDivB
+ * differences B across block faces, so the ghost zones are brought up to date first, as by the block accessors (and the
+ * primitives stored, where the last cycle kept them out of memory): the column is that of the current state whatever the
+ * stage loop left stale, and the call is collective where that completion is. */
 int apk_sim_history(apk_sim *sim, double *out8);
 /* linear-wave L1 errors vs the initial condition (src/pgen/linear_wave.cpp:183-335) */
 /* few-modes turbulence driver (job/problem_id = turbulence).  History: volume sums of Ms, Ma,
@@ -511,7 +514,11 @@ int apk_sim_write_linear_wave_errors(apk_sim *sim, const char *path);
  * tlim / nlim, write every <parthenon/output*> block with file_type = hst to
  * <outdir>/<parthenon/job problem_id, default "parthenon">.out<N>.hst at its `dt` cadence (t = 0
  * and the final time included), every block with file_type = npy as field snapshots (below) at the same
- * cadence rule, and, for linear_wave with compute_error, the error file. */
+ * cadence rule (a GLM-MHD history row completes the ghost zones first, see apk_sim_history), every block with
+ * file_type = rst as restart dumps (below; none at t = 0), and, for linear_wave with
+ * compute_error, the error file.  On a sim restored with apk_sim_restore it does not initialise, writes no row or dump for
+ * the restored time, appends to the history files and the triggering file, takes every output's next time and counter
+ * from the state file, and counts nlim from the run's cycle number. */
 int apk_sim_execute(apk_sim *sim, const char *outdir, int *ncycles);
 
 /* ---- field snapshots (csrc/host/snapshot.cpp, csrc/host/snapshot_format.cpp, csrc/kernels_output.hip) -----------------
@@ -522,7 +529,7 @@ int apk_sim_execute(apk_sim *sim, const char *outdir, int *ncycles);
  * (apk_output_component in apk_amd.h; with every problem generator, where the reference has them for the cluster only).
  * Duplicates collapse, order is kept.  Refused at creation with a message naming block and key: an unknown entry, an MHD
  * component or MHD-only field with hydro/fluid = euler, temperature without <units> and hydro/He_mass_fraction, a scalar
- * index >= nscalars, dt <= 0, an empty list.  hdf5 and rst blocks stay ignored; restart is not part of this.
+ * index >= nscalars, dt <= 0, an empty list.  hdf5 blocks stay ignored; rst blocks are restart outputs (below).
  * A dump is <prefix>.rank<r>.npy on every rank -- NumPy format 1.0, shape (nblocks_local, ncomp, nx3, nx2, nx1) of the
  * meshblock, interior cells, '<f8' or '<f4', blocks in local order -- and <prefix>.json on rank 0: time, cycle, dt,
  * components, dtype, fluid, gamma, nscalars, xmin, xmax, mesh_nx, block_nx, nghost, nranks and blocks (gid, level, lx1,
@@ -553,6 +560,54 @@ int apk_sim_snapshot_read(apk_sim *sim, const char *variables, int single, void 
 int apk_sim_write_snapshot(apk_sim *sim, const char *prefix, const char *variables, int single);
 /* the JSON index alone, to `path`, with the sim's time, cycle and dt (a host-only sim: time 0, cycle 0) */
 int apk_sim_write_snapshot_index(apk_sim *sim, const char *path, const char *variables, int single);
+/* ---- restart (csrc/host/restart.cpp, csrc/host/restart_format.cpp, csrc/kernels_output.hip) ---------------------------
+ * A <parthenon/outputN> block with file_type = rst: dt (> 0; missing or <= 0 is refused at creation naming block and key),
+ * id (default out<N>).  apk_sim_execute writes <outdir>/<problem_id>.<id>.<NNNNN> at the cadence rule of the other
+ * outputs and on the last cycle, not at t = 0.
+ * A dump is the conserved state as a field snapshot of `cons` in double (<prefix>.rank<r>.npy on every rank,
+ * <prefix>.json on rank 0: athenapk_amd.snapshots.load reads it) and the state file <prefix>.rst, which rank 0 writes
+ * last -- to a temporary name, then renamed; with several ranks after a reduction all ranks take part in -- so that its
+ * presence says the dump is complete.  The state file is text in the deck format: the deck as parsed with the overrides
+ * applied, every block and key, plus the block <apk_amd/restart> -- format_version, time, cycle, dt, the package's dt_hyp,
+ * mindx, c_h and dt_diff, the counters fofc_total, fofc_fallback_stages, zone_cycles, amr_refined and amr_derefined,
+ * nranks, nblocks, fluid, nvar, nghost, refinement, mesh_nx, block_nx, one key block_<gid> = level lx1 lx2 lx3 deref_count
+ * rank index per global block, the cluster problem's reduced quantities of AGN triggering with trig_rate, trig_time,
+ * trig_dt and the five split_totals, and output<N>_next_time / output<N>_counter per hst, npy and rst block while
+ * apk_sim_execute runs -- doubles as %.17g.  problem_id = turbulence adds accel_hat_<i>_<m>_r / _i, state_rng and
+ * state_dist to <problem/turbulence> (the reference's restart parameters, src/pgen/turbulence.cpp:166-197); a deck that
+ * carries them starts its driver from them.  Writing reads the interior of the current conserved state and changes
+ * nothing: a run that writes dumps computes what one that does not computes, bit for bit.
+ * apk_sim_restore takes the place of apk_sim_initialize on a sim created from the state file's text (which is a deck): it
+ * checks mesh, meshblock, nghost, fluid, number of variables and refinement mode against the sim, installs the forest with
+ * its derefinement counters on adaptive meshes (static forests are rebuilt from the deck and checked), moves the blocks
+ * from whichever rank files hold them -- looked up by level and logical location, so a dump written on R ranks restores
+ * on any number -- through the snapshots' pinned and device staging buffers (apk_amd/snapshot_staging_mb) into
+ * apk_restart_unpack, sets the scalars and the turbulence driver, and runs the ghost exchange and FillDerived.  No time
+ * step is estimated: dt, dt_hyp, mindx and c_h are the stored ones.  In the parity build the resumed run equals the
+ * uninterrupted one bit for bit; in the product build it equals the uninterrupted run that calls apk_sim_exchange_ghosts
+ * and apk_sim_fill_derived right after the dump (stage forms that derive primitives from the conserved state contract
+ * differently from those that read stored ones).
+ * Refused with a message naming the key: an rst block, apk_sim_write_restart or apk_sim_restore with tracers/enabled = true
+ * (tracer arrays and lookback histories are not stored); a state file of another format_version; a deck that is a state
+ * file with overrides that change mesh, meshblock, nghost, fluid, nscalars or refinement mode (at creation); restore on a
+ * sim that has been initialised, stepped or restored.  A failed restore leaves a message and the process running.  Every
+ * rank file the block table names is opened and checked (header, shape, size) on every rank before anything of the sim
+ * changes: a restore refused for one of the reasons above, or for a missing, foreign or truncated file, leaves a sim that
+ * may still be initialised or restored from another dump.  One that fails later (a block table that is no balanced
+ * forest, a read error, a device error) leaves a sim to destroy.  apk_sim_write_restart reduces its status over the ranks:
+ * if one rank cannot write its array, no state file is written and every rank reports the failure. */
+typedef struct apk_restart_output_info {
+  int number; /* N of <parthenon/outputN> */
+  double dt;
+  char id[64];
+} apk_restart_output_info;
+/* the deck's rst outputs as parsed: copies min(n, size) entries, *size = their number.  Works on a host-only sim. */
+int apk_sim_restart_outputs(const apk_sim *sim, apk_restart_output_info *out, int n, int *size);
+/* one dump to <prefix>.rank<r>.npy, <prefix>.json and <prefix>.rst.  Every rank calls it.  On a host-only sim: the state
+ * file alone (time 0, cycle 0). */
+int apk_sim_write_restart(apk_sim *sim, const char *prefix);
+/* the state of the dump behind <prefix>.rst into a new sim, in place of apk_sim_initialize.  Every rank calls it. */
+int apk_sim_restore(apk_sim *sim, const char *rst_path);
 /* wall seconds of the main loop of the last apk_sim_execute (initialisation excluded, device
  * synchronised): zones * cycles / this = Parthenon's "zone-cycles/wallsecond" */
 double apk_sim_loop_seconds(const apk_sim *sim);
