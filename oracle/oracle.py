@@ -80,6 +80,8 @@ def build(fast=False, force=False):
 
 REF_DIR = os.path.join(_HERE, "_ref")
 REF_BIN = os.path.join(REF_DIR, "ref_vectors")
+REF_PHYSICS_BIN = os.path.join(REF_DIR, "ref_physics")
+REF_BINS = {"ref_vectors": REF_BIN, "ref_physics": REF_PHYSICS_BIN}
 REF_SRC_DEFAULT = "/root/reference"
 
 
@@ -89,40 +91,52 @@ def reference_tree():
     return root if os.path.isfile(os.path.join(root, "src", "hydro", "rsolvers", "rsolvers.hpp")) else None
 
 
-def build_ref(force=False):
-    """Compile oracle/_ref/ref_vectors (the reference's own header-only arithmetic against the stand-in names of
-    oracle/ref/standin, recipe oracle/ref/Makefile).  Returns its path, or None when the reference tree is absent.
-    The binary is ignored by git and is never built from anything but the tree it was given."""
+def _ref_sources(recipe):
+    """what the two binaries are compiled from on this side: the drivers, the recipe and every stand-in header"""
+    srcs = [os.path.join(recipe, f) for f in ("ref_vectors.cpp", "ref_physics.cpp", "Makefile")]
+    for d, _, files in os.walk(os.path.join(recipe, "standin")):
+        srcs += [os.path.join(d, f) for f in sorted(files) if f.endswith(".hpp")]
+    return srcs
+
+
+def build_ref(force=False, which="ref_vectors"):
+    """Compile oracle/_ref/ref_vectors and oracle/_ref/ref_physics (the reference's own header-only arithmetic against
+    the stand-in names of oracle/ref/standin, recipe oracle/ref/Makefile).  Returns the path of the binary `which`, or
+    None when the reference tree is absent.  The binaries are ignored by git and are never built from anything but the
+    tree they were given."""
     root = reference_tree()
     if root is None:
         return None
     recipe = os.path.join(_HERE, "ref")
-    srcs = [os.path.join(recipe, f) for f in ("ref_vectors.cpp", "Makefile", os.path.join("standin", "apk_standin.hpp"))]
-    stale = (not os.path.exists(REF_BIN)) or any(os.path.getmtime(s) > os.path.getmtime(REF_BIN) for s in srcs)
+    srcs = _ref_sources(recipe)
+    stale = any((not os.path.exists(b)) or any(os.path.getmtime(s) > os.path.getmtime(b) for s in srcs)
+                for b in REF_BINS.values())
     if force or stale:
         cmd = ["make", "-C", recipe, "-s", "APK_REFERENCE_SRC=" + root]
         subprocess.run(cmd + (["-B"] if force else []), check=True, stdout=subprocess.DEVNULL)
-    return REF_BIN
+    return REF_BINS[which]
 
 
-def ref_binary():
-    """path of an already built oracle/_ref/ref_vectors (it travels with the tree to machines that lack the
-    reference), or None"""
-    return REF_BIN if os.path.isfile(REF_BIN) and os.access(REF_BIN, os.X_OK) else None
+def ref_binary(which="ref_vectors"):
+    """path of an already built oracle/_ref/<which> (it travels with the tree to machines that lack the reference), or
+    None"""
+    path = REF_BINS[which]
+    return path if os.path.isfile(path) and os.access(path, os.X_OK) else None
 
 
-def ref_run(args, *arrays, path=None):
-    """Pipe fp64 arrays through the reference binary in a child process; returns its output as a flat fp64 array.
-    args: the subcommand and its arguments (oracle/ref/ref_vectors.cpp); floats are passed with 17 digits."""
-    path = path or ref_binary()
+def ref_run(args, *arrays, path=None, which="ref_vectors", text=False):
+    """Pipe fp64 arrays through a reference binary in a child process; returns its output as a flat fp64 array (text:
+    as a string).  args: the subcommand and its arguments (oracle/ref/ref_vectors.cpp, ref_physics.cpp); floats are
+    passed with 17 digits."""
+    path = path or ref_binary(which)
     if path is None:
-        raise FileNotFoundError("oracle/_ref/ref_vectors is not built (oracle.build_ref())")
+        raise FileNotFoundError("oracle/_ref/%s is not built (oracle.build_ref())" % which)
     argv = [path] + [repr(float(a)) if isinstance(a, float) else str(a) for a in args]
     data = b"".join(np.ascontiguousarray(a, dtype="<f8").tobytes() for a in arrays)
     r = subprocess.run(argv, input=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     if r.returncode != 0:
-        raise RuntimeError("ref_vectors %s: exit %d: %s" % (" ".join(argv[1:]), r.returncode, r.stderr.decode()[-500:]))
-    return np.frombuffer(r.stdout, dtype="<f8").astype(np.float64)
+        raise RuntimeError("%s %s: exit %d: %s" % (os.path.basename(path), " ".join(argv[1:]), r.returncode, r.stderr.decode()[-500:]))
+    return r.stdout.decode() if text else np.frombuffer(r.stdout, dtype="<f8").astype(np.float64)
 
 
 def _declare(lib):

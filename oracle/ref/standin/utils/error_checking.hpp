@@ -1,0 +1,1 @@
+#include "../apk_standin_physics.hpp" // forwarding file: see apk_standin_physics.hpp

@@ -155,6 +155,15 @@ def _rk45(h, y0, f):
 STEPPERS = {"rk12": (_rk12, 2), "rk45": (_rk45, 5)}
 
 
+def optimal_step(order, h, err, tol):
+    """RK12Stepper / RK45Stepper::OptimalStep.  pow(tol / err, 2) is the correctly rounded square: compiled from the
+    reference's own header (oracle/ref, g++ -O2) a pow with the constant exponent 2 is the product, which is also what the
+    product build's kernel writes, while libm's pow, which math.pow calls, is one ulp off it on about one ratio in a
+    thousand (tests/test_reference_physics.py holds this function to the compiled header).  The fifth power stays libm's."""
+    r = tol / err
+    return 0.95 * h * (r * r if order == 2 else math.pow(r, order))
+
+
 EVENTS = ("reject", "clamp_min", "accept_over_tol", "invalid_retry", "to_floor", "err_zero", "grow", "end_at_floor")
 
 
@@ -172,7 +181,7 @@ def subcycle_cell(T, integrator, rho, e0, dt, counts=None, events=None):
     end_at_floor   a cell whose final energy is clamped to the floor)"""
     step, order = STEPPERS[integrator]
     f = lambda e: T.dedt(e, rho)  # noqa: E731
-    opt = lambda h, err, tol: 0.95 * h * math.pow(tol / err, order)  # noqa: E731
+    opt = lambda h, err, tol: optimal_step(order, h, err, tol)  # noqa: E731
     max_iter, d_e_tol, floor = T.max_iter, T.d_e_tol, T.e_floor_sub
     min_sub_dt = dt / max_iter
 
