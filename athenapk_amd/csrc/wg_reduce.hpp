@@ -6,10 +6,15 @@
 // and flat 256: the wave of a lane is (threadIdx.y * 64 + threadIdx.x) >> 6.  Every lane of the workgroup calls, and a
 // kernel calls each function once (its four LDS words are not fenced against a second round).
 //
-// Order of additions (the contract of the sums; tests/helpers.py restates it and
-// test_gpu_parity.py::test_history_sums_in_the_stated_order holds history_kernel to it bit for bit):
+// Order of additions (the contract of the sums; tests/helpers.py restates it,
+// test_gpu_parity.py::test_history_sums_in_the_stated_order holds history_kernel to it bit for bit and
+// test_gpu_turbulence_shapes.py the turbulence sums and the user history of kernels_turb.hip):
 //   1. wave_sum: lane l adds lane l + off to itself, off = 32, 16, 8, 4, 2, 1;
 //   2. wg_sums_to_row: (w0 + w1) + (w2 + w3) over the four waves' results;
+//   2a. mid_sum_kernel (kernels_turb.hip; only where a launch leaves more than 2048 rows): with chunk = ceil(rows / 256),
+//      workgroup g of 256 owns the rows [g * chunk, min((g + 1) * chunk, rows)); its thread t of 256 adds the rows
+//      lo + t, lo + t + 256, ... to 0.0 in that order, then steps 1 and 2 over the 256 threads.  A workgroup whose share
+//      is empty leaves 0.0, and step 3 runs over these 256 rows instead;
 //   3. final_sum_kernel: lane l of 32 adds the rows l, l + 32, l + 64, ... to 0.0 in that order, then the same tree at
 //      width 32, off = 16 .. 1.
 // Minima and maxima do not depend on an order.

@@ -249,6 +249,57 @@ def final_sum32(partial):
     return wave_tree_sum(s)
 
 
+def mid_sum256(partial):
+    """[nwg, nq] rows of partials -> [256, nq], mid_sum_kernel (csrc/kernels_turb.hip) restated: chunk = ceil(nwg / 256),
+    group g owns the rows [g * chunk, min((g + 1) * chunk, nwg)), its thread t of 256 adds the rows lo + t, lo + t + 256,
+    ... to 0.0 in turn, then the workgroup's tree (wave_tree_sum, wg_pair_sum).  Groups past the last row give 0.0."""
+    nwg, nq = partial.shape
+    chunk = -(-nwg // 256)
+    lo = np.arange(256)[:, None] * chunk
+    hi = np.minimum(lo + chunk, nwg)
+    h = np.zeros((256, 256, nq))
+    for p in range(-(-chunk // 256)):
+        w = lo + np.arange(256)[None, :] + 256 * p
+        ok = w < hi
+        h[ok] += partial[w[ok]]
+    return wg_pair_sum(np.moveaxis(wave_tree_sum(np.moveaxis(h.reshape(256, 4, 64, nq), 2, -1)), 1, -1))
+
+
+def rect_lanes(nb, nx):
+    """Interior cell -> (workgroup, lane of 256) as rect_ij / rect_grid (csrc/apk_internal.hpp) hand them out for a
+    launch over rect_grid(nx1, nx2, nx3 * nblocks): (64, 4) tiles of a plane where nx1 >= 48, else the plane's rows
+    flattened over 256 lanes.  Returns (wg, lane, nwg); wg and lane are [nb, nx3, nx2, nx1]."""
+    n1, n2, n3 = nx
+    B, K, J, I = np.meshgrid(np.arange(nb), np.arange(n3), np.arange(n2), np.arange(n1), indexing="ij")
+    if n1 >= 48:
+        gx, gy = (n1 + 63) // 64, (n2 + 3) // 4
+        bx, by, tid = I // 64, J // 4, (J % 4) * 64 + I % 64
+    else:
+        gx, gy = 1, (n1 * n2 + 255) // 256
+        f = J * n1 + I
+        bx, by, tid = 0 * f, f // 256, f % 256
+    wg = ((B * n3 + K) * gy + by) * gx + bx
+    return wg, tid, nb * n3 * gy * gx
+
+
+def wg_partial_sums(h, nx):
+    """[nq, nb, nx3, nx2, nx1] per-cell terms -> [nwg, nq]: the row every workgroup of such a launch leaves behind
+    (wg_sums_to_row), lanes without a cell adding 0.0.  One quantity at a time: a pack of 65540 workgroups fits."""
+    nq, nb = h.shape[:2]
+    wg, tid, nwg = rect_lanes(nb, nx)
+    live = int(tid.max()) // 64 + 1  # (waves past the last cell's: all lanes 0.0, so their tree gives 0.0)
+    out = np.zeros((nwg, nq))
+    for q in range(nq):
+        if not h[q].any():  # (a column of zeros, e.g. the magnetic sums of an Euler run)
+            continue
+        lanes = np.zeros((nwg, live * 64))
+        lanes[wg, tid] = h[q]
+        waves = np.zeros((nwg, 4))
+        waves[:, :live] = wave_tree_sum(lanes.reshape(nwg, live, 64))
+        out[:, q] = wg_pair_sum(waves)
+    return out
+
+
 def interior(a, nx, ng):
     """Slice the interior cells of [..., nvar, Nk, Nj, Ni]."""
     sk = slice(ng, ng + nx[2]) if nx[2] > 1 else slice(0, 1)

@@ -477,16 +477,8 @@ def _history_lane_terms(fluid, nx, ng, dx, cons):
         assert np.all(abs_b != 0)
         h[7] = 0.5 * np.sqrt(sqr(dx[0]) + sqr(dx[1]) + sqr(dx[2])) * np.abs(divb) / abs_b * vol
     # lanes: (64, 4) tiles of a plane where nx1 >= 48, else the plane's rows flattened over 256 lanes
-    B, K, J, I = np.meshgrid(np.arange(nb), np.arange(n3), np.arange(n2), np.arange(n1), indexing="ij")
-    if n1 >= 48:
-        gx, gy = (n1 + 63) // 64, (n2 + 3) // 4
-        bx, by, tid = I // 64, J // 4, (J % 4) * 64 + I % 64
-    else:
-        gx, gy = 1, (n1 * n2 + 255) // 256
-        f = J * n1 + I
-        bx, by, tid = 0 * f, f // 256, f % 256
-    wg = ((B * n3 + K) * gy + by) * gx + bx
-    lanes = np.zeros((nb * n3 * gy * gx, 256, 8))
+    wg, tid, nwg = H.rect_lanes(nb, nx)
+    lanes = np.zeros((nwg, 256, 8))
     lanes[wg, tid] = np.moveaxis(h, 0, -1)
     return lanes.reshape(-1, 4, 64, 8)
 
